@@ -12,6 +12,10 @@ spectrogram -> posterior encoder -> flow (src forward, tgt reverse) -> HiFi-GAN 
 in HBM, including the per-batch RCCL broadcast of the packed src/tgt speaker embeddings when N > 1.
 Prints ONE JSON line on rank 0 (contract in the task statement): value = aggregate real-time factor
 (audio seconds produced per wall second over all GPUs).
+
+A plain run only sets up, warms up, times the --steps steps (--dump-outputs DIR: writes what the last one returned)
+and prints the line.  --full adds everything else after the timed region: roofline and per-kernel-group times, the
+PCIe-inclusive rate, the opt-in split-precision line, configs[3] / [4], the oracle self-check and the CPU baseline.
 """
 import argparse
 import json
@@ -253,10 +257,12 @@ def cpu_baseline(sd, cfg, seconds, budget_s=20.0, want_reference=True, batch32=N
 
 def self_launch(n):
     """``python bench.py --gpus N`` (N > 1) started WITHOUT torch.distributed.run -- the way the driver starts the
-    1-GPU line: re-execute this same command line under ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N``
-    on a free local port, one rank per GPU, instead of failing on the launch convention.  The torchrun path itself
-    (WORLD_SIZE set by the launcher) never comes here."""
+    1-GPU line: run this same command line under ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N``
+    on a free local port, one rank per GPU, instead of failing on the launch convention, and return its exit code.
+    The launcher is a fresh child process (this one has already asked the HIP runtime for the device count, so it is
+    not replaced in place).  The torchrun path itself (WORLD_SIZE set by the launcher) never comes here."""
     import socket
+    import subprocess
     with socket.socket() as sock:
         sock.bind(("127.0.0.1", 0))
         port = sock.getsockname()[1]
@@ -266,7 +272,7 @@ def self_launch(n):
     print(f"bench.py: --gpus {n} without a launcher; re-executing under torch.distributed.run on port {port}",
           file=sys.stderr, flush=True)
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    return subprocess.call(cmd)
 
 
 def distributed_environment(gpu):
@@ -363,6 +369,26 @@ def rank_stats(per_rank_s, steps):
 
 
 PARITY_TOLERANCE = 1e-3      # BASELINE.json north_star: "output within 1e-3 max-abs of reference fp32"
+DUMP_BUDGET_BYTES = 64 * 10**6
+NOISE_SEED = 2024
+
+
+def dump_outputs(outdir, arrays, budget=DUMP_BUDGET_BYTES):
+    """``--dump-outputs DIR``: the arrays the timed path returned in its last step, each as DIR/<name>.npy in float32,
+    so that two builds can be compared output for output.  When together they exceed ``budget`` bytes, every array is
+    cut to the same fraction of its elements, chosen by a fixed seed (the same positions on every run with the same
+    arguments, flattened in C order)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    host = {name: t.detach().float().cpu().numpy() for name, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    budget -= 256 * len(host)                     # room for the .npy headers
+    for k, (name, a) in enumerate(host.items()):
+        if total > budget:
+            keep = max(1, a.size * budget // total)
+            idx = np.sort(np.random.default_rng(k).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def parity_of_item(model, sd, cfg, wave, se, tau, hop_cfg, item=0, seed=77):
@@ -582,9 +608,11 @@ def dry_run(args):
     if dist_on:
         names = [None] * world
         dist.all_gather_object(names, f"cpu (rank {rank})")
-    # the per-rank diagnostics of the measured run, with stand-in figures (same collective, same shape)
-    diag = gather_rank_diagnostics({"rank": rank, "mrf_ms": float(rank), "hbm_resident_bytes": 0, "device": f"cpu (rank {rank})"},
-                                   world, dist_on)
+    # the per-rank diagnostics of the measured --full run, with stand-in figures (same collective, same shape)
+    diag = None
+    if args.full:
+        diag = gather_rank_diagnostics({"rank": rank, "mrf_ms": float(rank), "hbm_resident_bytes": 0,
+                                        "device": f"cpu (rank {rank})"}, world, dist_on)
     line = None
     if rank == 0:
         line = {"metric": "real_time_factor", "value": None, "unit": "x real-time (audio s / wall s)",
@@ -594,18 +622,20 @@ def dry_run(args):
                 "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
                 "dry_run": True, "broadcast_consistent": ok,
                 "distributed": dict({"process_group": dist_on, "backend": dist.get_backend() if dist_on else None,
-                                     "rccl_ranks": 0, "devices": names, "per_rank": diag}, **distributed_environment(False)),
-                # the shape of the measured line's roofline object; no kernel ran, so no figures
-                "roofline": {"bound": "mfma", "achieved": None, "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                             "frac": None, "traffic": None},
+                                     "rccl_ranks": 0, "devices": names}, **distributed_environment(False)),
                 "config": {"workload": "control-flow rehearsal on CPU + gloo, no conversion",
                            "batch_per_gpu": B, "global_batch": B * world}}
+        if args.full:
+            line["distributed"]["per_rank"] = diag
+            # the shape of the measured line's roofline object; no kernel ran, so no figures
+            line["roofline"] = {"bound": "mfma", "achieved": None, "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                "frac": None, "traffic": None}
     if dist_on:
         dist.destroy_process_group()
     if rank == 0:
         # rank 0's CPU-baseline leg exactly where the measured run has it -- after the group is gone -- on a
         # 0.25 s utterance so that the rehearsal stays a rehearsal
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             from openvoice_amd.params import synthetic_state_dict
             from openvoice_amd.utils import default_converter_hparams
             hps = default_converter_hparams("v2")
@@ -623,6 +653,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=32, help="utterances per GPU")
     ap.add_argument("--seconds", type=float, default=10.0, help="utterance length")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure (off by default: a plain run sets up, warms up, times "
+                         "--steps steps and prints the line): the MFMA roofline and per-kernel-group times of one extra "
+                         "event-bracketed step, the PCIe-inclusive rate, the opt-in split-precision line, BASELINE.json "
+                         "configs[3] / [4], the oracle self-check and the CPU baseline; the --no-* options below thin it")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned (o_hat, y_mask, z, z_p, z_hat) as "
+                         "DIR/<name>.npy in float32, at most 64 MB in all (a fixed, seeded sample beyond that)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=20.0,
                     help="seconds of CPU baseline sampling at B = 1 on all threads (plus one 1-thread utterance)")
@@ -647,7 +685,7 @@ def main():
     ap.add_argument("--split-products", type=int, default=6, choices=(6, 3),
                     help="plane products per fp32 product with --split-bf16x3: 6 (fp32 level) or 3 (16-bit operands)")
     ap.add_argument("--no-opt-in", action="store_true",
-                    help="skip the short measurements the default line carries beside the contract figures: 'opt_in_split_bf16x3', "
+                    help="skip the short measurements the --full line carries beside the contract figures: 'opt_in_split_bf16x3', "
                          "'config_tts_v1' (BASELINE.json configs[3]) and 'config_bf16_decoder' (configs[4])")
     ap.add_argument("--pmc-calibration", action="store_true",
                     help="after the timed region, run three 1 GiB device-to-device copies (a known byte count) "
@@ -713,10 +751,16 @@ def main():
                                                       256, dev)
         spec = spectrogram_torch(wave, d.filter_length, d.sampling_rate, d.hop_length, d.win_length, center=False)
         assert spec.shape[2] == n_frames
-        o_hat, _, _ = model.voice_conversion(spec, lengths, src_se, tgt_se, tau=0.3)
-        return o_hat, spec.shape[2]
+        o_hat, y_mask, (z, z_p, z_hat) = model.voice_conversion(spec, lengths, src_se, tgt_se, tau=0.3)
+        return o_hat, spec.shape[2], (y_mask, z, z_p, z_hat)
 
-    elapsed, per_rank, (o_hat, frames) = timed_steps(step, args, world, dev)
+    # every step draws its noise from torch's generator on the device: seeded here, outside the timed region, so that
+    # the same arguments give the same outputs from run to run (--dump-outputs)
+    torch.cuda.manual_seed(NOISE_SEED)
+    elapsed, per_rank, (o_hat, frames, rest) = timed_steps(step, args, world, dev)
+    if args.dump_outputs and rank == 0:
+        # before any other step: the engine reuses its buffers
+        dump_outputs(args.dump_outputs, dict(zip(("o_hat", "y_mask", "z", "z_p", "z_hat"), (o_hat,) + rest)))
     dist_on = dist.is_available() and dist.is_initialized()
     devices = [torch.cuda.get_device_name(dev)]
     if dist_on:                      # every rank's device, gathered over the process group (a collective: all ranks)
@@ -724,79 +768,81 @@ def main():
         dist.all_gather_object(devices, torch.cuda.get_device_name(dev))
     assert o_hat.shape == (B, 1, frames * engine.total_upsample) and bool(torch.isfinite(o_hat).all())
 
-    # PCIe-inclusive rate, reported beside `value` (never as it): the same step with the waveforms coming from
-    # pinned host memory and the converted audio returned to pinned host memory, as a caller holding host buffers
-    # sees it.  Two steps, after the timed region; any failure here leaves the contract line untouched.
-    pcie = None
-    try:
-        if world > 1:       # N = 1 only: a one-sided failure here must never strand the other ranks in a collective
-            raise RuntimeError("measured at --gpus 1 only")
-        host_in = wave.cpu().pin_memory()
-        host_out = torch.empty(o_hat.shape, dtype=o_hat.dtype).pin_memory()
-        dev_wave = wave
+    # ---- --full only from here to the line: what the headline figure does not need ----
+    if args.full:
+        # PCIe-inclusive rate, reported beside `value` (never as it): the same step with the waveforms coming from
+        # pinned host memory and the converted audio returned to pinned host memory, as a caller holding host buffers
+        # sees it.  Two steps, after the timed region; any failure here leaves the contract line untouched.
+        pcie = None
+        try:
+            if world > 1:       # N = 1 only: a one-sided failure here must never strand the other ranks in a collective
+                raise RuntimeError("measured at --gpus 1 only")
+            host_in = wave.cpu().pin_memory()
+            host_out = torch.empty(o_hat.shape, dtype=o_hat.dtype).pin_memory()
+            dev_wave = wave
 
-        def pcie_step():
-            dev_wave.copy_(host_in, non_blocking=True)
-            o, _ = step()
-            host_out.copy_(o, non_blocking=True)
+            def pcie_step():
+                dev_wave.copy_(host_in, non_blocking=True)
+                o = step()[0]
+                host_out.copy_(o, non_blocking=True)
 
-        pcie_step()
-        torch.cuda.synchronize()
-        tp = time.perf_counter()
-        for _ in range(2):
             pcie_step()
-        torch.cuda.synchronize()
-        pcie_ms = (time.perf_counter() - tp) / 2 * 1e3
-        pcie = {"ms_per_step": round(pcie_ms, 3), "value": round(B * args.seconds / (pcie_ms * 1e-3), 2),
-                "host_bytes_per_step": int(host_in.numel() * 4 + host_out.numel() * 4),
-                "note": "per rank; pinned host -> HBM -> convert -> pinned host, copies on the compute stream"}
-    except Exception as exc:   # noqa: BLE001 -- diagnostics only
-        pcie = {"error": repr(exc)[:200]}
+            torch.cuda.synchronize()
+            tp = time.perf_counter()
+            for _ in range(2):
+                pcie_step()
+            torch.cuda.synchronize()
+            pcie_ms = (time.perf_counter() - tp) / 2 * 1e3
+            pcie = {"ms_per_step": round(pcie_ms, 3), "value": round(B * args.seconds / (pcie_ms * 1e-3), 2),
+                    "host_bytes_per_step": int(host_in.numel() * 4 + host_out.numel() * 4),
+                    "note": "per rank; pinned host -> HBM -> convert -> pinned host, copies on the compute stream"}
+        except Exception as exc:   # noqa: BLE001 -- diagnostics only
+            pcie = {"error": repr(exc)[:200]}
 
-    # ---- roofline of the dominant kernel: the MFMA conv family on the 72 MRF (ResBlock) convs ----
-    engine.profile = []
-    step()
-    torch.cuda.synchronize()
-    prof, engine.profile = engine.profile, None
-    by_tag = {}
-    wino_n, wino_alg, wino_s = 0, 0.0, 0.0
-    for r in prof:
-        tag, flops, e0, e1 = r[:4]
-        rec = by_tag.setdefault(tag, [0, 0.0, 0.0, 0.0])
-        dt = e0.elapsed_time(e1) * 1e-3
-        rec[0] += 1
-        rec[1] += flops
-        rec[2] += dt
-        rec[3] += r[4] if len(r) > 4 else flops      # FLOPs the kernels EXECUTE (Winograd-domain launches: fewer)
-        if len(r) > 4:
-            wino_n, wino_alg, wino_s = wino_n + 1, wino_alg + flops, wino_s + dt
-    if args.bf16_generator:
-        from openvoice_amd.bf16 import generator_alg_bytes
-        n_mrf, f_mrf, t_mrf, x_mrf = by_tag["gen_bf16"][0], 0.0, by_tag["gen_bf16"][2], 0.0
-        gen_bytes = generator_alg_bytes(cfg, B, frames)
-    else:
-        n_mrf, f_mrf, t_mrf, x_mrf = by_tag["mrf"]
-    # priced on the FLOPs the matrix pipe executes: the Winograd-domain launches execute 6 / 16 / 23 of the 12 / 28 / 44 products of their
-    # algorithmic FLOPs, so the fraction of the fp32 MFMA peak stays a utilisation (<= 1); what the same time would
-    # mean for the direct form is `algorithmic_equivalent_tflops`
-    achieved = x_mrf / t_mrf / 1e12
-    alg_equiv = f_mrf / t_mrf / 1e12
-    from openvoice_amd.engine import PAIR_POLICY
-    fused_set = PAIR_POLICY if engine.fuse_pairs else ()
-    traffic, traffic_note = pmc_traffic(B, frames, engine.fuse_pairs, PAIR_POLICY, n_mrf, engine.chain_streams)
-    alg_bytes = mrf_alg_bytes_per_launch(cfg, B, frames, fused_set)
-    all_flops = sum(r[1] for r in by_tag.values())
-    all_conv_s = sum(r[2] for r in by_tag.values())
-    # every rank's own figures on rank 0's line (a collective when a group exists: all ranks come through here)
-    rank_diag = gather_rank_diagnostics(
-        {"rank": rank, "device": torch.cuda.get_device_name(dev), "mrf_ms": round(t_mrf * 1e3, 3),
-         "by_kernel_group_ms": {k: round(v[2] * 1e3, 3) for k, v in sorted(by_tag.items())},
-         "hbm_resident_bytes": int(torch.cuda.memory_allocated(dev)), "hbm_reserved_bytes": int(torch.cuda.memory_reserved(dev)),
-         "hbm_total_bytes": int(torch.cuda.get_device_properties(dev).total_memory)}, world, dist_on)
+        # ---- roofline of the dominant kernel: the MFMA conv family on the 72 MRF (ResBlock) convs ----
+        engine.profile = []
+        step()
+        torch.cuda.synchronize()
+        prof, engine.profile = engine.profile, None
+        by_tag = {}
+        wino_n, wino_alg, wino_s = 0, 0.0, 0.0
+        for r in prof:
+            tag, flops, e0, e1 = r[:4]
+            rec = by_tag.setdefault(tag, [0, 0.0, 0.0, 0.0])
+            dt = e0.elapsed_time(e1) * 1e-3
+            rec[0] += 1
+            rec[1] += flops
+            rec[2] += dt
+            rec[3] += r[4] if len(r) > 4 else flops      # FLOPs the kernels EXECUTE (Winograd-domain launches: fewer)
+            if len(r) > 4:
+                wino_n, wino_alg, wino_s = wino_n + 1, wino_alg + flops, wino_s + dt
+        if args.bf16_generator:
+            from openvoice_amd.bf16 import generator_alg_bytes
+            n_mrf, f_mrf, t_mrf, x_mrf = by_tag["gen_bf16"][0], 0.0, by_tag["gen_bf16"][2], 0.0
+            gen_bytes = generator_alg_bytes(cfg, B, frames)
+        else:
+            n_mrf, f_mrf, t_mrf, x_mrf = by_tag["mrf"]
+        # priced on the FLOPs the matrix pipe executes: the Winograd-domain launches execute 6 / 16 / 23 of the 12 / 28 / 44 products of their
+        # algorithmic FLOPs, so the fraction of the fp32 MFMA peak stays a utilisation (<= 1); what the same time would
+        # mean for the direct form is `algorithmic_equivalent_tflops`
+        achieved = x_mrf / t_mrf / 1e12
+        alg_equiv = f_mrf / t_mrf / 1e12
+        from openvoice_amd.engine import PAIR_POLICY
+        fused_set = PAIR_POLICY if engine.fuse_pairs else ()
+        traffic, traffic_note = pmc_traffic(B, frames, engine.fuse_pairs, PAIR_POLICY, n_mrf, engine.chain_streams)
+        alg_bytes = mrf_alg_bytes_per_launch(cfg, B, frames, fused_set)
+        all_flops = sum(r[1] for r in by_tag.values())
+        all_conv_s = sum(r[2] for r in by_tag.values())
+        # every rank's own figures on rank 0's line (a collective when a group exists: all ranks come through here)
+        rank_diag = gather_rank_diagnostics(
+            {"rank": rank, "device": torch.cuda.get_device_name(dev), "mrf_ms": round(t_mrf * 1e3, 3),
+             "by_kernel_group_ms": {k: round(v[2] * 1e3, 3) for k, v in sorted(by_tag.items())},
+             "hbm_resident_bytes": int(torch.cuda.memory_allocated(dev)), "hbm_reserved_bytes": int(torch.cuda.memory_reserved(dev)),
+             "hbm_total_bytes": int(torch.cuda.get_device_properties(dev).total_memory)}, world, dist_on)
 
     # ---- opt-in split-precision MRF (never `value`): 3 timed steps + the oracle self-check, after the contract region ----
     opt_in = None
-    if rank == 0 and world == 1 and not (args.split_bf16x3 or args.bf16_generator or args.no_opt_in):
+    if args.full and rank == 0 and world == 1 and not (args.split_bf16x3 or args.bf16_generator or args.no_opt_in):
         try:
             opt_in = split_opt_in(engine, step, model, sd, cfg, wave, se, d, B, args.seconds, no_parity=args.no_parity)
         except Exception as exc:   # noqa: BLE001 -- diagnostics only; the contract line stands on its own
@@ -805,7 +851,7 @@ def main():
 
     # ---- BASELINE.json configs[3] and configs[4], bounded, after the contract region (never inside it, never `value`) ----
     extra_cfgs = {}
-    if rank == 0 and world == 1 and not (args.split_bf16x3 or args.bf16_generator or args.no_opt_in):
+    if args.full and rank == 0 and world == 1 and not (args.split_bf16x3 or args.bf16_generator or args.no_opt_in):
         for key, fn in (("config_tts_v1", config_tts_v1), ("config_bf16_decoder", config_bf16_decoder)):
             t_cfg = time.perf_counter()
             try:
@@ -835,8 +881,8 @@ def main():
             "distributed": dict({"process_group": dist_on, "backend": dist.get_backend() if dist_on else None,
                                  "rccl_ranks": world if dist_on else 0, "devices": devices,
                                  "collectives_per_step": "1 broadcast of [2,256] fp32 (src/tgt se)" if dist_on else "none",
-                                 "binding": __import__("openvoice_amd._lib", fromlist=["binding"]).binding(),
-                                 "per_rank": rank_diag}, **distributed_environment(True)),
+                                 "binding": __import__("openvoice_amd._lib", fromlist=["binding"]).binding()},
+                                **distributed_environment(True)),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32 (enc_q, flow) + bf16 generator, fp32 accumulation" if args.bf16_generator else "f32",
             "data": "synthetic",
@@ -845,40 +891,48 @@ def main():
                        "batch_per_gpu": B, "global_batch": B * world, "utterance_s": args.seconds,
                        "parallelism": f"dp{world} (utterance sharding, RCCL broadcast of src/tgt se)"},
             "per_batch_latency_rtf": round(args.seconds / (ms * 1e-3), 2),
-            "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": FP32_MFMA_PEAK_TFLOPS,
-                         "unit": "TFLOP/s", "frac": round(achieved / FP32_MFMA_PEAK_TFLOPS, 4), "traffic": traffic,
-                         "traffic_unit": "HBM bytes per MRF launch (rocprofv3 PMC, profiles/pmc_traffic_latest.json)",
-                         "traffic_source": traffic_note,
-                         "alg_bytes_per_launch": round(alg_bytes),
-                         "achieved_is": "EXECUTED matrix FLOPs of the MRF launches / their HIP-event time",
-                         "algorithmic_equivalent_tflops": round(alg_equiv, 2),
-                         "executed_over_algorithmic_flops": round(x_mrf / f_mrf, 4) if f_mrf else None,
-                         "winograd": {"launches_per_step": wino_n,
-                                      "share_of_mrf_alg_flops": round(wino_alg / f_mrf, 4) if f_mrf else None,
-                                      "ms_per_step": round(wino_s * 1e3, 3),
-                                      "which": "ResBlock convs with C >= 64 (k = 3 / 7 / 11, dilations 1 / 3 / 5) and the dilation-1 "
-                                               "k = 11 convs at C = 32 (ov_conv1d_wino_f32: nested F(4,3), fp32 MFMA; "
-                                               "engine.wino_policy); every other conv runs the direct implicit GEMM"}
-                         if wino_n else None,
-                         "kernel": "ovkw::conv1d_wino_kernel (Winograd-domain, where it has an instance) + ovk::conv1d_mfma_kernel "
-                                   "(+ ovk::respair_mfma_kernel where a ResBlock pair is one launch) on the MRF ResBlock convs",
-                         "fused_pairs": sorted(f"C={c} k={k}" for c, k in fused_set),
-                         "launches_per_step": n_mrf, "avg_launch_ms": round(t_mrf / n_mrf * 1e3, 4),
-                         "alg_gflop_per_launch": round(f_mrf / n_mrf / 1e9, 2),
-                         "all_conv_alg_tflop_per_step": round(all_flops / 1e12, 3),
-                         "all_conv_ms_per_step": round(all_conv_s * 1e3, 2),
-                         "whole_step_tflops": round(all_flops / (ms * 1e-3) / 1e12, 2)},
-            "by_kernel_group_ms": {k: round(v[2] * 1e3, 3) for k, v in sorted(by_tag.items())},
-            "pcie_inclusive": pcie,
         }
+        if args.full:
+            out["distributed"]["per_rank"] = rank_diag
+            out.update({
+                "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": FP32_MFMA_PEAK_TFLOPS,
+                             "unit": "TFLOP/s", "frac": round(achieved / FP32_MFMA_PEAK_TFLOPS, 4), "traffic": traffic,
+                             "traffic_unit": "HBM bytes per MRF launch (rocprofv3 PMC, profiles/pmc_traffic_latest.json)",
+                             "traffic_source": traffic_note,
+                             "alg_bytes_per_launch": round(alg_bytes),
+                             "achieved_is": "EXECUTED matrix FLOPs of the MRF launches / their HIP-event time",
+                             "algorithmic_equivalent_tflops": round(alg_equiv, 2),
+                             "executed_over_algorithmic_flops": round(x_mrf / f_mrf, 4) if f_mrf else None,
+                             "winograd": {"launches_per_step": wino_n,
+                                          "share_of_mrf_alg_flops": round(wino_alg / f_mrf, 4) if f_mrf else None,
+                                          "ms_per_step": round(wino_s * 1e3, 3),
+                                          "which": "ResBlock convs with C >= 64 (k = 3 / 7 / 11, dilations 1 / 3 / 5) and the dilation-1 "
+                                                   "k = 11 convs at C = 32 (ov_conv1d_wino_f32: nested F(4,3), fp32 MFMA; "
+                                                   "engine.wino_policy); every other conv runs the direct implicit GEMM"}
+                             if wino_n else None,
+                             "kernel": "ovkw::conv1d_wino_kernel (Winograd-domain, where it has an instance) + ovk::conv1d_mfma_kernel "
+                                       "(+ ovk::respair_mfma_kernel where a ResBlock pair is one launch) on the MRF ResBlock convs",
+                             "fused_pairs": sorted(f"C={c} k={k}" for c, k in fused_set),
+                             "launches_per_step": n_mrf, "avg_launch_ms": round(t_mrf / n_mrf * 1e3, 4),
+                             "alg_gflop_per_launch": round(f_mrf / n_mrf / 1e9, 2),
+                             "all_conv_alg_tflop_per_step": round(all_flops / 1e12, 3),
+                             "all_conv_ms_per_step": round(all_conv_s * 1e3, 2),
+                             "whole_step_tflops": round(all_flops / (ms * 1e-3) / 1e12, 2)},
+                "by_kernel_group_ms": {k: round(v[2] * 1e3, 3) for k, v in sorted(by_tag.items())},
+                "pcie_inclusive": pcie,
+            })
         if opt_in is not None:
             out["opt_in_split_bf16x3"] = opt_in
         out.update(extra_cfgs)
         if args.split_bf16x3:
-            n_s, f_s, t_s = by_tag["mrf_split"][:3]
-            pf = args.split_products * f_s / t_s / 1e15
             out["dtype"] = (f"f32 (enc_q, flow, C=32 stage) + bf16x3 split-precision MRF stages ({args.split_products} bf16 plane "
                             f"products per fp32 product, fp32 accumulation)")
+            out["note"] = "opt-in configuration (--split-bf16x3), not the contract line"
+        if args.bf16_generator:
+            out["note"] = "opt-in configuration (--bf16-generator), not the contract line"
+        if args.full and args.split_bf16x3:
+            n_s, f_s, t_s = by_tag["mrf_split"][:3]
+            pf = args.split_products * f_s / t_s / 1e15
             out["roofline"] = {"bound": "mfma", "achieved": round(pf * 1e3, 1), "peak": BF16_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
                                "frac": round(pf * 1e3 / BF16_MFMA_PEAK_TFLOPS, 4), "traffic": None,
                                "kernel": "ovks3::conv1d_split3_kernel (v_mfma_f32_16x16x32_bf16) on the MRF convs of the "
@@ -900,8 +954,7 @@ def main():
                     traffic_over_algorithmic=rec["traffic_over_algorithmic"],
                     hbm_tb_per_s=round(rec["bytes_per_step"] / t_s / 1e12, 3),
                     hbm_frac_of_8_tb_per_s=round(rec["bytes_per_step"] / t_s / 8e12, 4))
-            out["note"] = "opt-in configuration (--split-bf16x3), not the contract line"
-        if args.bf16_generator:
+        if args.full and args.bf16_generator:
             # this configuration is judged against BOTH roofs -- HBM bytes (PMC-measured where a
             # counter record of THESE kernel sources at this shape is committed, algorithmic otherwise) / 6.3 and 8.0
             # TB/s, and the generator's FLOPs / the dense bf16 MFMA peak
@@ -919,9 +972,8 @@ def main():
                                         "shader_clock_ghz": rec.get("shader_clock_ghz") if rec else None},
                                "kernel": "ovk16q::respair2_bf16_kernel + ovk16::conv1d_bf16cl_kernel (whole bf16 generator)",
                                "generator_ms": round(t_mrf * 1e3, 3)}
-            out["note"] = "opt-in configuration (--bf16-generator), not the contract line"
         rc = 0
-        if not args.no_parity and not args.bf16_generator:   # (with --split-bf16x3: the split path against the oracle)
+        if args.full and not args.no_parity and not args.bf16_generator:   # (--split-bf16x3: the split path vs the oracle)
             try:
                 out["parity"] = parity_of_item(model, sd, cfg, wave, se, 0.3, d)
                 rc = 0 if out["parity"]["ok"] else 3
@@ -935,7 +987,7 @@ def main():
     if dist_on:
         dist.destroy_process_group()
     if rank == 0:
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(sd, cfg, args.seconds, args.cpu_budget, batch32=args.cpu_batch32)
         print(json.dumps(out), flush=True)
     return rc

@@ -11,5 +11,5 @@ if [ -n "${CONVS:-}" ]; then
   echo "== convs $CONVS"; timeout 500 python tools/bench_convs.py $CONVS 2>&1 | grep -v amdgpu.ids | tee $O/convs.log | tail -${CONVS_TAIL:-60}
 fi
 if [ "${BENCH:-1}" = "1" ]; then
-  echo "== bench"; timeout 400 python bench.py --steps ${STEPS:-5} --warmup 2 --cpu-budget ${CPU_BUDGET:-12} ${BENCH_ARGS:-} 2>&1 | grep -v amdgpu.ids | tail -3 | tee $O/bench.log
+  echo "== bench"; timeout 400 python bench.py --full --steps ${STEPS:-5} --warmup 2 --cpu-budget ${CPU_BUDGET:-12} ${BENCH_ARGS:-} 2>&1 | grep -v amdgpu.ids | tail -3 | tee $O/bench.log
 fi

@@ -10,10 +10,10 @@ timeout 900 python -m pytest tests/test_gpu_wino.py -x -q 2>&1 | tail -5 | tee $
 for a in "--C 128 --K 3" "--C 128 --K 7" "--C 128 --K 11" "--C 128 --K 3 --res" "--C 64 --K 11" "--C 64 --K 3" "--C 32 --K 11" "--C 32 --K 11 --dil 5" "--C 128 --K 11 --dil 5"; do
   timeout 120 python tools/wino_phases.py $a 2>&1 | tail -1 | tee -a $O/phases.jsonl; done
 timeout 600 python tools/bench_wino.py --shapes --res --out $O/wino_table.json 2>&1 | grep -v "^{" | tee $O/wino_table.txt
-timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-opt-in 2>$O/bench.err | tail -1 > $O/bench.json; cut -c1-400 $O/bench.json
+timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-opt-in 2>$O/bench.err | tail -1 > $O/bench.json; cut -c1-400 $O/bench.json
 timeout 300 python -c "
 import sys, runpy
 import openvoice_amd.engine as e
 e.PAIR_POLICY = {(32, 3), (32, 7)}
-sys.argv = ['bench.py', '--steps', '10', '--warmup', '3', '--no-cpu-baseline', '--no-opt-in']
+sys.argv = ['bench.py', '--full', '--steps', '10', '--warmup', '3', '--no-cpu-baseline', '--no-opt-in']
 runpy.run_path('bench.py', run_name='__main__')" 2>$O/bench_c64k3_wino.err | tail -1 > $O/bench_c64k3_wino.json; cut -c1-400 $O/bench_c64k3_wino.json

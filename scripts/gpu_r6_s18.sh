@@ -7,4 +7,4 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 O=gpurun_out/r6s18; mkdir -p $O
 timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | tail -6 | tee $O/pytest_gpu.txt
 timeout 200 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee $O/smoke.txt
-timeout 900 python bench.py 2>$O/bench.err | tail -1 > $O/bench.json; cut -c1-300 $O/bench.json
+timeout 900 python bench.py --full 2>$O/bench.err | tail -1 > $O/bench.json; cut -c1-300 $O/bench.json

@@ -5,7 +5,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 O=gpurun_out/r6s34; mkdir -p $O
-timeout 300 python bench.py --split-bf16x3 --steps 6 --warmup 2 --no-cpu-baseline 2>$O/split_all.err | tail -1 > $O/split_all.json; cut -c1-330 $O/split_all.json
+timeout 300 python bench.py --full --split-bf16x3 --steps 6 --warmup 2 --no-cpu-baseline 2>$O/split_all.err | tail -1 > $O/split_all.json; cut -c1-330 $O/split_all.json
 timeout 300 python -c "
 import sys, runpy
 import openvoice_amd.engine as e
@@ -16,5 +16,5 @@ def patched(self, enable=True, products=6):
         self.split_resblocks[2] = None
     return r
 e.ConverterEngine.use_split_bf16x3 = patched
-sys.argv = ['bench.py', '--split-bf16x3', '--steps', '6', '--warmup', '2', '--no-cpu-baseline']
+sys.argv = ['bench.py', '--full', '--split-bf16x3', '--steps', '6', '--warmup', '2', '--no-cpu-baseline']
 runpy.run_path('bench.py', run_name='__main__')" 2>$O/split_stages01.err | tail -1 > $O/split_stages01.json; cut -c1-330 $O/split_stages01.json

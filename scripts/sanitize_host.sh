@@ -5,7 +5,9 @@
 #   bash scripts/sanitize_host.sh
 set -eu
 cd "$(dirname "$0")/.."
-make -C openvoice_amd/csrc -j"$(nproc)" sanitize > /tmp/ov_sanitize_build.log 2>&1 || { tail -20 /tmp/ov_sanitize_build.log; exit 1; }
+LOG=$(mktemp)      # a private file: a fixed name in a shared /tmp may belong to another user
+trap 'rm -f "$LOG"' EXIT
+make -C openvoice_amd/csrc -j"$(nproc)" sanitize > "$LOG" 2>&1 || { tail -20 "$LOG"; exit 1; }
 RT=$(find /opt/rocm/lib/llvm/lib/clang -name 'libclang_rt.asan-x86_64.so' | head -1)
 [ -n "$RT" ] || { echo "ASan runtime not found under /opt/rocm/lib/llvm"; exit 1; }
 export LD_PRELOAD="$RT"

@@ -29,7 +29,7 @@ def _lines(stdout):
 def test_bench_multi_rank_control_flow_on_gloo(n):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(REPO, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1", "--dry-run"]
+           os.path.join(REPO, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1", "--dry-run", "--full"]
     env = dict(os.environ, OMP_NUM_THREADS="1")
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=280, env=env, cwd=REPO)
     assert res.returncode == 0, res.stderr[-2000:]
@@ -42,7 +42,7 @@ def test_bench_multi_rank_control_flow_on_gloo(n):
     assert rec["ms_per_step"] >= 0
     pr = rec["per_rank_ms_per_step"]         # every rank's own time: a straggler shows up as max >> min
     assert len(pr["ranks"]) == n and pr["min"] <= pr["max"] <= rec["ms_per_step"] + 1e-3
-    # the N > 1 line is COMPLETE: roofline-shaped object, the CPU baseline (timed on rank 0 after the process group is
+    # the N > 1 --full line is COMPLETE: roofline-shaped object, the CPU baseline (timed on rank 0 after the process group is
     # gone), every rank's device gathered over the group
     assert set(rec["roofline"]) >= {"bound", "achieved", "peak", "unit", "frac", "traffic"}
     cb = rec["cpu_baseline"]
@@ -62,6 +62,9 @@ def test_bench_single_rank_dry_run_needs_no_process_group():
     assert res.returncode == 0, res.stderr[-2000:]
     (rec,) = _lines(res.stdout)
     assert rec["n_gpus"] == 1 and rec["dry_run"] is True
+    # a plain run carries the headline figures only: what --full adds is not measured
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(rec)
+    assert not {"cpu_baseline", "roofline", "parity"} & set(rec) and "per_rank" not in rec["distributed"]
 
 
 def test_force_dist_runs_the_collectives_at_one_rank():
@@ -99,7 +102,7 @@ def test_plain_python_launch_with_gpus_2_starts_its_own_ranks():
                         "GROUP_RANK", "TORCHELASTIC_RUN_ID")}
     env["OMP_NUM_THREADS"] = "1"
     res = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--dry-run", "--gpus", "2", "--steps", "2",
-                          "--warmup", "1"], capture_output=True, text=True, timeout=280, env=env, cwd=REPO)
+                          "--warmup", "1", "--full"], capture_output=True, text=True, timeout=280, env=env, cwd=REPO)
     assert res.returncode == 0, res.stderr[-2000:]
     assert "re-executing under torch.distributed.run" in res.stderr
     (rec,) = _lines(res.stdout)
@@ -121,3 +124,21 @@ def test_more_ranks_than_devices_is_one_json_error_line_before_any_launch():
     assert "re-executing" not in res.stderr
     (rec,) = _lines(res.stdout)
     assert "device_count() = 0" in rec["error"] and rec["n_gpus"] == 8 and rec["value"] is None
+
+
+def test_dump_outputs_float32_within_budget_and_repeatable(tmp_path):
+    """--dump-outputs: every array the timed path returned as <name>.npy in float32; above the byte budget each is cut
+    to the same fraction of its elements at seeded positions, the same on every run."""
+    import numpy as np
+    import torch
+    import bench
+    arrays = {"a": torch.arange(1000, dtype=torch.float32).reshape(10, 100), "b": torch.ones(3, 5, dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    a, b = (np.load(tmp_path / "whole" / f"{n}.npy") for n in "ab")
+    assert a.dtype == b.dtype == np.float32 and np.array_equal(a, arrays["a"].numpy()) and b.shape == (3, 5)
+    for run in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / run), arrays, budget=2000)
+    s1, s2 = ({n: np.load(tmp_path / run / f"{n}.npy") for n in "ab"} for run in ("s1", "s2"))
+    assert sum(os.path.getsize(tmp_path / "s1" / f"{n}.npy") for n in "ab") <= 2000    # files, headers included
+    assert all(np.array_equal(s1[n], s2[n]) for n in "ab")
+    assert s1["a"].size == 1000 * (2000 - 2 * 256) // 4060 and np.all(np.diff(s1["a"]) > 0) and s1["a"].max() < 1000

@@ -72,7 +72,7 @@ def test_rccl_broadcast_gather_and_sharded_api_at_world_size_1(synth_sd, tmp_pat
 def _bench(extra, launcher):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("OPENVOICE_AMD_BINDING", None)
-    cmd = launcher + [os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+    cmd = launcher + [os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--full",
                       "--no-cpu-baseline"] + extra
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]

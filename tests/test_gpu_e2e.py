@@ -456,9 +456,9 @@ def test_non_released_config_matches_oracle():
         SynthesizerTrn(0, 513, n_speakers=0, **dict(cfg, resblock="2"))
 
 
-def test_convert_and_extract_se_from_an_mp3_file(tmp_path, synth_sd):
+def test_convert_and_extract_se_from_an_mp3_file(tmp_path, golden_dir, synth_sd):
     """BASELINE.json configs[0] AS WRITTEN -- ``ToneColorConverter.convert`` / ``extract_se`` on an MP3 file (reference:
-    openvoice/api.py:123,144 ``librosa.load``): the MP3 that ships inside the image (kaleido's invalid_keypress.mp3, 0.52 s
+    openvoice/api.py:123,144 ``librosa.load``): kaleido's invalid_keypress.mp3 (tests/golden/mp3_invalid_keypress.mp3, 0.52 s
     of joint stereo at 44.1 kHz) goes through ``openvoice_amd.mp3`` (pinned against FFmpeg, tests/test_mp3_cpu.py), the
     channel mean and the kaiser_best resampler to the model rate, then through the HIP path; checked against the CPU
     oracle on the same decoded samples."""
@@ -467,9 +467,7 @@ def test_convert_and_extract_se_from_an_mp3_file(tmp_path, synth_sd):
     from openvoice_amd import api, audio_io
     from openvoice_amd.utils import default_converter_hparams
     from oracle import vc_oracle
-    mp3_path = "/usr/local/lib/python3.10/dist-packages/kaleido/executable/etc/mathjax/extensions/a11y/invalid_keypress.mp3"
-    if not os.path.exists(mp3_path):
-        pytest.skip("the image's bundled MP3 is not on this machine")
+    mp3_path = os.path.join(golden_dir, "mp3_invalid_keypress.mp3")
     hps = default_converter_hparams("v2")
     cfg = {"_version_": "v2", "data": dict(hps.data.items()), "model": dict(hps.model.items())}
     (tmp_path / "config.json").write_text(json.dumps(cfg))

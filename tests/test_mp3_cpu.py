@@ -1,9 +1,9 @@
 """``openvoice_amd.mp3``: the from-scratch MPEG-1 Layer III decoder behind ``audio_io.load`` (reference call sites
 openvoice/api.py:123,144: ``librosa.load`` on resources/*.mp3 -- BASELINE.json configs[0] as written) against golden PCM
 from a real decoder: FFmpeg inside the image's bundled Chromium (oracle/make_mp3_golden.py -> tests/golden/mp3_*.npz).
-``invalid_keypress.mp3`` (stereo / joint stereo, short + long blocks) ships with the image itself and runs everywhere;
-the reference's own files (mono VBR with a LAME header, 128 kbit/s joint stereo without one) exist only where
-/root/reference does -- those cases skip elsewhere.  Bars: identical sample count (gapless trimming included), max-abs
+The input files are stored beside their golden PCM (tests/golden/mp3_<name>.mp3, pinned by sha256): kaleido's
+``invalid_keypress.mp3`` (stereo / joint stereo, short + long blocks) and the reference's own resources/*.mp3 (mono VBR
+with a LAME header, 128 kbit/s joint stereo without one).  Bars: identical sample count (gapless trimming included), max-abs
 1e-4 on three 8192-sample excerpts (FFmpeg's decoder here is the fixed-point one: 16-bit PCM, 1 LSB = 3.05e-5), block RMS
 of the WHOLE file within 2e-5."""
 import hashlib
@@ -15,20 +15,16 @@ import pytest
 from openvoice_amd import audio_io, mp3
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-KEYPRESS = "/usr/local/lib/python3.10/dist-packages/kaleido/executable/etc/mathjax/extensions/a11y/invalid_keypress.mp3"
-CASES = {"invalid_keypress": KEYPRESS}
-CASES.update({n: f"/root/reference/resources/{n}.mp3" for n in ("example_reference", "demo_speaker0", "demo_speaker1",
-                                                                  "demo_speaker2")})
+CASES = {n: os.path.join(GOLDEN, f"mp3_{n}.mp3") for n in ("invalid_keypress", "example_reference", "demo_speaker0",
+                                                             "demo_speaker1", "demo_speaker2")}
 
 
 def _load(name):
     path = CASES[name]
-    if not os.path.exists(path):
-        pytest.skip(f"{path} is not on this machine")
     g = np.load(os.path.join(GOLDEN, f"mp3_{name}.npz"))
-    data = open(path, "rb").read()
-    if hashlib.sha256(data).hexdigest() != str(g["sha256"]):
-        pytest.skip(f"{path} is not the file the golden vectors were made from")
+    with open(path, "rb") as fh:
+        data = fh.read()
+    assert hashlib.sha256(data).hexdigest() == str(g["sha256"]), f"{path} is not the file the golden vectors were made from"
     return data, g
 
 

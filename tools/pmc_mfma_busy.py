@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Matrix-pipe utilisation per kernel family from one rocprofv3 --pmc pass over bench.py.
 
-    rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_LDS ... -- python bench.py ...
+    rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_LDS ... -- python bench.py --full ...
     python tools/pmc_mfma_busy.py DIR > profiles/rNN_pmc_mfma_busy.txt
 
 SQ_VALU_MFMA_BUSY_CYCLES sums, over the 1024 SIMDs, the cycles a matrix instruction occupies the pipe (64 per

@@ -3,7 +3,7 @@
 
     python tools/pmc_traffic.py FETCH_DIR WRITE_DIR [STEPS_IN_PASS [BATCH [FRAMES]]] > profiles/rNN_pmc_traffic.json
 
-STEPS_IN_PASS = conversions the profiled command ran (bench.py --steps 1 --warmup 0: the timed step, the two
+STEPS_IN_PASS = conversions the profiled command ran (bench.py --full --steps 1 --warmup 0: the timed step, the two
 PCIe-inclusive steps + their warm-up, the roofline step = 5); with it the record carries the MRF launches per step,
 which bench.py compares with what it launches itself.
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """HBM traffic of the split-precision conv launches (ovks3::conv1d_split3_kernel) from two rocprofv3 --pmc passes of
-`bench.py --split-bf16x3` (FETCH_SIZE, WRITE_SIZE), per kernel instance and per conversion, next to the ALGORITHMIC bytes:
+`bench.py --full --split-bf16x3` (FETCH_SIZE, WRITE_SIZE), per kernel instance and per conversion, next to the ALGORITHMIC bytes:
 every tensor element is three bf16 planes = 6 bytes; a launch reads its input once, its residual once (residual form) and
 writes its output once -- B x L x C x 6 bytes each; the packed weights (C x C x K x 6 bytes, L2-resident) are not counted.
 
