@@ -250,6 +250,26 @@ int ov_wn_layer_tile(int B, int T, int width);
 int ov_frame_hops_f32(const float* wave, float* hops, int B, int N, int hop, int pad, int U, int ld,
                       ov_stream_t stream);
 
+/* Windowed framing for long recordings (openvoice_amd/longform.py), replacing for each window the reflect pad + framing of
+ * the reference's one-pass spectrogram_torch (openvoice/mel_processing.py:54-72, called at openvoice/api.py:145):
+ *   hops[w][c][u] = ypad[hop * (first_frame[w] + u) + c],  u < U,
+ * ypad = the ONE long waveform wave[n_samples] reflect-padded by `pad` samples at its two true ends (zero beyond), so
+ * that window w's plane is the slice [first_frame[w], first_frame[w] + U) of ov_frame_hops_f32's whole-file plane and
+ * the K = 4 framing conv with OV_EPI_MAGNITUDE yields spectrogram(whole)[:, :, f0 : f0 + U - 3] bit for bit without
+ * the whole-file spectrogram.  first_frame is a DEVICE int64 [W]; hops is [W][hop][ld], ld % 4 == 0 and 16-byte
+ * aligned (stored as 16-byte vectors; columns [U, U rounded up to 4) are written as 0).  Sample indices are 64-bit.
+ * ABI 2.10. */
+int ov_frame_hops_windows_f32(const float* wave, int64_t n_samples, const int64_t* first_frame, int W, int hop, int pad,
+                              int U, int ld, float* hops, ov_stream_t stream);
+/* The cores of W windows into the long output (the reference writes the one-pass o_hat, openvoice/api.py:146-156):
+ * windows is a DEVICE int64 [W][3] of (first_frame, core_lo, core_hi) in frames, o_hat [W][Tw * spf] the windows'
+ * generator outputs (spf samples per frame);
+ *   out[(core_lo - out_frame0) * spf + s] = o_hat[w][(core_lo - first_frame) * spf + s],  s < (core_hi - core_lo) * spf.
+ * A record whose core is not inside its window or whose samples would land outside [0, out_len) copies nothing.
+ * 64-bit output offsets.  ABI 2.10. */
+int ov_stitch_window_cores_f32(const float* o_hat, const int64_t* windows, int W, int Tw, int spf, float* out,
+                               int64_t out_len, int64_t out_frame0, ov_stream_t stream);
+
 /* Rate conversion at the audio boundary, reference openvoice/api.py:123,144 (``librosa.load(path, sr=...)`` = resampy's
  * kaiser_best band-limited sinc interpolation): a polyphase FIR over a mono waveform,
  *   y[t] = sum_{j < 2 taps} h[t % P][j] * x[(t * Q) / P - taps + 1 + j]        (x = 0 outside [0, n_in))
@@ -578,7 +598,7 @@ int ov_conv1d_wino_pack_f32(const float* w, int Cout, int Cin, int K, float* dst
  * was `reserved`; the struct grew by one pointer at its end).  2.06: ov_polyphase_fir_f32.  2.07: ov_conv1d_wino_f32 (+ _supported, _chunk,
  * _pack_size, _pack_f32).  2.08: ov_conv1d_wino_f32 instances for Cout % 32 == 0 at K = 11 (one 32-row fragment per
  * workgroup; ov_conv1d_wino_chunk(11, 32) = 2 where 2.07 returned 0).  2.09: ov_conv1d_wino_params.out_slope (the field that
- * was `reserved0`: same size and offset, 0 = none).  The Python binding
+ * was `reserved0`: same size and offset, 0 = none).  2.10: ov_frame_hops_windows_f32, ov_stitch_window_cores_f32.  The Python binding
  * refuses a library older than the entry points it calls (openvoice_amd/_lib.py MIN_VERSION). */
 int ov_version(void);
 /* The version THIS header describes.  Parameter structs grow at their END in minor versions (2.04, 2.05, 2.07 did): a
@@ -588,7 +608,7 @@ int ov_version(void);
  * tests/test_abi_cpu.py).  A struct is never reordered and a field never changes meaning within a major version, with
  * one exception stated here: 2.05 renamed ov_wn_layer_params.reserved to row_split AND appended `acts`, so a caller
  * built against 2.04 or older is NOT binary compatible with 2.05+ for that struct. */
-#define OV_ABI_VERSION 209
+#define OV_ABI_VERSION 210
 /* 0 for a production build; non-zero = a measurement build with parts of the kernels compiled out (results are
  * meaningless; openvoice_amd/_lib.py refuses to load it unless OPENVOICE_AMD_ALLOW_EXPERIMENT=1). */
 int ov_build_experiment(void);

@@ -22,7 +22,7 @@ import re
 import numpy as np
 import torch
 
-from . import audio_io, utils
+from . import audio_io, longform, utils
 from .mel_processing import spectrogram_torch
 from .models import SynthesizerTrn
 
@@ -321,15 +321,53 @@ class ToneColorConverter(OpenVoiceBaseClass):
         return out
 
     def convert(self, audio_src_path, src_se, tgt_se, output_path=None, tau=0.3, message="default"):
-        """reference: openvoice/api.py:141-160."""
+        """reference: openvoice/api.py:141-160.  A file at or beyond the one-pass launch limit
+        (``longform.one_pass_limit_frames``: 63 551 frames = 12.3 min for the released configuration), which one pass
+        cannot convert, goes through ``convert_long`` with its defaults; every shorter file is converted in one pass."""
         hps = self.hps
-        y = audio_io.load_to_device(audio_src_path, hps.data.sampling_rate, self.device).unsqueeze(0)
-        o_hat, _ = self.convert_batch(y, src_se, tgt_se, tau=tau)
+        y = audio_io.load_to_device(audio_src_path, hps.data.sampling_rate, self.device)
+        d = hps.data
+        if longform.frames_of(y.numel(), d.filter_length, d.hop_length) >= longform.one_pass_limit_frames(self.model.model_cfg):
+            return self.convert_long(y, src_se, tgt_se, output_path=output_path, tau=tau, message=message)
+        o_hat, _ = self.convert_batch(y.unsqueeze(0), src_se, tgt_se, tau=tau)
         audio = o_hat[0, 0].data.cpu().float().numpy()
         audio = self.add_watermark(audio, message)
         if output_path is None:
             return audio
         audio_io.write(output_path, audio, hps.data.sampling_rate)
+
+    # ---- recordings of any length (openvoice_amd/longform.py) -----------------------------------------------------------
+    def _windowed(self, window_frames, windows_per_launch=1):
+        d = self.hps.data
+        return longform.WindowedConverter(self.model, n_fft=d.filter_length, hop=d.hop_length, window_frames=window_frames,
+                                          windows_per_launch=windows_per_launch, graph=self.use_graphs)
+
+    def convert_long(self, audio_or_path, src_se, tgt_se, output_path=None, tau=0.3, message="default",
+                     window_frames=longform.DEFAULT_WINDOW_FRAMES, windows_per_launch=longform.DEFAULT_WINDOWS_PER_LAUNCH,
+                     noise=None):
+        """``convert`` for a recording of any length: overlapping windows of ``window_frames`` frames, up to
+        ``windows_per_launch`` of them per launch (``longform.WindowedConverter``); device memory is bounded by the window,
+        not by the file.  ``audio_or_path``: a file path, or a 1-D float32 waveform at the model rate (host or device).
+        ``noise``: ``[1, 192, >= T]`` or None -- then ``torch.randn(1, 192, T)`` on the device, the draw of a seeded
+        one-pass ``convert``.  Same return value / file output as ``convert``."""
+        hps = self.hps
+        if isinstance(audio_or_path, (str, os.PathLike)):
+            y = audio_io.load_to_device(audio_or_path, hps.data.sampling_rate, self.device)
+        else:
+            y = torch.as_tensor(audio_or_path, dtype=torch.float32).reshape(-1).to(self.device)
+        o = self._windowed(window_frames, windows_per_launch).convert(y, src_se, tgt_se, tau=tau, noise=noise)
+        audio = o.cpu().numpy()
+        audio = self.add_watermark(audio, message)
+        if output_path is None:
+            return audio
+        audio_io.write(output_path, audio, hps.data.sampling_rate)
+
+    def stream(self, src_se, tgt_se, tau=0.3, window_frames=longform.DEFAULT_STREAM_WINDOW_FRAMES, noise=None):
+        """A ``longform.ConversionStream``: ``push(samples)`` -> newly finished converted samples (device tensor, maybe
+        empty), ``close()`` -> the rest, ``latency_samples`` = ``(window_frames - 1) * hop + n_fft - (n_fft - hop) / 2``.
+        Input at ``hps.data.sampling_rate`` (no resampling inside the stream); ``noise`` ``[1, 192, >= T]`` makes it
+        reproducible.  The output equals ``convert_long(..., windows_per_launch=1)`` of the whole input, bit for bit."""
+        return self._windowed(window_frames, 1).stream(src_se, tgt_se, tau=tau, noise=noise)
 
     # ---- optional watermark hook (third-party model; behaviour of the reference's openvoice/api.py:162-201) ----------
     # The message travels as 32-bit groups, group n in the 16 000-sample window that starts at sample 32 000 n (every other

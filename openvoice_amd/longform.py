@@ -1,0 +1,333 @@
+"""Recordings of any length: overlapping fixed-size windows (``WindowedConverter``) and a streaming converter
+(``ConversionStream``).
+
+The one-pass path (``ToneColorConverter.convert``, reference: openvoice/api.py:141-160) converts a file as ONE utterance:
+its workspace grows with the file (~0.3 MB per frame at batch 1) and the generator's per-utterance 32-bit offsets
+refuse a file of 63 551 frames (12.3 min at 22.05 kHz; ``one_pass_limit_frames``).  The model itself does not need the whole file:
+its receptive field is bounded (``context_frames``), so windows of a fixed length that overlap by that much context
+reproduce the one-pass result on their cores:
+
+* device memory is bounded by the window size, not by the file length, and there is no length ceiling;
+* the same window grid serves a stream whose converted audio comes out after a fixed delay.
+
+A window is a batch item of the unchanged ``voice_conversion`` (reference: openvoice/models.py:492-499) with
+``spec_lengths = Tw``; its spectrogram is framed straight out of the long waveform (``ov_frame_hops_windows_f32`` + the
+K = 4 framing conv of ``mel_processing``), so it equals ``spectrogram_torch(whole)[:, :, f0:f0 + Tw]`` bit for bit; its
+core samples are copied into the long output by ``ov_stitch_window_cores_f32``.
+"""
+import math
+
+import torch
+
+from . import _lib
+from .engine import GENERATOR_MARGIN, generator_margin_frames
+from .params import ENC_Q_KERNEL, ENC_Q_LAYERS, FLOW_KERNEL, FLOW_LAYERS, N_FLOWS
+
+# Defaults, picked with tools/bench_long.py (profiles/r07_bench_long.jsonl, 20 min file): 8192-frame windows (95 s, 3 % of
+# the frames computed twice), two per launch -- 20.7 ms per minute of audio at 3.5 GiB peak, the peak of 4096 x 4 (21.4 ms)
+# and within 7 % of one pass (19.3-20.1 ms); 8192 x 4 gains 2.5 % more for 6.2 GiB.  Beyond the fixed workspace a file
+# costs its waveform, output and noise: 8 bytes per sample + 768 per frame (2.8 KB per frame; one pass: ~0.3 MB).
+DEFAULT_WINDOW_FRAMES = 8192
+DEFAULT_WINDOWS_PER_LAUNCH = 2
+# streams: the window sets the latency (256 Tw + 384 samples): 11.9 s at 1024 frames, ~980x real time
+DEFAULT_STREAM_WINDOW_FRAMES = 1024
+
+
+def winograd_grid_frames(cfg):
+    """Smallest G (frames) such that a shift of the input by a multiple of G frames moves every Winograd tile of every
+    generator stage by a whole number of tiles: a tile covers 4 * dil columns at its stage's rate, so G * rate must be a
+    multiple of lcm(4 * dil) over the dilations of that stage (1 for the convs2, the configured ones for the convs1).
+    15 for the released configurations (stage 0: lcm(4, 12, 20) = 60 columns at 8 columns per frame)."""
+    tile = 4
+    for d in [1] + [v for dl in cfg["resblock_dilation_sizes"] for v in dl]:
+        tile = tile * 4 * d // math.gcd(tile, 4 * d)
+    g, rate = 1, 1
+    for u in cfg["upsample_rates"]:
+        rate *= u
+        gi = tile // math.gcd(tile, rate)
+        g = g * gi // math.gcd(g, gi)
+    return g
+
+
+def context_frames(cfg):
+    """One-sided reach, in frames, of a whole conversion (spectrogram frames + noise -> waveform), rounded up to the
+    window grid (``winograd_grid_frames``): the posterior encoder's WaveNet (reference: openvoice/models.py:442-448,
+    16 layers of kernel 5, dilation 1: 32 frames), the flow forward and reverse (models.py:374-397: 4 couplings x 4 WN
+    layers of kernel 5 each way: 2 x 32) and the generator (``max(GENERATOR_MARGIN, generator_margin_frames(cfg))``: 16).
+    112 -> 120 for the released configurations."""
+    reach = ENC_Q_LAYERS * (ENC_Q_KERNEL - 1) // 2
+    reach += 2 * N_FLOWS * FLOW_LAYERS * (FLOW_KERNEL - 1) // 2
+    reach += max(GENERATOR_MARGIN, generator_margin_frames(cfg))
+    g = winograd_grid_frames(cfg)
+    return -(-reach // g) * g
+
+
+def plan_windows(T, window_frames, context, grid=1):
+    """Window records ``(first_frame, core_lo, core_hi)`` for a file of ``T`` frames.
+
+    * Every window has ``window_frames`` frames (one workspace shape for the whole file), except when
+      ``T <= window_frames``: then one window of ``T`` frames, the one-pass conversion.
+    * The cores partition ``[0, T)`` in order; the first window starts at 0 and the last one ends exactly at ``T``
+      (shifted left over its neighbour: never padded past ``T``, where an unmasked generator would see bias-driven
+      frames instead of the zero padding of a one-pass run).
+    * Every core edge that is not a file edge has at least ``context`` frames of real input beyond it.
+    * Regular window k starts at ``k * core`` (``core`` = the largest multiple of ``grid`` <= ``window_frames - 2 *
+      context``) and keeps ``[k * core + context, (k + 1) * core + context)`` (window 0 from 0); it is in the plan iff
+      it ends before ``T``, so the regular windows of a length are a prefix of those of any longer length (what
+      ``ConversionStream`` relies on).  The last window starts at ``T - window_frames``."""
+    T, Tw, ctx, grid = int(T), int(window_frames), int(context), int(grid)
+    if T < 1:
+        raise ValueError(f"plan_windows: T = {T} frames")
+    if T <= Tw:
+        return [(0, 0, T)]
+    core = window_core(Tw, ctx, grid)
+    plan, k = [], 0
+    while k * core + Tw < T:
+        f0 = k * core
+        plan.append((f0, 0 if k == 0 else f0 + ctx, f0 + ctx + core))
+        k += 1
+    plan.append((T - Tw, plan[-1][2] if plan else 0, T))
+    return plan
+
+
+def window_core(window_frames, context, grid=1):
+    """Frames a regular window keeps: the largest multiple of ``grid`` that leaves ``context`` frames on both sides."""
+    core = (int(window_frames) - 2 * int(context)) // int(grid) * int(grid)
+    if core < 1:
+        raise ValueError(f"window of {window_frames} frames leaves no core with {context} frames of context on each side "
+                         f"(grid {grid}): use at least {2 * context + grid} frames")
+    return core
+
+
+def one_pass_limit_frames(cfg):
+    """Smallest T whose one-pass conversion a generator launch refuses with OV_E_BADARG, from the launchers' own checks:
+    ``ov_conv1d_f32`` once an utterance's input rows (Cin x x_ld) or output rows ((M + 32) x out_ld) span 2^32 elements,
+    ``ov_conv1d_wino_f32`` once Cout x out_ld reaches 2^31.  The binding launch of the released configuration is stage
+    1's ConvTranspose (M = 128 channels x 8 phase rows, out_ld = 64 T): 1056 x 64 T >= 2^32 at T = 63 551 frames
+    (12.3 min at 22.05 kHz); the Winograd bound alone would be 262 144 frames (50.7 min)."""
+    u32, s32 = (1 << 32) - 1, (1 << 31) - 1
+    checks = []                                    # (elements per frame, largest accepted element count)
+    ch, rate = cfg["upsample_initial_channel"], 1
+    for u in cfg["upsample_rates"]:
+        cin, ch = ch, ch // 2
+        checks.append((cin * rate, u32))                         # ConvTranspose (phase conv) input rows
+        rate *= u
+        checks.append(((ch * u + 32) * rate, u32))               # ... its ch x u phase rows of L x u columns
+        checks += [(ch * rate, u32), ((ch + 32) * rate, u32)]    # direct ResBlock convs
+        checks.append((ch * rate, s32))                          # Winograd ResBlock convs
+    return min(bound // per_frame + 1 for per_frame, bound in checks)
+
+
+def frames_of(n_samples, n_fft, hop):
+    """Frames of ``spectrogram_torch`` (center=False, reflect pad (n_fft - hop) / 2) for ``n_samples``."""
+    pad = (n_fft - hop) // 2
+    return (int(n_samples) + 2 * pad - n_fft) // hop + 1
+
+
+class WindowedConverter:
+    """Runs a window plan through ``SynthesizerTrn.voice_conversion`` in launches of up to ``windows_per_launch``
+    windows.  ``graph=True`` replays each launch shape from a captured HIP graph (the window shape is fixed, so a file
+    captures at most three shapes: full batches, the last partial batch, and the single-window case)."""
+
+    def __init__(self, model, n_fft=1024, hop=256, window_frames=DEFAULT_WINDOW_FRAMES,
+                 windows_per_launch=DEFAULT_WINDOWS_PER_LAUNCH, graph=False):
+        self.model = model
+        self.cfg = model.model_cfg
+        self.n_fft, self.hop, self.pad = int(n_fft), int(hop), (int(n_fft) - int(hop)) // 2
+        self.window_frames = int(window_frames)
+        self.windows_per_launch = int(windows_per_launch)
+        if self.windows_per_launch < 1:
+            raise ValueError(f"windows_per_launch = {windows_per_launch}")
+        self.graph = bool(graph)
+        self.grid = winograd_grid_frames(self.cfg)
+        self.context = context_frames(self.cfg)
+        self.core = window_core(self.window_frames, self.context, self.grid)
+        self.spf = 1
+        for u in self.cfg["upsample_rates"]:
+            self.spf *= u
+        self.inter = self.cfg["inter_channels"]
+
+    def _device(self):
+        return next(self.model.parameters()).device
+
+    def _spectrogram(self):
+        from .mel_processing import native_spectrogram
+        return native_spectrogram(self._device(), self.n_fft, self.hop)
+
+    def _launch(self, wave, n_samples, plan_dev, firsts_dev, Tw, src_se, tgt_se, tau, nz, out, out_frame0):
+        """One launch of W = len(firsts_dev) windows: framing -> spectrogram -> voice_conversion -> their cores into
+        ``out`` (``plan_dev`` [W, 3] int64 records, ``nz`` [W, inter, Tw] noise)."""
+        W = firsts_dev.shape[0]
+        spec = self._spectrogram().windows(wave, n_samples, firsts_dev, Tw)
+        lengths = torch.full((W,), Tw, dtype=torch.int64, device=wave.device)
+        o_hat = self.model.voice_conversion(spec, lengths, sid_src=src_se, sid_tgt=tgt_se, tau=tau, noise=nz,
+                                            graph=self.graph)[0]
+        _lib.call("ov_stitch_window_cores_f32", o_hat, plan_dev, W, Tw, self.spf, out, out.numel(), out_frame0)
+
+    @torch.no_grad()
+    def convert(self, wave, src_se, tgt_se, tau=0.3, noise=None):
+        """``wave``: 1-D float32 waveform at the model rate (host or device).  ``noise``: ``[1, inter, >= T]`` or None
+        (then ``torch.randn(1, inter, T)`` on the device: the stream of a seeded one-pass ``convert``).  Returns the
+        converted waveform ``[spf * T]`` on the device (spf = the generator's samples per frame = hop), ``T`` = frames of ``spectrogram_torch``."""
+        dev = self._device()
+        wave = torch.as_tensor(wave, dtype=torch.float32).reshape(-1).to(dev).contiguous()
+        N = wave.numel()
+        if self.pad >= N:
+            raise ValueError("waveform shorter than the reflect padding")       # spectrogram_torch raises too
+        T = frames_of(N, self.n_fft, self.hop)
+        if T < 1:
+            raise ValueError("waveform shorter than one frame")
+        if noise is None:
+            noise = torch.randn(1, self.inter, T, dtype=torch.float32, device=dev)
+        else:
+            noise = noise.to(dev, torch.float32)
+            if noise.dim() != 3 or noise.shape[0] != 1 or noise.shape[1] != self.inter or noise.shape[2] < T:
+                raise ValueError(f"noise must be [1, {self.inter}, >= {T}], got {tuple(noise.shape)}")
+        plan = plan_windows(T, self.window_frames, self.context, self.grid)
+        Tw = min(T, self.window_frames)
+        plan_dev = torch.tensor(plan, dtype=torch.int64).to(dev)
+        firsts_dev = plan_dev[:, 0].contiguous()
+        out = torch.empty(T * self.spf, dtype=torch.float32, device=dev)
+        for i0 in range(0, len(plan), self.windows_per_launch):
+            i1 = min(len(plan), i0 + self.windows_per_launch)
+            # each window's noise is a slice of the file's [1, inter, T] draw (voice_conversion copies it into its rows)
+            nz = torch.stack([noise[0, :, f0:f0 + Tw] for f0, _, _ in plan[i0:i1]])
+            self._launch(wave, N, plan_dev[i0:i1], firsts_dev[i0:i1], Tw, src_se, tgt_se, tau, nz, out, 0)
+        return out
+
+    def stream(self, src_se, tgt_se, tau=0.3, noise=None):
+        return ConversionStream(self, src_se, tgt_se, tau=tau, noise=noise)
+
+
+class ConversionStream:
+    """Streaming conversion on the window grid of ``WindowedConverter`` (one window per launch).
+
+    ``push(samples)`` appends 1-D float32 samples at the model rate (host or device) and returns the newly finished
+    output samples as a device tensor (possibly empty); ``close()`` applies the end-of-file reflect padding, runs the last
+    window (aligned to the end) and returns the rest.  Regular window k runs as soon as all its frames are interior
+    (no reflect padding at the end can reach them) and the file is certain to extend past it:
+    ``(f0 + Tw - 1) * hop + n_fft - pad`` samples, f0 = k * core.  The concatenated output equals
+    ``WindowedConverter(windows_per_launch=1).convert`` of the whole input with the same noise, bit for bit.
+
+    ``latency_samples``: input samples that arrive before the first output sample leaves, and the upper bound of any
+    sample's delay: ``(Tw - 1) * hop + n_fft - pad``.  Device memory stays bounded: the waveform and noise buffers are
+    trimmed as windows finish."""
+
+    def __init__(self, conv, src_se, tgt_se, tau=0.3, noise=None):
+        self.conv, self.src_se, self.tgt_se, self.tau = conv, src_se, tgt_se, tau
+        self.dev = conv._device()
+        c = conv
+        self._Tw, self._core, self._ctx = c.window_frames, c.core, c.context
+        self._latency = (self._Tw - 1) * c.hop + c.n_fft - c.pad
+        self._buf = torch.empty(0, dtype=torch.float32, device=self.dev)
+        self._len = 0               # valid samples in _buf
+        self._base = 0              # file index of _buf[0]; a multiple of hop
+        self._n = 0                 # samples received
+        self._k = 0                 # next regular window
+        self._emitted = 0           # frames of output handed out
+        self._noise = noise.to(self.dev, torch.float32) if noise is not None else None
+        self._nz = torch.empty(1, c.inter, 0, dtype=torch.float32, device=self.dev)   # drawn noise, frames [_nz0, ..)
+        self._nz0 = 0
+        self._closed = False
+
+    @property
+    def latency_samples(self):
+        return self._latency
+
+    def _need(self, k):
+        """Samples after which regular window k can run."""
+        c = self.conv
+        end = k * self._core + self._Tw
+        interior = (end - 1) * c.hop + c.n_fft - c.pad
+        longer = end * c.hop + c.n_fft - 2 * c.pad          # frames_of(n) >= end + 1: the file extends past the window
+        return max(interior, longer)
+
+    def _noise_for(self, f0, Tw):
+        """[1, inter, Tw] noise of frames [f0, f0 + Tw): a slice of the caller's tensor, or drawn once per frame."""
+        if self._noise is not None:
+            if self._noise.shape[2] < f0 + Tw:
+                raise ValueError(f"noise has {self._noise.shape[2]} frames, the stream needs {f0 + Tw}")
+            return self._noise[:, :, f0:f0 + Tw]
+        have = self._nz0 + self._nz.shape[2]
+        if f0 + Tw > have:
+            fresh = torch.randn(1, self.conv.inter, f0 + Tw - have, dtype=torch.float32, device=self.dev)
+            self._nz = torch.cat([self._nz, fresh], dim=2)
+        return self._nz[:, :, f0 - self._nz0:f0 - self._nz0 + Tw]
+
+    def _run(self, rec, Tw):
+        """One window of the stream: its core samples as a fresh device tensor.  The buffer starts ``_base`` samples
+        into the file (whole hops), so the window is framed at its first frame relative to the buffer; only a window
+        at the file's start (``_base`` 0) or end reads reflect padding, and the buffer holds that end."""
+        c = self.conv
+        f0, lo, hi = rec
+        rel = f0 - self._base // c.hop
+        assert self._base == 0 or rel * c.hop - c.pad >= 0, "stream buffer trimmed past a window's first sample"
+        plan_dev = torch.tensor([(rel, rel + lo - f0, rel + hi - f0)], dtype=torch.int64).to(self.dev)
+        out = torch.empty((hi - lo) * c.spf, dtype=torch.float32, device=self.dev)
+        nz = self._noise_for(f0, Tw)
+        c._launch(self._buf[:self._len], self._len, plan_dev, plan_dev[:, 0].contiguous(), Tw, self.src_se, self.tgt_se,
+                  self.tau, nz, out, rel + lo - f0)
+        self._emitted = hi
+        return out
+
+    def _regular(self, k):
+        f0 = k * self._core
+        return (f0, 0 if k == 0 else f0 + self._ctx, f0 + self._ctx + self._core)
+
+    def _trim(self, keep_from_frame):
+        """Drop buffered samples and noise no later window reads (whole hops, kept from before the reflect padding)."""
+        c = self.conv
+        base = max(0, keep_from_frame * c.hop - -(-c.pad // c.hop) * c.hop)
+        if base > self._base:
+            keep = self._buf[base - self._base:self._len].clone()
+            self._buf, self._len, self._base = keep, keep.numel(), base
+        if self._noise is None and keep_from_frame > self._nz0:
+            self._nz = self._nz[:, :, keep_from_frame - self._nz0:].clone()
+            self._nz0 = keep_from_frame
+
+    def _append(self, x):
+        n = x.numel()
+        if self._len + n > self._buf.numel():          # grow geometrically: pushes of one sample stay O(1) amortised
+            grown = torch.empty(max(2 * self._buf.numel(), self._len + n, 1 << 16), dtype=torch.float32, device=self.dev)
+            grown[:self._len].copy_(self._buf[:self._len])
+            self._buf = grown
+        self._buf[self._len:self._len + n].copy_(x)
+        self._len += n
+        self._n += n
+
+    @torch.no_grad()
+    def push(self, samples):
+        if self._closed:
+            raise RuntimeError("push() after close()")
+        self._append(torch.as_tensor(samples, dtype=torch.float32).reshape(-1).to(self.dev))
+        outs = []
+        while self._n >= self._need(self._k):
+            rec = self._regular(self._k)
+            outs.append(self._run(rec, self._Tw))
+            self._k += 1
+            self._trim(rec[0] + 1)      # every later window (regular or the last one) starts after this one
+        if not outs:
+            return torch.empty(0, dtype=torch.float32, device=self.dev)
+        return outs[0] if len(outs) == 1 else torch.cat(outs)
+
+    @torch.no_grad()
+    def close(self):
+        if self._closed:
+            raise RuntimeError("close() called twice")
+        self._closed = True
+        c = self.conv
+        if c.pad >= self._n:
+            raise ValueError("waveform shorter than the reflect padding")       # spectrogram_torch raises too
+        T = frames_of(self._n, c.n_fft, c.hop)
+        if T < 1:
+            raise ValueError("waveform shorter than one frame")
+        outs = []
+        if T > self._Tw:
+            # regular windows of the plan whose last frames reach into the end's reflect padding: only now defined
+            while self._k * self._core + self._Tw < T:
+                outs.append(self._run(self._regular(self._k), self._Tw))
+                self._k += 1
+        Tw = min(T, self._Tw)
+        outs.append(self._run((T - Tw, self._emitted, T), Tw))
+        self._buf, self._len = self._buf[:0], 0
+        return outs[0] if len(outs) == 1 else torch.cat(outs)

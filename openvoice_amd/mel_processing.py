@@ -72,6 +72,37 @@ class _NativeSpectrogram:
         # rows are padded to a multiple of 4 floats (16-byte aligned for the next conv); the caller sees [B, bins, T]
         return spec[:, :, :T]
 
+    def windows(self, wave, n_samples, first_frames, Tw):
+        """Spectrogram frames [f0, f0 + Tw) of the 1-D waveform ``wave`` (its first ``n_samples`` samples are the file)
+        for every f0 of the device int64 vector ``first_frames``: ``[W, bins, Tw]``, bit-identical to
+        ``self(wave[None])[0, :, f0:f0 + Tw]`` without framing the whole file (``ov_frame_hops_windows_f32``, reflect
+        padding at the file's true ends only)."""
+        from . import _lib
+        from .engine import launch_conv, padded_frames
+        W = first_frames.shape[0]
+        pad = (self.n_fft - self.hop) // 2
+        U = Tw + self.n_fft // self.hop - 1
+        ldu, lds = padded_frames(U), padded_frames(Tw)
+        hops = torch.empty(W, self.hop, ldu, dtype=torch.float32, device=wave.device)
+        _lib.call("ov_frame_hops_windows_f32", wave, int(n_samples), first_frames, W, self.hop, pad, U, ldu, hops)
+        spec = torch.zeros(W, self.bins, lds, dtype=torch.float32, device=wave.device)
+        launch_conv(self.layer, hops, 0, self.hop * ldu, spec, 0, self.bins * lds, W, Tw, epi=_lib.EPI_MAGNITUDE,
+                    scale=1e-6, rows=self.layer.rows, x_ld=ldu, out_ld=lds)
+        return spec[:, :, :Tw]
+
+
+def native_spectrogram(device, n_fft, hop):
+    """The cached ``_NativeSpectrogram`` of (device, n_fft, hop) -- the object ``spectrogram_torch`` runs on a device."""
+    device = torch.device(device)
+    if n_fft != 4 * hop:
+        from ._lib import OvError
+        raise OvError(f"native spectrogram: n_fft == 4 * hop only (got {n_fft} / {hop})")
+    key = (str(device), n_fft, hop)
+    eng = _native.get(key)
+    if eng is None:
+        eng = _native[key] = _NativeSpectrogram(device, n_fft, hop)
+    return eng
+
 
 def spectrogram_torch(y, n_fft, sampling_rate, hop_size, win_size, center=False):
     if os.environ.get("OV_CHECK_RANGE") == "1":

@@ -111,6 +111,23 @@ class SynthesizerTrn(nn.Module):
             return g(y, y_lengths, sid_src, sid_tgt, noise=noise)
         return eng.voice_conversion(y, y_lengths, sid_src, sid_tgt, tau=tau, noise=noise, skip_padding=skip_padding)
 
+    def voice_conversion_windowed(self, y, sid_src, sid_tgt, tau=1.0, noise=None, window_frames=None,
+                                  windows_per_launch=None, n_fft=1024, hop_length=256, graph=False):
+        """``voice_conversion`` of ONE recording of any length, from its waveform ``y`` ([N] or [1, N], float32 at the
+        model rate): what ``spectrogram_torch`` + ``voice_conversion`` compute in one pass (reference:
+        openvoice/api.py:145-147, models.py:492-499), as overlapping windows of ``window_frames`` frames
+        (``longform.WindowedConverter``) so that device memory is bounded by the window and there is no length limit.
+        ``noise`` ``[1, 192, >= T]`` (None: drawn on the device like the one-pass path).  Returns ``o_hat [1, 1, 256 T]``."""
+        from . import longform
+        if self.n_speakers != 0:
+            raise RuntimeError("voice_conversion_windowed() needs the converter model (n_speakers == 0)")
+        conv = longform.WindowedConverter(
+            self, n_fft=n_fft, hop=hop_length,
+            window_frames=longform.DEFAULT_WINDOW_FRAMES if window_frames is None else window_frames,
+            windows_per_launch=longform.DEFAULT_WINDOWS_PER_LAUNCH if windows_per_launch is None else windows_per_launch,
+            graph=graph)
+        return conv.convert(y, sid_src, sid_tgt, tau=tau, noise=noise).view(1, 1, -1)
+
     def infer(self, x, x_lengths, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1., sdp_ratio=0.2,
               max_len=None, noise_w=None, noise_z=None, skip_padding=False):
         """reference: openvoice/models.py:467-490; ``noise_w`` / ``noise_z`` are the explicit forms of the
