@@ -261,6 +261,16 @@ int ov_frame_hops_f32(const float* wave, float* hops, int B, int N, int hop, int
  * ABI 2.10. */
 int ov_frame_hops_windows_f32(const float* wave, int64_t n_samples, const int64_t* first_frame, int W, int hop, int pad,
                               int U, int ld, float* hops, ov_stream_t stream);
+/* ov_frame_hops_windows_f32 with one source per window (many streams / recordings in one launch,
+ * openvoice_amd/longform.py StreamPool / convert_many): records is a DEVICE int64 [W][3] of (base, n_samples,
+ * first_frame); window w frames pool[base, base + n_samples) as its own waveform,
+ *   hops[w][c][u] = ypad_w[hop * (first_frame + u) + c],  u < U,
+ * ypad_w = that span reflect-padded by `pad` samples at both of its ends (zero beyond).  Same host checks and error
+ * codes as ov_frame_hops_windows_f32 (pool_len plays n_samples' part, pad < n_samples is checked per record).  The
+ * kernel checks every record itself: base < 0, n_samples <= pad or base + n_samples > pool_len writes zeros for that
+ * window and reads nothing.  64-bit sample indices.  ABI 2.11. */
+int ov_frame_hops_multi_f32(const float* pool, int64_t pool_len, const int64_t* records, int W, int hop, int pad, int U,
+                            int ld, float* hops, ov_stream_t stream);
 /* The cores of W windows into the long output (the reference writes the one-pass o_hat, openvoice/api.py:146-156):
  * windows is a DEVICE int64 [W][3] of (first_frame, core_lo, core_hi) in frames, o_hat [W][Tw * spf] the windows'
  * generator outputs (spf samples per frame);
@@ -598,7 +608,7 @@ int ov_conv1d_wino_pack_f32(const float* w, int Cout, int Cin, int K, float* dst
  * was `reserved`; the struct grew by one pointer at its end).  2.06: ov_polyphase_fir_f32.  2.07: ov_conv1d_wino_f32 (+ _supported, _chunk,
  * _pack_size, _pack_f32).  2.08: ov_conv1d_wino_f32 instances for Cout % 32 == 0 at K = 11 (one 32-row fragment per
  * workgroup; ov_conv1d_wino_chunk(11, 32) = 2 where 2.07 returned 0).  2.09: ov_conv1d_wino_params.out_slope (the field that
- * was `reserved0`: same size and offset, 0 = none).  2.10: ov_frame_hops_windows_f32, ov_stitch_window_cores_f32.  The Python binding
+ * was `reserved0`: same size and offset, 0 = none).  2.10: ov_frame_hops_windows_f32, ov_stitch_window_cores_f32.  2.11: ov_frame_hops_multi_f32.  The Python binding
  * refuses a library older than the entry points it calls (openvoice_amd/_lib.py MIN_VERSION). */
 int ov_version(void);
 /* The version THIS header describes.  Parameter structs grow at their END in minor versions (2.04, 2.05, 2.07 did): a
@@ -608,7 +618,7 @@ int ov_version(void);
  * tests/test_abi_cpu.py).  A struct is never reordered and a field never changes meaning within a major version, with
  * one exception stated here: 2.05 renamed ov_wn_layer_params.reserved to row_split AND appended `acts`, so a caller
  * built against 2.04 or older is NOT binary compatible with 2.05+ for that struct. */
-#define OV_ABI_VERSION 210
+#define OV_ABI_VERSION 211
 /* 0 for a production build; non-zero = a measurement build with parts of the kernels compiled out (results are
  * meaningless; openvoice_amd/_lib.py refuses to load it unless OPENVOICE_AMD_ALLOW_EXPERIMENT=1). */
 int ov_build_experiment(void);

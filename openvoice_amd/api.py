@@ -369,6 +369,40 @@ class ToneColorConverter(OpenVoiceBaseClass):
         reproducible.  The output equals ``convert_long(..., windows_per_launch=1)`` of the whole input, bit for bit."""
         return self._windowed(window_frames, 1).stream(src_se, tgt_se, tau=tau, noise=noise)
 
+    # ---- many streams and recordings in shared launches -------------------------------------------------------------
+    def stream_pool(self, tau=0.3, window_frames=longform.DEFAULT_STREAM_WINDOW_FRAMES,
+                    max_windows_per_launch=longform.DEFAULT_POOL_WINDOWS_PER_LAUNCH):
+        """A ``longform.StreamPool``: many live streams (``open(src_se, tgt_se, noise=None)`` -> handle, ``push(h,
+        samples)``, ``close(h)``), whose ready windows one ``step()`` converts together, up to
+        ``max_windows_per_launch`` per launch -> ``{handle: newly finished samples}``.  Each stream's output equals a
+        ``stream(...)`` fed the same samples with the same noise.  One ``tau`` for the whole pool."""
+        return self._windowed(window_frames, 1).stream_pool(tau=tau, max_windows_per_launch=max_windows_per_launch)
+
+    def convert_many(self, items, src_se, tgt_se, tau=0.3, window_frames=longform.DEFAULT_WINDOW_FRAMES,
+                     windows_per_launch=longform.DEFAULT_MANY_WINDOWS_PER_LAUNCH, noise=None, output_paths=None,
+                     message="default"):
+        """``convert_long`` of many recordings with their windows packed ACROSS recordings into launches of up to
+        ``windows_per_launch`` (``longform.WindowedConverter.convert_many``).  ``items``: file paths (any rate, decoded
+        and resampled like ``convert_long``) or 1-D waveforms at the model rate.  ``src_se`` / ``tgt_se``: one
+        ``[1, 256, 1]`` for every item, or a list with one per item.  ``noise``: None or a list of ``[1, 192, >= T_i]``.
+        Returns a list of numpy arrays (watermark hook applied per item), or writes ``output_paths[i]`` instead.  Each
+        item equals ``convert_long`` of it with the same ``window_frames`` and noise."""
+        hps = self.hps
+        items = list(items)
+        n = len(items)
+        per_item = lambda se: list(se) if isinstance(se, (list, tuple)) else [se] * n
+        srcs, tgts = per_item(src_se), per_item(tgt_se)
+        if output_paths is not None and len(output_paths) != n:
+            raise ValueError("convert_many: one output path per item")
+        waves = [audio_io.load_to_device(x, hps.data.sampling_rate, self.device) if isinstance(x, (str, os.PathLike))
+                 else torch.as_tensor(x, dtype=torch.float32).reshape(-1).to(self.device) for x in items]
+        outs = self._windowed(window_frames, windows_per_launch).convert_many(waves, srcs, tgts, tau=tau, noises=noise)
+        audios = [self.add_watermark(o.cpu().numpy(), message) for o in outs]
+        if output_paths is None:
+            return audios
+        for path, audio in zip(output_paths, audios):
+            audio_io.write(path, audio, hps.data.sampling_rate)
+
     # ---- optional watermark hook (third-party model; behaviour of the reference's openvoice/api.py:162-201) ----------
     # The message travels as 32-bit groups, group n in the 16 000-sample window that starts at sample 32 000 n (every other
     # window of the waveform stays untouched); ``watermark_model`` is any object with ``encode(signal [1, 16000], bits

@@ -1,6 +1,7 @@
 // Windowed long-form conversion (openvoice_amd/longform.py): the framing of W fixed-length windows straight out of one
-// long waveform, and the copy of each window's core samples into the long output.  Both are memory-bound gathers /
-// copies with 64-bit sample indices; neither uses LDS.
+// long waveform (or out of one span per window, for many streams / recordings in one launch), and the copy of each
+// window's core samples into the long output.  Both are memory-bound gathers / copies with 64-bit sample indices; neither
+// uses LDS.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -34,6 +35,38 @@ __global__ __launch_bounds__(256) void frame_hops_windows_kernel(const float* __
       const int64_t i = (f0 + u0 + j) * hop + c - pad;     // index into the un-padded waveform
       float x = 0.f;
       if (u0 + j < U && i >= -(int64_t)pad && i < n + pad) {
+        const int64_t k = i < 0 ? -i : (i >= n ? 2 * (n - 1) - i : i);   // in [0, n) because pad < n
+        x = wave[k];
+      }
+      v[j] = x;
+    }
+    *reinterpret_cast<f32x4*>(row + u0) = v;
+  }
+}
+
+// ov_frame_hops_multi_f32: frame_hops_windows_kernel with one source per window.  Window w frames the span
+// pool[base, base + n) of its record (base, n, f0) as its own waveform, reflect-padded at the span's two ends.  The
+// records live on the device, so a record the host could not check is checked here: base < 0, n <= pad (reflection
+// undefined) or base + n > pool_len make the window all zeros, and nothing outside `pool` is read.
+__global__ __launch_bounds__(256) void frame_hops_multi_kernel(const float* __restrict__ pool, int64_t pool_len,
+                                                               const int64_t* __restrict__ records, int hop, int pad,
+                                                               int U, int ld, float* __restrict__ hops) {
+  const int w = blockIdx.z;
+  const int c = blockIdx.y * 64 + (threadIdx.x & 63);
+  if (c >= hop) return;
+  const int64_t base = records[3 * w], n = records[3 * w + 1], f0 = records[3 * w + 2];
+  const bool ok = base >= 0 && n > pad && base <= pool_len - n;
+  const float* wave = pool + (ok ? base : 0);
+  float* row = hops + ((int64_t)w * hop + c) * ld;
+  for (int g = threadIdx.x >> 6; g < 16; g += 4) {
+    const int u0 = blockIdx.x * 64 + 4 * g;
+    if (u0 >= U) break;
+    f32x4 v;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int64_t i = (f0 + u0 + j) * hop + c - pad;     // index into the un-padded span
+      float x = 0.f;
+      if (ok && u0 + j < U && i >= -(int64_t)pad && i < n + pad) {
         const int64_t k = i < 0 ? -i : (i >= n ? 2 * (n - 1) - i : i);   // in [0, n) because pad < n
         x = wave[k];
       }
@@ -78,6 +111,18 @@ int ov_frame_hops_windows_f32(const float* wave, int64_t n_samples, const int64_
   dim3 grid((U + 63) / 64, (hop + 63) / 64, W);
   hipLaunchKernelGGL(frame_hops_windows_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), wave, n_samples,
                      first_frame, hop, pad, U, ld, hops);
+  return hipGetLastError() == hipSuccess ? OV_OK : OV_E_LAUNCH;
+}
+
+int ov_frame_hops_multi_f32(const float* pool, int64_t pool_len, const int64_t* records, int W, int hop, int pad, int U,
+                            int ld, float* hops, ov_stream_t stream) {
+  if (!pool || !records || !hops || pool_len <= 0 || W <= 0 || W > 65535 || hop <= 0 || hop > 1024 || pad < 0 ||
+      U <= 0 || ld < U)
+    return OV_E_BADARG;
+  if (ld % 4 != 0 || (reinterpret_cast<uintptr_t>(hops) & 15)) return OV_E_ALIGN;
+  dim3 grid((U + 63) / 64, (hop + 63) / 64, W);
+  hipLaunchKernelGGL(frame_hops_multi_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), pool, pool_len,
+                     records, hop, pad, U, ld, hops);
   return hipGetLastError() == hipSuccess ? OV_OK : OV_E_LAUNCH;
 }
 

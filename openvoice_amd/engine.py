@@ -521,6 +521,10 @@ class ConverterEngine:
                 proj_w=sd["ref_enc.proj.weight"].contiguous().to(dev),
                 proj_b=sd["ref_enc.proj.bias"].contiguous().to(dev))
         self._ws = {}
+        # (B, T) workspaces kept resident at once, least recently used evicted first.  1 (the default): a new shape
+        # frees the previous one.  StreamPool raises it to its ladder of launch sizes so that a varying ready count
+        # does not rebuild gigabytes of decoder scratch per step (workspace_bytes() prices a shape).
+        self.resident_workspaces = 1
         self.profile = None   # set to [] to collect per-launch HIP-event timings
         # independent ResBlock chains of a generator stage on this many HIP streams when the batch is at most
         # chain_streams_max_batch utterances (decode()); 1 = always the serial one-stream order
@@ -612,9 +616,14 @@ class ConverterEngine:
 
     def _workspace(self, B, T):
         key = (B, T)
-        ws = self._ws.get(key)
-        if ws is None:
-            self._ws.clear()   # one resident shape at a time; the decoder scratch is GBs at B=32
+        ws = self._ws.pop(key, None)
+        if ws is not None:
+            self._ws[key] = ws     # re-inserted last: the dict is the LRU order
+        else:
+            # resident_workspaces shapes at a time (default one: the decoder scratch is GBs at B=32); the least
+            # recently used one goes first
+            while self._ws and len(self._ws) >= max(1, int(self.resident_workspaces)):
+                self._ws.pop(next(iter(self._ws)))
             dev, H, C = self.device, self.hidden, self.inter
             Tp = padded_frames(T)
             # zero-filled once: the pad columns [T, Tp) are never written by a kernel and never read as data
@@ -633,6 +642,19 @@ class ConverterEngine:
             ws["dec"] = [f(B * biggest) for _ in range(5)]
             self._ws[key] = ws
         return ws
+
+    def workspace_bytes(self, B, T):
+        """Device bytes of the ``_workspace(B, T)`` allocation (the frame-rate tensors and the decoder scratch; the
+        opt-in paths' lazily added buffers not included)."""
+        H, C, Tp = self.hidden, self.inter, padded_frames(T)
+        ch = self.cfg["upsample_initial_channel"]
+        frame_rate = Tp + 4 * H * Tp + C * Tp + 3 * C * Tp + ch * Tp          # mask, h / h2 / acts / skip, noise, lat, pre
+        L, biggest = T, 0
+        for u in self.cfg["upsample_rates"]:
+            ch //= 2
+            L *= u
+            biggest = max(biggest, ch * L)
+        return 4 * B * (frame_rate + 5 * biggest)
 
     def _zeros_like_cached(self, t):
         """An all-zero tensor of ``t``'s shape (the ``zero_g`` conditioning, models.py:495,498) without a fill launch

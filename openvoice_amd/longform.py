@@ -14,6 +14,10 @@ A window is a batch item of the unchanged ``voice_conversion`` (reference: openv
 ``spec_lengths = Tw``; its spectrogram is framed straight out of the long waveform (``ov_frame_hops_windows_f32`` + the
 K = 4 framing conv of ``mel_processing``), so it equals ``spectrogram_torch(whole)[:, :, f0:f0 + Tw]`` bit for bit; its
 core samples are copied into the long output by ``ov_stitch_window_cores_f32``.
+
+Many sources share launches: ``StreamPool`` steps many live streams and ``WindowedConverter.convert_many`` converts many
+recordings, both framing every window of a launch from its own source span (``ov_frame_hops_multi_f32``) and stitching
+the cores into one packed output.
 """
 import math
 
@@ -31,6 +35,10 @@ DEFAULT_WINDOW_FRAMES = 8192
 DEFAULT_WINDOWS_PER_LAUNCH = 2
 # streams: the window sets the latency (256 Tw + 384 samples): 11.9 s at 1024 frames, ~980x real time
 DEFAULT_STREAM_WINDOW_FRAMES = 1024
+# StreamPool: windows per launch at most (the ladder of launch sizes is the powers of two below it, and it)
+DEFAULT_POOL_WINDOWS_PER_LAUNCH = 32
+# convert_many: windows per launch
+DEFAULT_MANY_WINDOWS_PER_LAUNCH = 8
 
 
 def winograd_grid_frames(cfg):
@@ -118,6 +126,18 @@ def one_pass_limit_frames(cfg):
     return min(bound // per_frame + 1 for per_frame, bound in checks)
 
 
+def launch_ladder(max_windows):
+    """Launch sizes of a ``StreamPool``: the powers of two below ``max_windows``, and ``max_windows`` itself."""
+    m = int(max_windows)
+    if m < 1:
+        raise ValueError(f"max_windows_per_launch = {max_windows}")
+    ladder, b = [], 1
+    while b < m:
+        ladder.append(b)
+        b *= 2
+    return ladder + [m]
+
+
 def frames_of(n_samples, n_fft, hop):
     """Frames of ``spectrogram_torch`` (center=False, reflect pad (n_fft - hop) / 2) for ``n_samples``."""
     pad = (n_fft - hop) // 2
@@ -164,12 +184,53 @@ class WindowedConverter:
                                             graph=self.graph)[0]
         _lib.call("ov_stitch_window_cores_f32", o_hat, plan_dev, W, Tw, self.spf, out, out.numel(), out_frame0)
 
-    @torch.no_grad()
-    def convert(self, wave, src_se, tgt_se, tau=0.3, noise=None):
-        """``wave``: 1-D float32 waveform at the model rate (host or device).  ``noise``: ``[1, inter, >= T]`` or None
-        (then ``torch.randn(1, inter, T)`` on the device: the stream of a seeded one-pass ``convert``).  Returns the
-        converted waveform ``[spf * T]`` on the device (spf = the generator's samples per frame = hop), ``T`` = frames of ``spectrogram_torch``."""
-        dev = self._device()
+    def _launch_multi(self, pool, records_dev, Tw, src_se, tgt_se, tau, nz, out, stitch_dev, n_out):
+        """One launch of W = len(records_dev) windows, each from its own span of ``pool`` (``records_dev`` [W, 3] int64
+        (base, n_samples, first_frame)): framing -> spectrogram -> voice_conversion with per-window embedding rows ->
+        the cores of the first ``n_out`` windows into the packed ``out`` (``stitch_dev`` [n_out, 3] virtual records,
+        out_frame0 = 0); rows past ``n_out`` pad the launch to a ladder size and their output is dropped."""
+        W = records_dev.shape[0]
+        spec = self._spectrogram().windows_multi(pool, records_dev, Tw)
+        lengths = torch.full((W,), Tw, dtype=torch.int64, device=pool.device)
+        o_hat = self.model.voice_conversion(spec, lengths, sid_src=src_se, sid_tgt=tgt_se, tau=tau, noise=nz,
+                                            graph=self.graph)[0]
+        _lib.call("ov_stitch_window_cores_f32", o_hat, stitch_dev, n_out, Tw, self.spf, out, out.numel(), 0)
+
+    def _run_jobs(self, sources, jobs, tau, out, max_windows, ladder=None):
+        """Windows of many sources in shared launches.  ``sources``: 1-D device waveforms (spans); ``jobs``: window
+        jobs ``(source, f0, lo, hi, Tw, noise [1, inter, Tw], src_se [1, gin, 1], tgt_se, dst)`` with frames relative to
+        the source span and ``dst`` the packed output frame of the core's first frame.  Jobs of equal ``Tw`` share
+        launches of up to ``max_windows`` in the given order; a partial launch is padded up to the next ``ladder`` size
+        (None: launched as it is) with copies of its last window.  Returns the number of launches."""
+        if not jobs:
+            return 0
+        bases, acc = [], 0
+        for x in sources:
+            bases.append(acc)
+            acc += x.numel()
+        pool = sources[0] if len(sources) == 1 else torch.cat(sources)
+        groups = {}
+        for j in jobs:
+            groups.setdefault(j[4], []).append(j)
+        launches = 0
+        for Tw, js in groups.items():
+            for i0 in range(0, len(js), max_windows):
+                chunk = js[i0:i0 + max_windows]
+                r = len(chunk)
+                W = r if ladder is None else min(b for b in ladder if b >= r)
+                rows = chunk + [chunk[-1]] * (W - r)
+                recs = [(bases[j[0]], sources[j[0]].numel(), j[1]) for j in rows]
+                recs += [(j[8] - (j[2] - j[1]), j[8], j[8] + j[3] - j[2]) for j in chunk]
+                recs_dev = torch.tensor(recs, dtype=torch.int64).to(pool.device)      # one host -> device copy
+                nz = torch.cat([j[5] for j in rows])
+                g_src = torch.cat([j[6].reshape(1, -1, 1) for j in rows])
+                g_tgt = torch.cat([j[7].reshape(1, -1, 1) for j in rows])
+                self._launch_multi(pool, recs_dev[:W], Tw, g_src, g_tgt, tau, nz, out, recs_dev[W:], r)
+                launches += 1
+        return launches
+
+    def _prepare(self, wave, noise, dev):
+        """(device waveform, T, noise [1, inter, >= T]) of one recording, checked like ``convert``."""
         wave = torch.as_tensor(wave, dtype=torch.float32).reshape(-1).to(dev).contiguous()
         N = wave.numel()
         if self.pad >= N:
@@ -183,6 +244,43 @@ class WindowedConverter:
             noise = noise.to(dev, torch.float32)
             if noise.dim() != 3 or noise.shape[0] != 1 or noise.shape[1] != self.inter or noise.shape[2] < T:
                 raise ValueError(f"noise must be [1, {self.inter}, >= {T}], got {tuple(noise.shape)}")
+        return wave, T, noise
+
+    @torch.no_grad()
+    def convert_many(self, waves, src_ses, tgt_ses, tau=0.3, noises=None):
+        """``convert`` of many recordings with their windows packed across recordings into launches of up to
+        ``windows_per_launch`` (``ov_frame_hops_multi_f32``: each window framed from its own recording).  ``src_ses`` /
+        ``tgt_ses``: one embedding per recording; ``noises``: None or one ``[1, inter, >= T_i]`` (or None) per
+        recording -- drawn in order like ``convert`` otherwise.  Every recording runs the windows of its own
+        ``plan_windows``; recordings of ``T <= window_frames`` frames are one ``T``-frame window each and share launches
+        with the recordings of equal ``T``.  Returns the converted waveforms (device tensors, views of one packed
+        output), each equal to ``convert`` of that recording with the same noise (bit for bit with direct kernels)."""
+        dev = self._device()
+        n = len(waves)
+        if len(src_ses) != n or len(tgt_ses) != n or (noises is not None and len(noises) != n):
+            raise ValueError("convert_many: one src / tgt embedding (and noise) per recording")
+        items = [self._prepare(w, None if noises is None else noises[i], dev) for i, w in enumerate(waves)]
+        jobs, offs, acc = [], [], 0
+        for i, (wave, T, noise) in enumerate(items):
+            offs.append(acc)
+            Tw = min(T, self.window_frames)
+            for f0, lo, hi in plan_windows(T, self.window_frames, self.context, self.grid):
+                jobs.append((i, f0, lo, hi, Tw, noise[:, :, f0:f0 + Tw], src_ses[i], tgt_ses[i], acc + lo))
+            acc += T
+        out = torch.empty(acc * self.spf, dtype=torch.float32, device=dev)
+        # windows of full length first (one shape), then the short recordings grouped by length
+        jobs.sort(key=lambda j: j[4] != self.window_frames)
+        self._run_jobs([w for w, _, _ in items], jobs, tau, out, self.windows_per_launch)
+        return [out[o * self.spf:(o + T) * self.spf] for o, (_, T, _) in zip(offs, items)]
+
+    @torch.no_grad()
+    def convert(self, wave, src_se, tgt_se, tau=0.3, noise=None):
+        """``wave``: 1-D float32 waveform at the model rate (host or device).  ``noise``: ``[1, inter, >= T]`` or None
+        (then ``torch.randn(1, inter, T)`` on the device: the stream of a seeded one-pass ``convert``).  Returns the
+        converted waveform ``[spf * T]`` on the device (spf = the generator's samples per frame = hop), ``T`` = frames of ``spectrogram_torch``."""
+        dev = self._device()
+        wave, T, noise = self._prepare(wave, noise, dev)
+        N = wave.numel()
         plan = plan_windows(T, self.window_frames, self.context, self.grid)
         Tw = min(T, self.window_frames)
         plan_dev = torch.tensor(plan, dtype=torch.int64).to(dev)
@@ -198,23 +296,17 @@ class WindowedConverter:
     def stream(self, src_se, tgt_se, tau=0.3, noise=None):
         return ConversionStream(self, src_se, tgt_se, tau=tau, noise=noise)
 
+    def stream_pool(self, tau=0.3, max_windows_per_launch=DEFAULT_POOL_WINDOWS_PER_LAUNCH):
+        return StreamPool(self, tau=tau, max_windows_per_launch=max_windows_per_launch)
 
-class ConversionStream:
-    """Streaming conversion on the window grid of ``WindowedConverter`` (one window per launch).
 
-    ``push(samples)`` appends 1-D float32 samples at the model rate (host or device) and returns the newly finished
-    output samples as a device tensor (possibly empty); ``close()`` applies the end-of-file reflect padding, runs the last
-    window (aligned to the end) and returns the rest.  Regular window k runs as soon as all its frames are interior
-    (no reflect padding at the end can reach them) and the file is certain to extend past it:
-    ``(f0 + Tw - 1) * hop + n_fft - pad`` samples, f0 = k * core.  The concatenated output equals
-    ``WindowedConverter(windows_per_launch=1).convert`` of the whole input with the same noise, bit for bit.
+class _StreamState:
+    """Bookkeeping of one stream on the window grid, shared by ``ConversionStream`` (one window per launch) and
+    ``StreamPool`` (many streams per launch): the buffered tail of the input, the next regular window, the readiness
+    rule, the end-of-input plan and the noise."""
 
-    ``latency_samples``: input samples that arrive before the first output sample leaves, and the upper bound of any
-    sample's delay: ``(Tw - 1) * hop + n_fft - pad``.  Device memory stays bounded: the waveform and noise buffers are
-    trimmed as windows finish."""
-
-    def __init__(self, conv, src_se, tgt_se, tau=0.3, noise=None):
-        self.conv, self.src_se, self.tgt_se, self.tau = conv, src_se, tgt_se, tau
+    def __init__(self, conv, src_se, tgt_se, noise=None):
+        self.conv, self.src_se, self.tgt_se = conv, src_se, tgt_se
         self.dev = conv._device()
         c = conv
         self._Tw, self._core, self._ctx = c.window_frames, c.core, c.context
@@ -229,6 +321,7 @@ class ConversionStream:
         self._nz = torch.empty(1, c.inter, 0, dtype=torch.float32, device=self.dev)   # drawn noise, frames [_nz0, ..)
         self._nz0 = 0
         self._closed = False
+        self._tail = None           # StreamPool: the end-of-input plan, taken by close()
 
     @property
     def latency_samples(self):
@@ -253,22 +346,6 @@ class ConversionStream:
             fresh = torch.randn(1, self.conv.inter, f0 + Tw - have, dtype=torch.float32, device=self.dev)
             self._nz = torch.cat([self._nz, fresh], dim=2)
         return self._nz[:, :, f0 - self._nz0:f0 - self._nz0 + Tw]
-
-    def _run(self, rec, Tw):
-        """One window of the stream: its core samples as a fresh device tensor.  The buffer starts ``_base`` samples
-        into the file (whole hops), so the window is framed at its first frame relative to the buffer; only a window
-        at the file's start (``_base`` 0) or end reads reflect padding, and the buffer holds that end."""
-        c = self.conv
-        f0, lo, hi = rec
-        rel = f0 - self._base // c.hop
-        assert self._base == 0 or rel * c.hop - c.pad >= 0, "stream buffer trimmed past a window's first sample"
-        plan_dev = torch.tensor([(rel, rel + lo - f0, rel + hi - f0)], dtype=torch.int64).to(self.dev)
-        out = torch.empty((hi - lo) * c.spf, dtype=torch.float32, device=self.dev)
-        nz = self._noise_for(f0, Tw)
-        c._launch(self._buf[:self._len], self._len, plan_dev, plan_dev[:, 0].contiguous(), Tw, self.src_se, self.tgt_se,
-                  self.tau, nz, out, rel + lo - f0)
-        self._emitted = hi
-        return out
 
     def _regular(self, k):
         f0 = k * self._core
@@ -295,6 +372,63 @@ class ConversionStream:
         self._len += n
         self._n += n
 
+    def _tail_plan(self):
+        """At the end of the input: ``[(record, Tw)]`` of the windows still to run -- the regular windows of the plan not
+        yet run (those whose last frames reach into the end's reflect padding are only now defined) and the last
+        window, aligned to the end (``T`` frames when ``T <= Tw``).  Raises ValueError for input shorter than the reflect
+        padding or one frame, like ``spectrogram_torch``."""
+        c = self.conv
+        if c.pad >= self._n:
+            raise ValueError("waveform shorter than the reflect padding")       # spectrogram_torch raises too
+        T = frames_of(self._n, c.n_fft, c.hop)
+        if T < 1:
+            raise ValueError("waveform shorter than one frame")
+        plan, k, emitted = [], self._k, self._emitted
+        if T > self._Tw:
+            while k * self._core + self._Tw < T:
+                rec = self._regular(k)
+                plan.append((rec, self._Tw))
+                emitted = rec[2]
+                k += 1
+        Tw = min(T, self._Tw)
+        plan.append(((T - Tw, emitted, T), Tw))
+        return plan
+
+
+class ConversionStream(_StreamState):
+    """Streaming conversion on the window grid of ``WindowedConverter`` (one window per launch).
+
+    ``push(samples)`` appends 1-D float32 samples at the model rate (host or device) and returns the newly finished
+    output samples as a device tensor (possibly empty); ``close()`` applies the end-of-file reflect padding, runs the last
+    window (aligned to the end) and returns the rest.  Regular window k runs as soon as all its frames are interior
+    (no reflect padding at the end can reach them) and the file is certain to extend past it:
+    ``(f0 + Tw - 1) * hop + n_fft - pad`` samples, f0 = k * core.  The concatenated output equals
+    ``WindowedConverter(windows_per_launch=1).convert`` of the whole input with the same noise, bit for bit.
+
+    ``latency_samples``: input samples that arrive before the first output sample leaves, and the upper bound of any
+    sample's delay: ``(Tw - 1) * hop + n_fft - pad``.  Device memory stays bounded: the waveform and noise buffers are
+    trimmed as windows finish."""
+
+    def __init__(self, conv, src_se, tgt_se, tau=0.3, noise=None):
+        super().__init__(conv, src_se, tgt_se, noise)
+        self.tau = tau
+
+    def _run(self, rec, Tw):
+        """One window of the stream: its core samples as a fresh device tensor.  The buffer starts ``_base`` samples
+        into the file (whole hops), so the window is framed at its first frame relative to the buffer; only a window
+        at the file's start (``_base`` 0) or end reads reflect padding, and the buffer holds that end."""
+        c = self.conv
+        f0, lo, hi = rec
+        rel = f0 - self._base // c.hop
+        assert self._base == 0 or rel * c.hop - c.pad >= 0, "stream buffer trimmed past a window's first sample"
+        plan_dev = torch.tensor([(rel, rel + lo - f0, rel + hi - f0)], dtype=torch.int64).to(self.dev)
+        out = torch.empty((hi - lo) * c.spf, dtype=torch.float32, device=self.dev)
+        nz = self._noise_for(f0, Tw)
+        c._launch(self._buf[:self._len], self._len, plan_dev, plan_dev[:, 0].contiguous(), Tw, self.src_se, self.tgt_se,
+                  self.tau, nz, out, rel + lo - f0)
+        self._emitted = hi
+        return out
+
     @torch.no_grad()
     def push(self, samples):
         if self._closed:
@@ -315,19 +449,126 @@ class ConversionStream:
         if self._closed:
             raise RuntimeError("close() called twice")
         self._closed = True
-        c = self.conv
-        if c.pad >= self._n:
-            raise ValueError("waveform shorter than the reflect padding")       # spectrogram_torch raises too
-        T = frames_of(self._n, c.n_fft, c.hop)
-        if T < 1:
-            raise ValueError("waveform shorter than one frame")
-        outs = []
-        if T > self._Tw:
-            # regular windows of the plan whose last frames reach into the end's reflect padding: only now defined
-            while self._k * self._core + self._Tw < T:
-                outs.append(self._run(self._regular(self._k), self._Tw))
-                self._k += 1
-        Tw = min(T, self._Tw)
-        outs.append(self._run((T - Tw, self._emitted, T), Tw))
+        outs = [self._run(rec, Tw) for rec, Tw in self._tail_plan()]
         self._buf, self._len = self._buf[:0], 0
         return outs[0] if len(outs) == 1 else torch.cat(outs)
+
+
+class StreamPool:
+    """Many live streams on one window grid, their ready windows converted together: one ``step()`` runs every ready
+    window of every open stream in ``ceil(R / max_windows_per_launch)`` launches (fewer per stream than one launch per
+    window, which is what the solo ``ConversionStream`` costs).
+
+    ``open(src_se, tgt_se, noise=None)`` -> a handle (per-stream embeddings; ``noise`` ``[1, inter, >= T]`` or None:
+    drawn lazily per stream); ``push(h, samples)`` only buffers (a host -> device copy); ``step()`` -> ``{handle: newly
+    finished samples}`` (device tensors, views of one packed output) for the streams with output; ``close(h)`` marks the
+    end of h's input -- its last window(s) run in the next ``step()``, which retires h.  A window becomes ready exactly
+    when it would in ``ConversionStream`` (the same ``_need`` / ``_tail_plan``), so each stream's concatenated output
+    equals a solo stream's fed the same samples with the same noise: bit for bit with direct kernels, and within the
+    cross-family bar with the defaults (the Winograd choice depends on the launch size).
+
+    Launch sizes come from a fixed ladder (``launch_ladder``: 1, 2, 4, ..., max_windows_per_launch); a partial launch
+    is padded with copies of one of its windows whose output is dropped, and the engine keeps one workspace per ladder
+    size resident (``ConverterEngine.resident_workspaces`` is raised to len(ladder) + 1, the one spare for the T-frame
+    final windows of streams shorter than a window).  ``tau`` is one launch scalar for the whole pool."""
+
+    def __init__(self, conv, tau=0.3, max_windows_per_launch=DEFAULT_POOL_WINDOWS_PER_LAUNCH):
+        self.conv, self.tau = conv, tau
+        self.ladder = launch_ladder(max_windows_per_launch)
+        self.max_windows_per_launch = self.ladder[-1]
+        self._streams = {}          # handle -> _StreamState, in handle order
+        self._next = 0
+        self._retired = set()
+        engine = getattr(conv.model, "engine", None)
+        if callable(engine):
+            eng = engine()
+            eng.resident_workspaces = max(eng.resident_workspaces, len(self.ladder) + 1)
+
+    @property
+    def active(self):
+        """Handles of the streams not yet retired (open, or closed with their tail still to run)."""
+        return list(self._streams)
+
+    @property
+    def latency_samples(self):
+        """As ``ConversionStream.latency_samples``: ``(Tw - 1) * hop + n_fft - pad`` (plus the wait for the next
+        ``step()``)."""
+        c = self.conv
+        return (c.window_frames - 1) * c.hop + c.n_fft - c.pad
+
+    def open(self, src_se, tgt_se, noise=None):
+        h = self._next
+        self._next += 1
+        self._streams[h] = _StreamState(self.conv, src_se, tgt_se, noise)
+        return h
+
+    def _stream(self, h):
+        st = self._streams.get(h)
+        if st is None:
+            raise RuntimeError(f"stream {h!r} is closed" if h in self._retired else f"no stream {h!r} in this pool")
+        return st
+
+    @torch.no_grad()
+    def push(self, h, samples):
+        st = self._stream(h)
+        if st._closed:
+            raise RuntimeError(f"push() after close() on stream {h!r}")
+        st._append(torch.as_tensor(samples, dtype=torch.float32).reshape(-1).to(st.dev))
+
+    def close(self, h):
+        """End of h's input.  Input shorter than the reflect padding or one frame raises ValueError here and retires h
+        (the other streams are untouched)."""
+        st = self._stream(h)
+        if st._closed:
+            raise RuntimeError(f"close() called twice on stream {h!r}")
+        st._closed = True
+        try:
+            st._tail = st._tail_plan()
+        except ValueError:
+            self._retire(h)
+            raise
+
+    def _retire(self, h):
+        st = self._streams.pop(h)
+        st._buf, st._len = st._buf[:0], 0
+        self._retired.add(h)
+
+    @torch.no_grad()
+    def step(self):
+        c = self.conv
+        sources, jobs, spans, acc = [], [], {}, 0
+        for h, st in self._streams.items():
+            if st._closed:
+                recs = st._tail
+            else:
+                recs = []
+                while st._n >= st._need(st._k):
+                    recs.append((st._regular(st._k), st._Tw))
+                    st._k += 1
+            if not recs:
+                continue
+            first = acc
+            sh = st._base // c.hop
+            for (f0, lo, hi), Tw in recs:
+                assert st._base == 0 or (f0 - sh) * c.hop - c.pad >= 0, "stream buffer trimmed past a window's first sample"
+                jobs.append((len(sources), f0 - sh, lo - sh, hi - sh, Tw, st._noise_for(f0, Tw), st.src_se, st.tgt_se,
+                             acc))
+                acc += hi - lo
+            sources.append(st._buf[:st._len])
+            spans[h] = (first, acc, recs[-1][0])
+        if not jobs:
+            return {}
+        out = torch.empty(acc * c.spf, dtype=torch.float32, device=sources[0].device)
+        # windows of full length first (the ladder's shapes), then the T-frame final windows grouped by length
+        jobs.sort(key=lambda j: j[4] != c.window_frames)
+        c._run_jobs(sources, jobs, self.tau, out, self.max_windows_per_launch, ladder=self.ladder)
+        outs = {}
+        for h, (a, b, (f0, _, hi)) in spans.items():
+            outs[h] = out[a * c.spf:b * c.spf]
+            st = self._streams[h]
+            st._emitted = hi
+            if st._closed:
+                self._retire(h)
+            else:
+                st._trim(f0 + 1)        # every later window (regular or the last one) starts after this one
+        return outs

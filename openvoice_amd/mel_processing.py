@@ -90,6 +90,24 @@ class _NativeSpectrogram:
                     scale=1e-6, rows=self.layer.rows, x_ld=ldu, out_ld=lds)
         return spec[:, :, :Tw]
 
+    def windows_multi(self, pool, records, Tw):
+        """``windows`` with one source per window: ``records`` is a device int64 ``[W, 3]`` of (base, n_samples,
+        first_frame), and window w is frames [first_frame, first_frame + Tw) of the waveform
+        ``pool[base:base + n_samples]`` (reflect padding at that span's two ends; ``ov_frame_hops_multi_f32``).
+        ``[W, bins, Tw]``, bit-identical to ``self.windows(pool[base:base + n_samples], n_samples, ...)`` per window."""
+        from . import _lib
+        from .engine import launch_conv, padded_frames
+        W = records.shape[0]
+        pad = (self.n_fft - self.hop) // 2
+        U = Tw + self.n_fft // self.hop - 1
+        ldu, lds = padded_frames(U), padded_frames(Tw)
+        hops = torch.empty(W, self.hop, ldu, dtype=torch.float32, device=pool.device)
+        _lib.call("ov_frame_hops_multi_f32", pool, pool.numel(), records, W, self.hop, pad, U, ldu, hops)
+        spec = torch.zeros(W, self.bins, lds, dtype=torch.float32, device=pool.device)
+        launch_conv(self.layer, hops, 0, self.hop * ldu, spec, 0, self.bins * lds, W, Tw, epi=_lib.EPI_MAGNITUDE,
+                    scale=1e-6, rows=self.layer.rows, x_ld=ldu, out_ld=lds)
+        return spec[:, :, :Tw]
+
 
 def native_spectrogram(device, n_fft, hop):
     """The cached ``_NativeSpectrogram`` of (device, n_fft, hop) -- the object ``spectrogram_torch`` runs on a device."""
