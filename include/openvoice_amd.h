@@ -279,6 +279,20 @@ int ov_frame_hops_multi_f32(const float* pool, int64_t pool_len, const int64_t* 
  * 64-bit output offsets.  ABI 2.10. */
 int ov_stitch_window_cores_f32(const float* o_hat, const int64_t* windows, int W, int Tw, int spf, float* out,
                                int64_t out_len, int64_t out_frame0, ov_stream_t stream);
+/* Record-driven row copy of live streams' carried state (openvoice_amd/live.py): records is a DEVICE int64
+ * [n_records][6] of (src_off, dst_off, rows, cols, src_ld, dst_ld), in elements relative to src_base / dst_base;
+ *   dst_base[dst_off + i * dst_ld + j] = src_base[src_off + i * src_ld + j],  i < rows, j < cols.
+ * One launch serves every unit and stream of a step: a stream's history shift between ping-pong halves, a pool's gather
+ * of ready streams' state from its per-stream arena into batch rows, and the scatter of new columns back; it replaces
+ * the units x streams Python-issued slice copies (torch `dst[...].copy_(src[...])`) a step would otherwise cost.
+ * Source and destination regions of one launch must not overlap.  Host checks: null pointers, n_records in
+ * [1, 65535], extents > 0 (OV_E_BADARG).  The kernel checks every record against src_elems / dst_elems: a record with a
+ * negative, oversized (rows, cols, ld > 2^31) or overlapping-row (rows > 1 and dst_ld < cols) destination, or whose
+ * destination leaves [0, dst_elems), touches nothing; one whose destination is in range but whose source is not writes
+ * zeros there.  Rows move as 16-byte vectors when both bases are 16-byte aligned and the record's offsets and lds are
+ * multiples of 4, as scalars otherwise; 64-bit offsets.  ABI 2.12. */
+int ov_carry_rows_f32(const int64_t* records, int n_records, const float* src_base, int64_t src_elems, float* dst_base,
+                      int64_t dst_elems, ov_stream_t stream);
 
 /* Rate conversion at the audio boundary, reference openvoice/api.py:123,144 (``librosa.load(path, sr=...)`` = resampy's
  * kaiser_best band-limited sinc interpolation): a polyphase FIR over a mono waveform,
@@ -608,7 +622,7 @@ int ov_conv1d_wino_pack_f32(const float* w, int Cout, int Cin, int K, float* dst
  * was `reserved`; the struct grew by one pointer at its end).  2.06: ov_polyphase_fir_f32.  2.07: ov_conv1d_wino_f32 (+ _supported, _chunk,
  * _pack_size, _pack_f32).  2.08: ov_conv1d_wino_f32 instances for Cout % 32 == 0 at K = 11 (one 32-row fragment per
  * workgroup; ov_conv1d_wino_chunk(11, 32) = 2 where 2.07 returned 0).  2.09: ov_conv1d_wino_params.out_slope (the field that
- * was `reserved0`: same size and offset, 0 = none).  2.10: ov_frame_hops_windows_f32, ov_stitch_window_cores_f32.  2.11: ov_frame_hops_multi_f32.  The Python binding
+ * was `reserved0`: same size and offset, 0 = none).  2.10: ov_frame_hops_windows_f32, ov_stitch_window_cores_f32.  2.11: ov_frame_hops_multi_f32.  2.12: ov_carry_rows_f32.  The Python binding
  * refuses a library older than the entry points it calls (openvoice_amd/_lib.py MIN_VERSION). */
 int ov_version(void);
 /* The version THIS header describes.  Parameter structs grow at their END in minor versions (2.04, 2.05, 2.07 did): a
@@ -618,7 +632,7 @@ int ov_version(void);
  * tests/test_abi_cpu.py).  A struct is never reordered and a field never changes meaning within a major version, with
  * one exception stated here: 2.05 renamed ov_wn_layer_params.reserved to row_split AND appended `acts`, so a caller
  * built against 2.04 or older is NOT binary compatible with 2.05+ for that struct. */
-#define OV_ABI_VERSION 211
+#define OV_ABI_VERSION 212
 /* 0 for a production build; non-zero = a measurement build with parts of the kernels compiled out (results are
  * meaningless; openvoice_amd/_lib.py refuses to load it unless OPENVOICE_AMD_ALLOW_EXPERIMENT=1). */
 int ov_build_experiment(void);

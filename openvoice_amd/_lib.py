@@ -22,7 +22,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OPENVOICE_AMD_LIB") or os.path.join(_HERE, "libopenvoice_amd.so")
 
 OV_OK = 0
-MIN_VERSION = 211     # ov_version() of the newest entry point this package calls (include/openvoice_amd.h)
+MIN_VERSION = 212     # ov_version() of the newest entry point this package calls (include/openvoice_amd.h)
 OV_ERRORS = {-1: "OV_E_BADARG", -2: "OV_E_UNSUPPORTED", -3: "OV_E_ALIGN", -4: "OV_E_LAUNCH"}
 
 EPI_LINEAR, EPI_GATE, EPI_RESSKIP, EPI_COUPLE, EPI_POSTERIOR, EPI_CONVT, EPI_MAGNITUDE = range(7)
@@ -175,6 +175,7 @@ SIGNATURES = {
     "ov_frame_hops_windows_f32": (ctypes.c_int, [_fp, _i64, _fp, _i, _i, _i, _i, _i, _fp, _fp]),
     "ov_frame_hops_multi_f32": (ctypes.c_int, [_fp, _i64, _fp, _i, _i, _i, _i, _i, _fp, _fp]),
     "ov_stitch_window_cores_f32": (ctypes.c_int, [_fp, _fp, _i, _i, _i, _fp, _i64, _i64, _fp]),
+    "ov_carry_rows_f32": (ctypes.c_int, [_fp, _i, _fp, _i64, _fp, _i64, _fp]),
     "ov_embed_f32": (ctypes.c_int, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, ctypes.c_float, _fp]),
     "ov_layernorm_ch_f32": (ctypes.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, ctypes.c_float, _i, _fp]),
     "ov_rel_attention_f32": (ctypes.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i64, _i64, _i, _i, _i, _i, _i, _i,

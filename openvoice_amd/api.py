@@ -378,6 +378,27 @@ class ToneColorConverter(OpenVoiceBaseClass):
         ``stream(...)`` fed the same samples with the same noise.  One ``tau`` for the whole pool."""
         return self._windowed(window_frames, 1).stream_pool(tau=tau, max_windows_per_launch=max_windows_per_launch)
 
+    # ---- low-latency live streams ------------------------------------------------------------------------------------
+    def live_stream(self, src_se, tgt_se, tau=0.3, chunk_frames=15, noise=None):
+        """A ``live.LiveStream``: the conversion as a cascade of units that carry their recent input as state.
+        ``push(samples)`` -> newly finished samples, ``close()`` -> the rest, ``latency_samples`` =
+        ``live.live_latency_samples`` (1.45 s at 15 frames).  ``chunk_frames``: a positive multiple of 15 (the Winograd
+        grid).  The fp32 generator only (ValueError with use_bf16_generator / enable_split_bf16x3); never graph-captured.
+        With ``noise`` ``[1, 192, >= T]`` the output equals ``convert_long`` of the whole input."""
+        from . import live
+        d = self.hps.data
+        return live.LiveStream(self.model, src_se, tgt_se, tau=tau, chunk_frames=chunk_frames, noise=noise,
+                               n_fft=d.filter_length, hop=d.hop_length)
+
+    def live_pool(self, tau=0.3, chunk_frames=15, max_streams_per_launch=32):
+        """A ``live.LivePool``: many live streams (``open`` / ``push`` / ``close``), every stream with a ready chunk
+        converted by one ``step()`` in launches of up to ``max_streams_per_launch`` rows per unit.  Each stream equals
+        its solo ``live_stream``.  One ``tau`` for the pool."""
+        from . import live
+        d = self.hps.data
+        return live.LivePool(self.model, tau=tau, chunk_frames=chunk_frames, max_streams_per_launch=max_streams_per_launch,
+                             n_fft=d.filter_length, hop=d.hop_length)
+
     def convert_many(self, items, src_se, tgt_se, tau=0.3, window_frames=longform.DEFAULT_WINDOW_FRAMES,
                      windows_per_launch=longform.DEFAULT_MANY_WINDOWS_PER_LAUNCH, noise=None, output_paths=None,
                      message="default"):

@@ -397,6 +397,7 @@ TORCH_LIBRARY(openvoice_amd, m) {
   bind_device<&ov_frame_hops_f32>(m, "frame_hops_f32");
   bind_device<&ov_frame_hops_windows_f32>(m, "frame_hops_windows_f32");
   bind_device<&ov_frame_hops_multi_f32>(m, "frame_hops_multi_f32");
+  bind_device<&ov_carry_rows_f32>(m, "carry_rows_f32");
   bind_device<&ov_stitch_window_cores_f32>(m, "stitch_window_cores_f32");
   bind_device<&ov_conv_post_tanh_f32>(m, "conv_post_tanh_f32");
   bind_device<&ov_conv_post_tanh_limited_f32>(m, "conv_post_tanh_limited_f32");

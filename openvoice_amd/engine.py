@@ -965,6 +965,91 @@ class ConverterEngine:
         _lib.call("ov_frame_limits_i32", lengths, lim[1], B, int(T), 0)
         return lim
 
+    def _upsample(self, i, x, x_ld, u, B, L, cin, ch, **lim):
+        """leaky_relu(0.1) + ConvTranspose1d of generator stage ``i`` (models.py:278-279): x [B, cin, x_ld] with ``L``
+        valid columns -> u, dense [B, ch, L * stride]."""
+        up = self.ups[i]
+        s = up["stride"]
+        self._conv(up["conv"], x, 0, cin * x_ld, u, 0, ch * L * s, B, L, epi=EPI_CONVT, in_slope=LRELU_SLOPE,
+                   flags=up["flags"], phase_s=s, x_ld=x_ld, tag="ups", alg_flops=2.0 * cin * ch * 2 * s * L * B, **lim)
+
+    def _mrf(self, i, u, t1, ra, acc, ws, B, ch, L, limits, rate):
+        """MRF of generator stage ``i`` on the fp32 kernels: u (dense [B, ch, L]) -> acc = mean of the ResBlock1
+        outputs; t1 / ra are scratch of the same size.  ``limits`` / ``rate``: the length-aware work lists of decode()."""
+        cfg = self.cfg
+        nk = len(cfg["resblock_kernel_sizes"])
+        lim = lambda scale: dict(col_limit=limits, col_limit_scale=scale) if limits is not None else {}
+        bs = ch * L
+        # MRF: mean of the 3 ResBlock1 outputs (models.py:280-286, modules.py:296-306).  The three ResBlocks of a
+        # stage are independent chains until the sum.  At small batches one launch does not fill the chip (batch 1,
+        # stage 0: 108 workgroups for 512 slots; stages 1-3: one partial round of 431), so there the chains run on
+        # separate HIP streams and fill each other's ramps and tails; chain j's last launch waits for chain j - 1's
+        # (the running sum keeps its order: bit-identical to the serial sequence).
+        concurrent = (self.chain_streams > 1 and nk > 1 and B <= self.chain_streams_max_batch and self.profile is None
+                      # the chains' extra scratch is allocated lazily: never from a capturing graph's private pool
+                      and not (torch.cuda.is_current_stream_capturing() and len(ws.get("dec_extra", [])) < 2 * (nk - 1)))
+        scratch = [(t1, ra)]
+        if concurrent:
+            extra = self._chain_scratch(ws, 2 * (nk - 1))
+            scratch += [(extra[2 * j], extra[2 * j + 1]) for j in range(nk - 1)]
+
+        def chain(j, pairs):
+            t1_, ra_ = scratch[j if concurrent else 0]
+            cur = u
+            fused = self.fuse_pairs and L % 4 == 0 and all(
+                (ch, c1.K) in PAIR_POLICY and pair_supported(ch, c1.K, c1.dil) for c1, _ in pairs)
+            # Winograd-domain convs where an instance exists and wino_policy() picks it; they carry the same
+            # length-aware work lists (skip_padding) as the direct kernels
+            wn = self.wino_resblocks[i][j] if (self.use_winograd and L % 4 == 0) else None
+            for n, (c1, c2) in enumerate(pairs):
+                last = n == len(pairs) - 1
+                if last and concurrent and j > 0:
+                    torch.cuda.current_stream(self.device).wait_event(done[j - 1])
+                add = acc if (last and j > 0) else None
+                scale = 1.0 / nk if (last and j == nk - 1) else 1.0
+                if fused:
+                    # one launch per pair, intermediate in LDS; out must not alias x: ra / t1 ping-pong
+                    dst = acc if last else (t1_ if cur is ra_ else ra_)
+                    self._pair(c1, c2, cur, dst, bs, B, L, add, scale, **lim(rate))
+                else:
+                    w1, w2 = wn[n] if wn is not None else (None, None)
+                    if w1 is not None and wino_items(ch, w1.dil, B, L) < WINO_MIN_ITEMS:
+                        w1 = None           # too few items for one workgroup per CU: the direct kernel's small tiles
+                    if w2 is not None and wino_items(ch, 1, B, L) < WINO_MIN_ITEMS:
+                        w2 = None
+                    # t1 is read by c2 only, which activates it: a Winograd c1 stores it activated (the same
+                    # values, modules.py:298-301) and c2 -- either kernel -- stages it as is
+                    if w1 is not None:
+                        self._wino(w1, cur, t1_, bs, B, L, out_slope=LRELU_SLOPE, **lim(rate))
+                    else:
+                        self._conv(c1, cur, 0, bs, t1_, 0, bs, B, L, in_slope=LRELU_SLOPE, tag="mrf", **lim(rate))
+                    c2_slope = 1.0 if w1 is not None else LRELU_SLOPE
+                    dst = acc if last else ra_
+                    if w2 is not None:
+                        self._wino(w2, t1_, dst, bs, B, L, res=cur, add=add, scale=scale, in_slope=c2_slope, **lim(rate))
+                    else:
+                        self._conv(c2, t1_, 0, bs, dst, 0, bs, B, L, in_slope=c2_slope, res=cur, res_bs=bs,
+                                   add=add, add_bs=bs, scale=scale, tag="mrf", **lim(rate))
+                cur = dst
+
+        if not concurrent:
+            for j, pairs in enumerate(self.resblocks[i]):
+                chain(j, pairs)
+        else:
+            main = torch.cuda.current_stream(self.device)
+            side = self._side_streams(nk)
+            fork = torch.cuda.Event()
+            fork.record(main)
+            done = [None] * nk
+            for j, pairs in enumerate(self.resblocks[i]):
+                with torch.cuda.stream(side[j]):
+                    side[j].wait_event(fork)
+                    chain(j, pairs)
+                    done[j] = torch.cuda.Event()
+                    done[j].record(side[j])
+            for j in range(nk):                     # every chain's scratch is free again before the next stage
+                main.wait_event(done[j])
+
     def decode(self, z_hat, cond_d, ws=None, T=None, limits=None):
         """Generator (models.py:272-291).  ``z_hat`` is [B, C, ld] with ``T`` valid frames per row
         (``T`` defaults to the full row, i.e. a dense tensor).  ``limits`` (``frame_limits``): frames per utterance
@@ -990,16 +1075,12 @@ class ConverterEngine:
                    **lim(1))
         x, L, x_ld = ws["pre"], T, Tp
         free = list(ws["dec"])
-        nk = len(cfg["resblock_kernel_sizes"])
         rate = 1                                  # columns per frame at the current stage
         for i, up in enumerate(self.ups):
             s = up["stride"]
             cin, ch = ch, ch // 2
             u = free.pop()
-            # leaky_relu(0.1) + ConvTranspose1d (models.py:278-279)
-            self._conv(up["conv"], x, 0, cin * x_ld, u, 0, ch * L * s, B, L, epi=EPI_CONVT, in_slope=LRELU_SLOPE,
-                       flags=up["flags"], phase_s=s, x_ld=x_ld, tag="ups", alg_flops=2.0 * cin * ch * 2 * s * L * B,
-                       **lim(rate))
+            self._upsample(i, x, x_ld, u, B, L, cin, ch, **lim(rate))
             rate *= s
             if i > 0:
                 free.append(x)
@@ -1013,76 +1094,7 @@ class ConverterEngine:
                 x = acc
                 continue
             t1, ra, acc = free.pop(), free.pop(), free.pop()
-            bs = ch * L
-            # MRF: mean of the 3 ResBlock1 outputs (models.py:280-286, modules.py:296-306).  The three ResBlocks of a
-            # stage are independent chains until the sum.  At small batches one launch does not fill the chip (batch 1,
-            # stage 0: 108 workgroups for 512 slots; stages 1-3: one partial round of 431), so there the chains run on
-            # separate HIP streams and fill each other's ramps and tails; chain j's last launch waits for chain j - 1's
-            # (the running sum keeps its order: bit-identical to the serial sequence).
-            concurrent = (self.chain_streams > 1 and nk > 1 and B <= self.chain_streams_max_batch and self.profile is None
-                          # the chains' extra scratch is allocated lazily: never from a capturing graph's private pool
-                          and not (torch.cuda.is_current_stream_capturing() and len(ws.get("dec_extra", [])) < 2 * (nk - 1)))
-            scratch = [(t1, ra)]
-            if concurrent:
-                extra = self._chain_scratch(ws, 2 * (nk - 1))
-                scratch += [(extra[2 * j], extra[2 * j + 1]) for j in range(nk - 1)]
-
-            def chain(j, pairs):
-                t1_, ra_ = scratch[j if concurrent else 0]
-                cur = u
-                fused = self.fuse_pairs and L % 4 == 0 and all(
-                    (ch, c1.K) in PAIR_POLICY and pair_supported(ch, c1.K, c1.dil) for c1, _ in pairs)
-                # Winograd-domain convs where an instance exists and wino_policy() picks it; they carry the same
-                # length-aware work lists (skip_padding) as the direct kernels
-                wn = self.wino_resblocks[i][j] if (self.use_winograd and L % 4 == 0) else None
-                for n, (c1, c2) in enumerate(pairs):
-                    last = n == len(pairs) - 1
-                    if last and concurrent and j > 0:
-                        torch.cuda.current_stream(self.device).wait_event(done[j - 1])
-                    add = acc if (last and j > 0) else None
-                    scale = 1.0 / nk if (last and j == nk - 1) else 1.0
-                    if fused:
-                        # one launch per pair, intermediate in LDS; out must not alias x: ra / t1 ping-pong
-                        dst = acc if last else (t1_ if cur is ra_ else ra_)
-                        self._pair(c1, c2, cur, dst, bs, B, L, add, scale, **lim(rate))
-                    else:
-                        w1, w2 = wn[n] if wn is not None else (None, None)
-                        if w1 is not None and wino_items(ch, w1.dil, B, L) < WINO_MIN_ITEMS:
-                            w1 = None           # too few items for one workgroup per CU: the direct kernel's small tiles
-                        if w2 is not None and wino_items(ch, 1, B, L) < WINO_MIN_ITEMS:
-                            w2 = None
-                        # t1 is read by c2 only, which activates it: a Winograd c1 stores it activated (the same
-                        # values, modules.py:298-301) and c2 -- either kernel -- stages it as is
-                        if w1 is not None:
-                            self._wino(w1, cur, t1_, bs, B, L, out_slope=LRELU_SLOPE, **lim(rate))
-                        else:
-                            self._conv(c1, cur, 0, bs, t1_, 0, bs, B, L, in_slope=LRELU_SLOPE, tag="mrf", **lim(rate))
-                        c2_slope = 1.0 if w1 is not None else LRELU_SLOPE
-                        dst = acc if last else ra_
-                        if w2 is not None:
-                            self._wino(w2, t1_, dst, bs, B, L, res=cur, add=add, scale=scale, in_slope=c2_slope, **lim(rate))
-                        else:
-                            self._conv(c2, t1_, 0, bs, dst, 0, bs, B, L, in_slope=c2_slope, res=cur, res_bs=bs,
-                                       add=add, add_bs=bs, scale=scale, tag="mrf", **lim(rate))
-                    cur = dst
-
-            if not concurrent:
-                for j, pairs in enumerate(self.resblocks[i]):
-                    chain(j, pairs)
-            else:
-                main = torch.cuda.current_stream(self.device)
-                side = self._side_streams(nk)
-                fork = torch.cuda.Event()
-                fork.record(main)
-                done = [None] * nk
-                for j, pairs in enumerate(self.resblocks[i]):
-                    with torch.cuda.stream(side[j]):
-                        side[j].wait_event(fork)
-                        chain(j, pairs)
-                        done[j] = torch.cuda.Event()
-                        done[j].record(side[j])
-                for j in range(nk):                     # every chain's scratch is free again before the next stage
-                    main.wait_event(done[j])
+            self._mrf(i, u, t1, ra, acc, ws, B, ch, L, limits, rate)
             free += [u, t1, ra]
             x = acc
         o_hat = torch.empty(B, 1, L, dtype=torch.float32, device=self.device)
@@ -1092,6 +1104,110 @@ class ConverterEngine:
         else:
             _lib.call("ov_conv_post_tanh_f32", x, self.post_w, o_hat, B, ch, L, self.post_w.shape[1], FINAL_LRELU_SLOPE)
         return o_hat
+
+    # ---- live streams (openvoice_amd/live.py): one conversion unit on caller-given buffers -----------------------
+    # A unit runs on B rows of [left history | new columns] of equal width L, with the kernels' ordinary "same" zero
+    # padding at both ends; the caller keeps the output columns whose receptive field lies inside the buffer.  Inputs and
+    # outputs are views of the caller's memory with explicit row (ld) and batch strides; the scratch comes from
+    # ``live_workspace`` (sized by the unit's widest buffer, never by a file length).
+    def live_workspace(self, key, B, width, stage=None):
+        """Scratch of one live unit launch of ``B`` rows, ``width`` input columns at most; allocated once per
+        ``(key, B)`` and kept (``self.live_ws_builds`` counts the allocations).  Frame-rate units (``stage`` None): the
+        WaveNet tensors and the mask in the ``_workspace`` layout (ld = ``padded_frames(width)``).  Generator stage i:
+        the conv_pre output (stage 0), the ConvTranspose output and the two MRF scratch buffers, and the MRF output of
+        the last stage (conv_post reads it)."""
+        cache = self.__dict__.setdefault("_live_ws", {})
+        ws = cache.get((key, B))
+        if ws is not None:
+            assert ws["width"] >= width, "live unit wider than its workspace"
+            return ws
+        self.live_ws_builds = getattr(self, "live_ws_builds", 0) + 1
+        dev, H = self.device, self.hidden
+        z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
+        Tp = padded_frames(width)
+        if stage is None:
+            ws = dict(Tp=Tp, mask=z(B, Tp), mask_len=-1, h=z(B, H, Tp), h2=z(B, H, Tp), acts=z(B, H, Tp),
+                      skip=z(B, H, Tp))
+        else:
+            ch, rate_in = self.cfg["upsample_initial_channel"], 1
+            for u in self.cfg["upsample_rates"][:stage]:
+                ch, rate_in = ch // 2, rate_in * u
+            out_cols = width * self.cfg["upsample_rates"][stage]
+            n = B * (ch // 2) * out_cols
+            ws = dict(Tp=Tp, dec=[z(n) for _ in range(3)])
+            if stage == 0:
+                ws["pre"] = z(B, ch, Tp)
+            if stage == len(self.cfg["upsample_rates"]) - 1:
+                ws["acc"] = z(n)
+        ws["width"] = width
+        cache[(key, B)] = ws
+        return ws
+
+    def live_conds(self, g_src, g_tgt):
+        """Per-row conditioning of a live launch (``g_src`` / ``g_tgt`` [B, gin]): the WaveNet gate biases of the
+        posterior encoder and of every coupling in both directions, and the generator's cond bias."""
+        g_q = self._zeros_like_cached(g_src) if self.zero_g else g_src
+        g_d = self._zeros_like_cached(g_tgt) if self.zero_g else g_tgt
+        return dict(q=self._wn_cond(self.q_wn, g_q), src=[self._wn_cond(cp["wn"], g_src) for cp in self.couplings],
+                    tgt=[self._wn_cond(cp["wn"], g_tgt) for cp in self.couplings],
+                    d=self._linear(g_d, self.dec_cond_w, self.dec_cond_b))
+
+    def _live_mask(self, ws, B, L):
+        if ws["mask_len"] != L:
+            lengths = torch.full((B,), L, dtype=torch.int64, device=self.device)
+            _lib.call("ov_sequence_mask_f32", lengths, ws["mask"], B, L, ws["Tp"])
+            ws["mask_len"] = L
+        return ws["mask"]
+
+    @torch.no_grad()
+    @on_own_device
+    def live_posterior(self, spec, spec_ld, spec_bs, noise, noise_bs, out, ld, bs, B, L, cond_q, tau, ws):
+        """Posterior encoder unit (models.py:212-221: q_pre, the 16-layer WaveNet, q_proj with ``OV_EPI_POSTERIOR``):
+        ``spec`` [B rows of ``spec_bs``][513][``spec_ld``] -> ``out`` z [B rows of ``bs``][inter][``ld``]; ``noise``
+        [B rows of ``noise_bs``][inter][``ld``]; ``L`` columns; ``cond_q`` the rows' gate biases (``live_conds``).""" 
+        H, C, Tp = self.hidden, self.inter, ws["Tp"]
+        mask = self._live_mask(ws, B, L)
+        self._conv(self.q_pre, spec, 0, spec_bs, ws["h"], 0, H * Tp, B, L, flags=F_MASK_V, mask=mask, mask_bs=Tp,
+                   x_ld=spec_ld, out_ld=Tp, tag="q_pre")
+        self._wavenet(self.q_wn, ws, B, L, cond_q, mask)
+        self._conv(self.q_proj, ws["skip"], 0, H * Tp, out, 0, bs, B, L, epi=EPI_POSTERIOR, res=noise, res_bs=noise_bs,
+                   scale=float(tau), mask=mask, mask_bs=Tp, rows=2 * C, x_ld=Tp, out_ld=ld, tag="q_proj")
+
+    @torch.no_grad()
+    @on_own_device
+    def live_flow(self, src, dst, B, L, conds, reverse, ws):
+        """One flow direction (models.py:390-397) as a unit: ``src`` -> ``dst``, both [B][inter][ws Tp] (``_flow``'s
+        layout), ``L`` columns, ``conds`` the rows' per-coupling gate biases."""
+        self._flow(src, dst, ws, B, L, conds, self._live_mask(ws, B, L), reverse)
+
+    @torch.no_grad()
+    @on_own_device
+    def live_generator_stage(self, i, x, x_ld, x_bs, out, B, L, ws, cond_d=None):
+        """Generator stage ``i`` as a unit (models.py:274-291): [conv_pre + cond (stage 0)], leaky_relu, the
+        ConvTranspose and the MRF; the last stage adds leaky_relu(0.01), conv_post and tanh.  ``x`` [B rows of
+        ``x_bs``][C_in][``x_ld``] with ``L`` columns -> ``out`` dense [B, C_out, L * stride] ([B, 1, L * stride] for the
+        last stage).  ``decode``'s own launches (``_upsample``, ``_mrf``): bit-identical per column to a one-pass run
+        whose columns line up with the same Winograd tiles."""
+        if getattr(self, "_bf16_on", False) or self._split3_on:
+            raise _lib.OvError("live streams run the fp32 generator only (use_bf16_generator / split_bf16x3 are off)")
+        cfg = self.cfg
+        ch = cfg["upsample_initial_channel"]
+        for _ in range(i):
+            ch //= 2
+        if i == 0:
+            Tp = ws["Tp"]
+            self._conv(self.conv_pre, x, 0, x_bs, ws["pre"], 0, ch * Tp, B, L, bias_b=cond_d,
+                       bias_b_bs=0 if cond_d.shape[0] == 1 else cond_d.shape[1], x_ld=x_ld, out_ld=Tp, tag="conv_pre")
+            x, x_ld, x_bs = ws["pre"], Tp, ch * Tp
+        s = self.ups[i]["stride"]
+        u, t1, ra = ws["dec"]
+        self._upsample(i, x, x_ld, u, B, L, ch, ch // 2)
+        last = i == len(self.ups) - 1
+        acc = ws["acc"] if last else out
+        self._mrf(i, u, t1, ra, acc, ws, B, ch // 2, L * s, None, 1)
+        if last:
+            _lib.call("ov_conv_post_tanh_f32", acc, self.post_w, out, B, ch // 2, L * s, self.post_w.shape[1],
+                      FINAL_LRELU_SLOPE)
 
     # ---- extract_se path -----------------------------------------------------------------------------
     @torch.no_grad()

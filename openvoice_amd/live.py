@@ -1,0 +1,588 @@
+"""Low-latency live streams: the conversion as a cascade of units that keep their recent input as state.
+
+``longform.ConversionStream`` recomputes 2 x 120 frames of context per window, so its latency is the window
+(3.0 s at the smallest) and at low latency most of its work is context.  Here every stage of the conversion is a
+**unit** that runs the engine's own launches on a buffer ``[left history | new columns]`` with the kernels' "same" zero
+padding and keeps only the output columns whose receptive field lies inside the buffer:
+
+* ``q``: posterior encoder (q_pre, 16 WaveNet layers, q_proj with the noise), frame rate;
+* ``f`` / ``r``: the flow forward with ``g_src`` / reverse with ``g_tgt``, frame rate;
+* ``g0 .. g3``: one generator stage each (leaky_relu, ConvTranspose, MRF; conv_pre + cond in ``g0``, conv_post + tanh in
+  the last one), at that stage's input column rate.
+
+A unit with input columns ``[0, n)`` received emits the output of input columns ``[e, n - right)`` (everything, once its
+input is complete).  The buffer it runs on starts ``left`` columns before ``e``, rounded down to the unit's ``align``
+grid: for a generator stage that grid puts the buffer's first output column on the stage's Winograd tile grid
+(``4 x dil`` columns, lcm over the dilations), so tiles keep their one-pass phase.  At the file start the kernels' zero
+padding is what one pass sees; at the end (``close``) the spectrogram's reflect padding is applied and every unit runs
+once more up to its true right end, never past frame ``T`` (the generator is unmasked).
+
+Only the input chunk is quantised: the stream advances the posterior encoder by ``chunk_frames`` interior frames at a
+time; every downstream unit emits all it can.  A sample therefore leaves ``live_latency_samples`` =
+``R + hop * chunk + (n_fft - hop) / 2`` input samples after it arrived at most, ``R`` = the units' right reaches in
+samples (``live_right_samples``).
+
+Device side, a ``LivePool`` keeps each stream's unit states in one arena slot per stream (two halves per unit, so a
+history shift never overlaps itself).  For every unit and launch, ``ov_carry_rows_f32`` gathers the ready streams'
+buffers into batch rows (and shifts their kept history into the other half) in one launch, the unit runs on the batch,
+and a second carry scatters the new columns into the next unit's state.  ``LiveStream`` is a pool of one.
+"""
+import math
+
+import torch
+
+from . import _lib
+from .longform import launch_ladder, stream_end_frames, winograd_grid_frames
+from .params import ENC_Q_KERNEL, ENC_Q_LAYERS, FLOW_KERNEL, FLOW_LAYERS, N_FLOWS
+
+DEFAULT_CHUNK_FRAMES = 15
+DEFAULT_LIVE_STREAMS_PER_LAUNCH = 32
+CONV_PRE_KERNEL = 7
+CONV_POST_KERNEL = 7
+
+
+def _stage_tile(cfg):
+    """Winograd tile grid of a generator stage in its own columns: lcm of 4 * dil over dilation 1 (the convs2) and the
+    configured ones (the convs1) -- what ``winograd_grid_frames`` aligns."""
+    tile = 4
+    for d in [1] + [v for dl in cfg["resblock_dilation_sizes"] for v in dl]:
+        tile = tile * 4 * d // math.gcd(tile, 4 * d)
+    return tile
+
+
+def live_units(cfg):
+    """The unit table, a pure function of the config: one dict per unit in cascade order with
+
+    * ``name``, ``kind`` (``q`` / ``f`` / ``r`` / ``g``), ``stage`` (generator stage or None);
+    * ``rate``: input columns per frame; ``stride``: output columns per input column;
+    * ``left`` / ``right``: the reach of one output column into the unit's input, in input columns;
+    * ``align``: the buffer start is a multiple of it (input columns);
+    * ``history``: input columns kept before the first column still to emit, at most (``left + align - 1``).
+
+    Frame-rate units: a WaveNet of n layers of kernel k (dilation 1) reaches n (k - 1) / 2 frames each way; q_pre,
+    q_proj and the coupling pre / post are 1 x 1.  Generator stage i (stride s, kernel 2 s, padding (k - s) / 2): the MRF
+    reaches rho = max over ResBlocks of (k - 1) / 2 * (sum(dil) + len(dil)) output columns (+ (7 - 1) / 2 for conv_post
+    on the last stage); the ConvTranspose maps output column j to inputs [ceil((j + pad - k + 1) / s), floor((j + pad) /
+    s)], so right = floor((s - 1 + rho + pad) / s) and left = floor((rho + k - 1 - pad) / s); conv_pre adds 3 frames to
+    both on stage 0.  Released configurations: q / f / r 32 each way, g0 11, g1 8, g2 31, g3 32 (input columns)."""
+    units = [dict(name="q", kind="q", stage=None, rate=1, stride=1, left=ENC_Q_LAYERS * (ENC_Q_KERNEL - 1) // 2,
+                  right=ENC_Q_LAYERS * (ENC_Q_KERNEL - 1) // 2, align=1)]
+    flow = N_FLOWS * FLOW_LAYERS * (FLOW_KERNEL - 1) // 2
+    units.append(dict(name="f", kind="f", stage=None, rate=1, stride=1, left=flow, right=flow, align=1))
+    units.append(dict(name="r", kind="r", stage=None, rate=1, stride=1, left=flow, right=flow, align=1))
+    tile = _stage_tile(cfg)
+    rho_mrf = max((k - 1) // 2 * (sum(d) + len(d)) for k, d in
+                  zip(cfg["resblock_kernel_sizes"], cfg["resblock_dilation_sizes"]))
+    rates, kernels = cfg["upsample_rates"], cfg["upsample_kernel_sizes"]
+    rate = 1
+    for i, (s, k) in enumerate(zip(rates, kernels)):
+        pad = (k - s) // 2
+        rho = rho_mrf + ((CONV_POST_KERNEL - 1) // 2 if i == len(rates) - 1 else 0)
+        right = (s - 1 + rho + pad) // s
+        left = (rho + k - 1 - pad) // s
+        if i == 0:
+            left += (CONV_PRE_KERNEL - 1) // 2
+            right += (CONV_PRE_KERNEL - 1) // 2
+        units.append(dict(name=f"g{i}", kind="g", stage=i, rate=rate, stride=s, left=left, right=right,
+                          align=tile // math.gcd(tile, s)))
+        rate *= s
+    for u in units:
+        u["history"] = u["left"] + u["align"] - 1
+    return units
+
+
+def samples_per_frame(cfg):
+    spf = 1
+    for s in cfg["upsample_rates"]:
+        spf *= s
+    return spf
+
+
+def live_right_samples(cfg):
+    """Sum of the units' right reaches in output samples (each unit's right reach x the samples one of its input
+    columns spans).  27 836 (108.7 frames) for the released configurations."""
+    spf = samples_per_frame(cfg)
+    return sum(u["right"] * spf // u["rate"] for u in live_units(cfg))
+
+
+def check_chunk(cfg, chunk_frames):
+    g = winograd_grid_frames(cfg)
+    if isinstance(chunk_frames, bool) or not isinstance(chunk_frames, int) or chunk_frames <= 0 or chunk_frames % g:
+        raise ValueError(f"chunk_frames must be a positive multiple of {g} (the Winograd grid), got {chunk_frames!r}")
+    return chunk_frames
+
+
+def live_latency_samples(cfg, chunk_frames, n_fft=1024, hop=256):
+    """The bound no output sample's delay exceeds: input samples that arrive after sample t before sample t of the
+    output leaves.  Output sample t leaves once the posterior encoder has taken ``m = floor((t + R) / hop) + 1`` frames
+    rounded up to the chunk, i.e. frames up to ``c * ceil(m / c)``; frame f is interior (no end reflect padding can
+    reach it) from ``f * hop + n_fft - pad`` samples on.  The worst case over t is
+    ``R + hop * chunk_frames + (n_fft - hop) / 2`` (R = ``live_right_samples``, hop = samples per frame): 32 060
+    samples (1.45 s at 22.05 kHz) at 15 frames for the released configurations."""
+    check_chunk(cfg, chunk_frames)
+    return live_right_samples(cfg) + hop * chunk_frames + (n_fft - hop) // 2
+
+
+def interior_frames(n_samples, n_fft, hop):
+    """Spectrogram frames whose samples have all arrived (no end reflect padding reaches them)."""
+    pad = (n_fft - hop) // 2
+    n = int(n_samples) + pad - n_fft
+    return 0 if n < 0 else n // hop + 1
+
+
+def _start(u, e):
+    """First input column of a buffer whose first emitted column is e: ``left`` before it, down to ``align``."""
+    return max(0, (e - u["left"]) // u["align"] * u["align"])
+
+
+class Cascade:
+    """Host bookkeeping of one stream through the units (no device work): ``round(new_frames, final)`` appends
+    posterior-encoder input and returns the pieces the units run this round, in cascade order, at most one per unit:
+    ``(k, b0, end, e0, e1)`` = unit k runs on input columns ``[b0, end)`` and keeps the output of ``[e0, e1)``.  A unit
+    emits ``[e, n - right)`` (``[e, n)`` once its input is complete), at most ``chunk x rate`` columns per round, so a
+    buffer never exceeds ``history + chunk x rate + right`` columns (``width``) and a unit's stored input
+    ``history + right + 2 x chunk x rate`` (``capacity``)."""
+
+    def __init__(self, units, chunk_frames):
+        self.units, self.c = units, int(chunk_frames)
+        K = len(units)
+        self.n = [0] * K            # input columns received
+        self.e = [0] * K            # input columns whose output has been emitted
+        self.s0 = [0] * K           # first input column still stored
+        self.final = False
+
+    def width(self, k):
+        u = self.units[k]
+        return u["history"] + self.c * u["rate"] + u["right"]
+
+    def capacity(self, k):
+        u = self.units[k]
+        return u["history"] + u["right"] + 2 * self.c * u["rate"]
+
+    @property
+    def done(self):
+        return self.final and all(e == n for e, n in zip(self.e, self.n))
+
+    def round(self, new_frames, final=False):
+        self.n[0] += int(new_frames)
+        self.final = self.final or bool(final)
+        pieces, complete = [], self.final
+        for k, u in enumerate(self.units):
+            complete = complete and (k == 0 or self.e[k - 1] == self.n[k - 1])
+            n, e0 = self.n[k], self.e[k]
+            e1 = min(n if complete else n - u["right"], e0 + self.c * u["rate"])
+            if e1 <= e0:
+                continue
+            b0, end = _start(u, e0), min(n, e1 + u["right"])
+            pieces.append((k, b0, end, e0, e1))
+            self.e[k] = e1
+            self.s0[k] = _start(u, e1)
+            if k + 1 < len(self.units):
+                self.n[k + 1] += (e1 - e0) * u["stride"]
+        return pieces
+
+
+class _Live:
+    """One stream of a ``LivePool``: waveform buffer, noise, cascade bookkeeping and its arena slot."""
+
+    def __init__(self, pool, slot, src_se, tgt_se, noise):
+        self.pool, self.slot = pool, slot
+        dev = pool.device
+        self.cas = Cascade(pool.units, pool.chunk)
+        self.buf = torch.empty(0, dtype=torch.float32, device=dev)
+        self.len = 0                # valid samples in buf
+        self.base = 0               # file index of buf[0]; a multiple of hop
+        self.n = 0                  # samples received
+        self.noise = noise.to(dev, torch.float32) if noise is not None else None
+        if self.noise is not None and (self.noise.dim() != 3 or self.noise.shape[:2] != (1, pool.inter)):
+            raise ValueError(f"noise must be [1, {pool.inter}, >= T], got {tuple(self.noise.shape)}")
+        eng = pool.engine
+        g_src = src_se.to(dev, torch.float32).reshape(1, -1)
+        g_tgt = tgt_se.to(dev, torch.float32).reshape(1, -1)
+        self.conds = eng.live_conds(g_src, g_tgt)
+        K = len(pool.units)
+        self.stored = [0] * K       # executor view: input columns stored = [s0, stored)
+        self.s0 = [0] * K
+        self.half = [0] * K
+        self.closed = False
+        self.T = None
+
+    def append(self, x):
+        n = x.numel()
+        if self.len + n > self.buf.numel():
+            grown = torch.empty(max(2 * self.buf.numel(), self.len + n, 1 << 16), dtype=torch.float32,
+                                device=self.buf.device)
+            grown[:self.len].copy_(self.buf[:self.len])
+            self.buf = grown
+        self.buf[self.len:self.len + n].copy_(x)
+        self.len += n
+        self.n += n
+
+    def trim(self):
+        """Drop samples no later frame reads (whole hops, from before the reflect padding of the next frame)."""
+        p = self.pool
+        base = max(0, self.cas.n[0] * p.hop - -(-p.pad // p.hop) * p.hop)
+        if base > self.base:
+            keep = self.buf[base - self.base:self.len].clone()
+            self.buf, self.len, self.base = keep, keep.numel(), base
+
+    def noise_for(self, f0, nf):
+        p = self.pool
+        if self.noise is None:
+            return torch.randn(p.inter, nf, dtype=torch.float32, device=p.device)
+        if self.noise.shape[2] < f0 + nf:
+            raise ValueError(f"noise has {self.noise.shape[2]} frames, the stream needs {f0 + nf}")
+        return self.noise[0, :, f0:f0 + nf]
+
+    def ready(self):
+        """New posterior-encoder frames of the next round (None: no round)."""
+        c = self.pool.chunk
+        if self.closed:
+            return None if self.cas.done else min(c, self.T - self.cas.n[0])
+        if interior_frames(self.n, self.pool.n_fft, self.pool.hop) >= self.cas.n[0] + c:
+            return c
+        return None
+
+
+class LivePool:
+    """Many live streams stepped together (see the module docstring).  ``open(src_se, tgt_se, noise=None)`` -> handle;
+    ``push(h, samples)`` buffers; ``step()`` runs every stream with a ready chunk (and every closed stream's remaining
+    rounds) -> ``{handle: newly finished samples}`` (device tensors); ``close(h)`` marks the end of h's input.  Rounds:
+    every ready stream advances by one chunk per round, each unit runs its streams' buffers in launches of up to
+    ``max_streams_per_launch`` rows grouped by buffer width (steady-state streams share one width; a stream's first
+    rounds and its end run narrower), padded up to the ``launch_ladder`` sizes.  ``tau`` is one scalar for the pool.
+    Live units run eagerly, never from a captured graph."""
+
+    def __init__(self, model, tau=0.3, chunk_frames=DEFAULT_CHUNK_FRAMES,
+                 max_streams_per_launch=DEFAULT_LIVE_STREAMS_PER_LAUNCH, n_fft=1024, hop=256):
+        self.model, self.tau = model, float(tau)
+        self.cfg = model.model_cfg
+        self.chunk = check_chunk(self.cfg, chunk_frames)
+        eng = model.engine()
+        if getattr(eng, "_bf16_on", False) or getattr(eng, "_split3_on", False):
+            raise ValueError("live streams run the fp32 generator only: turn use_bf16_generator / enable_split_bf16x3 off")
+        self.engine = eng
+        self.device = eng.device
+        self.n_fft, self.hop, self.pad = int(n_fft), int(hop), (int(n_fft) - int(hop)) // 2
+        self.bins = self.n_fft // 2 + 1
+        self.inter = self.cfg["inter_channels"]
+        self.spf = samples_per_frame(self.cfg)
+        self.ladder = launch_ladder(max_streams_per_launch)
+        self.M = self.ladder[-1]
+        self.units = live_units(self.cfg)
+        self.latency_samples = live_latency_samples(self.cfg, self.chunk, self.n_fft, self.hop)
+        self._layout()
+        self._streams, self._retired, self._next = {}, set(), 0
+        self._free_slots, self._slots = [], 0
+        self.mem = None
+
+    # ---- memory layout --------------------------------------------------------------------------------------------
+    def _layout(self):
+        """Offsets (elements) in the one device tensor ``mem``: the batch slabs of M rows per unit (in / out) and the
+        staging rows of new frames first, then one arena slot per stream (every unit's two state halves)."""
+        pad4 = lambda n: (n + 3) // 4 * 4
+        from .engine import padded_frames
+        cas = Cascade(self.units, self.chunk)
+        ch = self.cfg["upsample_initial_channel"]
+        self.rows, self.cap, self.width, self.ld_in, self.ld_out, self.cout = [], [], [], [], [], []
+        for k, u in enumerate(self.units):
+            W = cas.width(k)
+            self.width.append(W)
+            self.cap.append(pad4(cas.capacity(k)))
+            if u["kind"] == "g":
+                cin = self.inter if u["stage"] == 0 else ch
+                ch //= 2
+                cout = ch
+                if u["stage"] == len(self.cfg["upsample_rates"]) - 1:
+                    cout = 1
+                self.ld_in.append(pad4(W))
+                self.ld_out.append(W * u["stride"])           # dense per launch: ld = L * stride
+            else:
+                cin = self.bins + self.inter if u["kind"] == "q" else self.inter
+                cout = self.inter
+                self.ld_in.append(padded_frames(W))               # the frame units' workspace layout (ld = Tp)
+                self.ld_out.append(padded_frames(W))
+            self.rows.append(cin)
+            self.cout.append(cout)
+        off, M = 0, self.M
+        self.in_off, self.out_off = [], []
+        for k in range(len(self.units)):
+            self.in_off.append(off)
+            off += pad4(M * self.rows[k] * self.ld_in[k])
+            self.out_off.append(off)
+            off += pad4(M * self.cout[k] * self.ld_out[k])
+        self.stage_ld = pad4(self.chunk)                          # a round appends at most one chunk of frames
+        self.stage_off = off
+        off += M * self.rows[0] * self.stage_ld
+        self.arena_off = off
+        self.state_off, so = [], 0
+        for k in range(len(self.units)):
+            self.state_off.append(so)
+            so += 2 * self.rows[k] * self.cap[k]
+        self.slot_elems = so
+
+    def state_bytes_per_stream(self):
+        """Device bytes one open stream adds: its arena slot (every unit's two state halves) and its conditioning rows
+        (the WaveNet gate biases of the posterior encoder and of both flow directions, the generator's cond bias).  Its
+        waveform buffer (>= 256 KiB, trimmed to the frames still to come) and an explicit noise tensor come on top.
+        5.6 MB at 15 frames for the released configurations."""
+        H, cfg = self.cfg["hidden_channels"], self.cfg
+        conds = 2 * H * ENC_Q_LAYERS + 2 * N_FLOWS * 2 * H * FLOW_LAYERS + cfg["upsample_initial_channel"]
+        return 4 * (self.slot_elems + conds)
+
+    def _state(self, st, k, half):
+        return self.arena_off + st.slot * self.slot_elems + self.state_off[k] + half * self.rows[k] * self.cap[k]
+
+    def _ensure_mem(self):
+        need = self.arena_off + self._slots * self.slot_elems
+        if self.mem is None or self.mem.numel() < need:
+            grown = torch.zeros(need, dtype=torch.float32, device=self.device)
+            if self.mem is not None:
+                grown[:self.mem.numel()].copy_(self.mem)
+            self.mem = grown
+
+    # ---- streams --------------------------------------------------------------------------------------------------
+    @property
+    def active(self):
+        return list(self._streams)
+
+    def open(self, src_se, tgt_se, noise=None):
+        if not self._free_slots:                 # the arena doubles: streams already open keep their slots
+            grown = max(1, 2 * self._slots)
+            self._free_slots = list(range(grown - 1, self._slots - 1, -1)) + self._free_slots
+            self._slots = grown
+            self._ensure_mem()
+        slot = self._free_slots.pop()
+        h = self._next
+        self._next += 1
+        self._streams[h] = _Live(self, slot, src_se, tgt_se, noise)
+        return h
+
+    def _stream(self, h):
+        st = self._streams.get(h)
+        if st is None:
+            raise RuntimeError(f"stream {h!r} is closed" if h in self._retired else f"no stream {h!r} in this pool")
+        return st
+
+    @torch.no_grad()
+    def push(self, h, samples):
+        st = self._stream(h)
+        if st.closed:
+            raise RuntimeError(f"push() after close() on stream {h!r}")
+        st.append(torch.as_tensor(samples, dtype=torch.float32).reshape(-1).to(self.device))
+
+    def close(self, h):
+        """End of h's input; too short an input raises ValueError here and retires h (the others are untouched)."""
+        st = self._stream(h)
+        if st.closed:
+            raise RuntimeError(f"close() called twice on stream {h!r}")
+        st.closed = True
+        try:
+            st.T = stream_end_frames(st.n, self.n_fft, self.hop)
+            if st.noise is not None and st.noise.shape[2] < st.T:
+                raise ValueError(f"noise has {st.noise.shape[2]} frames, the stream needs {st.T}")
+        except ValueError:
+            self._retire(h)
+            raise
+
+    def _retire(self, h):
+        st = self._streams.pop(h)
+        st.buf, st.len = st.buf[:0], 0
+        self._free_slots.append(st.slot)
+        self._retired.add(h)
+
+    # ---- stepping -------------------------------------------------------------------------------------------------
+    def _carry(self, recs, dst=None):
+        if not recs:
+            return
+        dst = self.mem if dst is None else dst
+        table = torch.tensor(recs, dtype=torch.int64).to(self.device)
+        for i in range(0, len(recs), 65535):
+            _lib.call("ov_carry_rows_f32", table[i:i + 65535], min(65535, len(recs) - i), self.mem, self.mem.numel(),
+                      dst, dst.numel())
+
+    def _batches(self, items, key):
+        """Items grouped by ``key`` in order, in launches of up to M, each padded up to a ladder size."""
+        groups = {}
+        for it in items:
+            groups.setdefault(key(it), []).append(it)
+        for kv, its in groups.items():
+            for i in range(0, len(its), self.M):
+                chunk = its[i:i + self.M]
+                B = min(b for b in self.ladder if b >= len(chunk))
+                yield kv, chunk, B
+
+    def _feed(self, jobs):
+        """New posterior-encoder frames of every ready stream: the spectrogram of frames [n_q, n_q + nf) of its
+        waveform (bit-identical to the whole file's) and its noise into the staging rows, then carried onto the end of
+        the stream's posterior state."""
+        from .mel_processing import native_spectrogram
+        spec_eng = native_spectrogram(self.device, self.n_fft, self.hop)
+        bins, rows0, sld = self.bins, self.rows[0], self.stage_ld
+        for nf, chunk, _ in self._batches([j for j in jobs if j[1] > 0], key=lambda j: j[1]):
+            srcs, recs, acc = [], [], 0
+            for st, _, f0 in chunk:
+                wave = st.buf[:st.len]
+                srcs.append(wave)
+                recs.append((acc, st.len, f0 - st.base // self.hop))
+                acc += st.len
+            pool = srcs[0] if len(srcs) == 1 else torch.cat(srcs)
+            rec_dev = torch.tensor(recs, dtype=torch.int64).to(self.device)
+            spec = spec_eng.windows_multi(pool, rec_dev, nf)
+            W = len(chunk)
+            stage = self.mem[self.stage_off:self.stage_off + W * rows0 * sld].view(W, rows0, sld)
+            stage[:, :bins, :nf].copy_(spec)
+            stage[:, bins:, :nf].copy_(torch.stack([st.noise_for(f0, nf) for st, _, f0 in chunk]))
+            carry = []
+            for w, (st, _, f0) in enumerate(chunk):
+                k = 0
+                col = st.stored[k] - st.s0[k]
+                if col + nf > self.cap[k]:
+                    raise RuntimeError("live stream state overflow (unit q)")
+                carry.append((self.stage_off + w * rows0 * sld, self._state(st, k, st.half[k]) + col, rows0, nf, sld,
+                              self.cap[k]))
+                st.stored[k] += nf
+            self._carry(carry)
+
+    def _run_unit(self, k, items, outputs, out):
+        """Unit k for ``items`` = [(stream, (k, b0, end, e0, e1))], per launch: one carry gathers the rows' buffers
+        (and shifts their kept history into the other state half), the unit runs, one carry scatters the kept output
+        columns into unit k + 1's state (the last unit's into ``out``) before the next launch reuses the slab."""
+        u = self.units[k]
+        for L, chunk, B in self._batches(items, key=lambda it: it[1][2] - it[1][1]):
+            rows = chunk + [chunk[-1]] * (B - len(chunk))
+            R, ldi = self.rows[k], self.ld_in[k]
+            gather, shift = [], []
+            for r, (st, (_, b0, end, e0, e1)) in enumerate(rows):
+                src = self._state(st, k, st.half[k])
+                gather.append((src + (b0 - st.s0[k]), self.in_off[k] + r * R * ldi, R, L, self.cap[k], ldi))
+                if r < len(chunk):
+                    nb = _start(u, e1)
+                    keep = st.stored[k] - nb
+                    if keep > 0:
+                        shift.append((src + (nb - st.s0[k]), self._state(st, k, 1 - st.half[k]), R, keep, self.cap[k],
+                                      self.cap[k]))
+            self._carry(gather + shift)
+            for st, (_, b0, end, e0, e1) in chunk:
+                st.s0[k] = _start(u, e1)
+                st.half[k] ^= 1
+            self._launch(k, rows, B, L)
+            recs = self._scatter(k, chunk, L, outputs)
+            if k == len(self.units) - 1:
+                self._carry(recs, dst=out)
+            else:
+                self._carry(recs)
+
+    def _launch(self, k, rows, B, L):
+        u, eng, mem = self.units[k], self.engine, self.mem
+        ws = eng.live_workspace((u["name"], self.width[k]), B, self.width[k], stage=u["stage"])
+        R, ldi, ldo, C = self.rows[k], self.ld_in[k], self.ld_out[k], self.cout[k]
+        x = mem[self.in_off[k]:]
+        out = mem[self.out_off[k]:]
+        cat = lambda t: torch.cat([t_ for t_ in t])
+        if u["kind"] == "q":
+            cond = cat([st.conds["q"] for st, _ in rows])
+            eng.live_posterior(x, ldi, R * ldi, mem[self.in_off[k] + self.bins * ldi:], R * ldi, out, ldo, C * ldo, B,
+                               L, cond, self.tau, ws)
+        elif u["kind"] in ("f", "r"):
+            key = "src" if u["kind"] == "f" else "tgt"
+            conds = [torch.cat([st.conds[key][f] for st, _ in rows]) for f in range(len(rows[0][0].conds[key]))]
+            eng.live_flow(x, out, B, L, conds, u["kind"] == "r", ws)
+        else:
+            cond = cat([st.conds["d"] for st, _ in rows]) if u["stage"] == 0 else None
+            eng.live_generator_stage(u["stage"], x, ldi, R * ldi, out, B, L, ws, cond_d=cond)
+
+    def _scatter(self, k, chunk, L, outputs):
+        """Records moving unit k's kept output columns of a launch's rows into unit k + 1's state (or into the round's
+        output)."""
+        u = self.units[k]
+        s = u["stride"]
+        last = k == len(self.units) - 1
+        recs = []
+        C = self.cout[k]
+        ldo = L * s if u["kind"] == "g" else self.ld_out[k]
+        for r, (st, (_, b0, end, e0, e1)) in enumerate(chunk):
+            src = self.out_off[k] + r * C * ldo + (e0 - b0) * s
+            n = (e1 - e0) * s
+            if last:
+                o = outputs[st]
+                recs.append((src, o[0] + o[1], 1, n, ldo, n))
+                o[1] += n
+                continue
+            col = st.stored[k + 1] - st.s0[k + 1]
+            if col + n > self.cap[k + 1]:
+                raise RuntimeError(f"live stream state overflow (unit {self.units[k + 1]['name']})")
+            recs.append((src, self._state(st, k + 1, st.half[k + 1]) + col, C, n, ldo, self.cap[k + 1]))
+            st.stored[k + 1] += n
+        return recs
+
+    @torch.no_grad()
+    def _round(self, streams):
+        """One round: every stream in ``streams`` ([(h, st, new_frames)]) advances by one chunk (or its end)."""
+        jobs, plans = [], []
+        for h, st, nf in streams:
+            f0 = st.cas.n[0]
+            plans.append((h, st, st.cas.round(nf, final=st.closed and f0 + nf == st.T)))
+            jobs.append((st, nf, f0))
+        self._feed(jobs)
+        for st, nf, f0 in jobs:
+            if not st.closed:
+                st.trim()
+        total, outputs, acc = 0, {}, 0
+        K = len(self.units)
+        for h, st, pieces in plans:
+            n = sum((e1 - e0) * self.units[k]["stride"] for k, _, _, e0, e1 in pieces if k == K - 1)
+            outputs[st] = [acc, 0, h]
+            acc += n
+        out = torch.empty(acc, dtype=torch.float32, device=self.device)
+        for k in range(K):
+            items = [(st, p) for h, st, pieces in plans for p in pieces if p[0] == k]
+            if not items:
+                continue
+            self._run_unit(k, items, outputs, out)
+        return {o[2]: out[o[0]:o[0] + o[1]] for st, o in outputs.items() if o[1]}
+
+    @torch.no_grad()
+    def step(self):
+        """Rounds until no stream has a ready chunk; closed streams run to their end and are retired."""
+        res = {}
+        while True:
+            ready = [(h, st, st.ready()) for h, st in self._streams.items()]
+            ready = [r for r in ready if r[2] is not None]
+            if not ready:
+                break
+            for h, o in self._round(ready).items():
+                res.setdefault(h, []).append(o)
+            for h, st, _ in ready:
+                if st.closed and st.cas.done:
+                    self._retire(h)
+        return {h: (v[0] if len(v) == 1 else torch.cat(v)) for h, v in res.items()}
+
+
+class LiveStream:
+    """One live stream (a ``LivePool`` of one): ``push(samples)`` -> newly finished samples (device tensor, possibly
+    empty), ``close()`` -> the rest, ``latency_samples`` the bound no output sample's delay exceeds."""
+
+    def __init__(self, model, src_se, tgt_se, tau=0.3, chunk_frames=DEFAULT_CHUNK_FRAMES, noise=None, n_fft=1024,
+                 hop=256):
+        self._pool = LivePool(model, tau=tau, chunk_frames=chunk_frames, max_streams_per_launch=1, n_fft=n_fft, hop=hop)
+        self._h = self._pool.open(src_se, tgt_se, noise=noise)
+        self.latency_samples = self._pool.latency_samples
+        self._closed = False
+
+    def _out(self, res):
+        o = res.get(self._h)
+        return o if o is not None else torch.empty(0, dtype=torch.float32, device=self._pool.device)
+
+    def push(self, samples):
+        if self._closed:
+            raise RuntimeError("push() after close()")
+        self._pool.push(self._h, samples)
+        return self._out(self._pool.step())
+
+    def close(self):
+        if self._closed:
+            raise RuntimeError("close() called twice")
+        self._closed = True
+        self._pool.close(self._h)
+        return self._out(self._pool.step())

@@ -144,6 +144,17 @@ def frames_of(n_samples, n_fft, hop):
     return (int(n_samples) + 2 * pad - n_fft) // hop + 1
 
 
+def stream_end_frames(n_samples, n_fft, hop):
+    """Frames ``T`` of a stream that ended after ``n_samples`` samples; ValueError for input shorter than the reflect
+    padding or one frame, like ``spectrogram_torch``."""
+    if (int(n_fft) - int(hop)) // 2 >= n_samples:
+        raise ValueError("waveform shorter than the reflect padding")       # spectrogram_torch raises too
+    T = frames_of(n_samples, n_fft, hop)
+    if T < 1:
+        raise ValueError("waveform shorter than one frame")
+    return T
+
+
 class WindowedConverter:
     """Runs a window plan through ``SynthesizerTrn.voice_conversion`` in launches of up to ``windows_per_launch``
     windows.  ``graph=True`` replays each launch shape from a captured HIP graph (the window shape is fixed, so a file
@@ -378,11 +389,7 @@ class _StreamState:
         window, aligned to the end (``T`` frames when ``T <= Tw``).  Raises ValueError for input shorter than the reflect
         padding or one frame, like ``spectrogram_torch``."""
         c = self.conv
-        if c.pad >= self._n:
-            raise ValueError("waveform shorter than the reflect padding")       # spectrogram_torch raises too
-        T = frames_of(self._n, c.n_fft, c.hop)
-        if T < 1:
-            raise ValueError("waveform shorter than one frame")
+        T = stream_end_frames(self._n, c.n_fft, c.hop)
         plan, k, emitted = [], self._k, self._emitted
         if T > self._Tw:
             while k * self._core + self._Tw < T:
