@@ -303,6 +303,30 @@ int ov_carry_rows_f32(const int64_t* records, int n_records, const float* src_ba
 int ov_polyphase_fir_f32(const float* x, const double* h, float* y, int64_t n_in, int64_t n_out, int P, int Q, int taps,
                          ov_stream_t stream);
 
+/* The same polyphase FIR for many streams in ONE launch (openvoice_amd/rates.py: the per-stream resamplers of live and
+ * windowed streams, and the whole-recording rate conversion of convert_many).  records is a DEVICE int64 [n_records][11]
+ * with one record per stream and direction, each with its own rate pair:
+ *   [0] src_off   element of src_base that holds input sample src_base_index ([1])
+ *   [1] src_base_index, [2] src_end: global input indices [src_base_index, src_end) are valid in the arena
+ *   [3] n_total   the input's total length once it has ended, -1 while it is still arriving
+ *   [4] t0, [5] n_out: the record computes outputs t0 .. t0 + n_out - 1 (global output indices)
+ *   [6] dst_off   dst_base[dst_off + k] receives output t0 + k
+ *   [7] h_off     element of h_base where the record's [P][2 taps] float64 phase table starts (kaiser_best_phases)
+ *   [8] P, [9] Q, [10] taps   as in ov_polyphase_fir_f32
+ * Output t equals ov_polyphase_fir_f32's output t of the whole input x[0 .. n_total) bit for bit (one __device__
+ * function computes both: the same n = (t Q) / P, j order, float64 accumulation, indices < 0 or >= n_total skipped, one
+ * rounding); while n_total is -1 no index is skipped on the right, so a record must only ask for outputs whose taps
+ * have all arrived.  Outputs t >= n_total * P / Q (resampy's count) are written as 0: librosa's fix=True padding.
+ * Host checks: null pointers, n_records in [1, 65535], extents > 0, max_out > 0 (OV_E_BADARG); max_out is the largest
+ * n_out of the table (the grid's width: up to 256 blocks of 256 outputs per record, longer records stride).  The kernel
+ * checks every record: non-positive or oversized fields (P, Q, taps > 2^20; indices > 2^40; offsets > 2^61), a
+ * destination [dst_off, dst_off + n_out) that leaves [0, dst_elems) or a phase table that leaves [0, h_elems): the
+ * record writes nothing; a record whose needed input indices leave [src_base_index, src_end) or the arena writes zeros.
+ * Additive symbol of ABI 2.12 (no version change). */
+int ov_polyphase_fir_rows_f32(const int64_t* records, int n_records, const float* src_base, int64_t src_elems,
+                              const double* h_base, int64_t h_elems, float* dst_base, int64_t dst_elems, int64_t max_out,
+                              ov_stream_t stream);
+
 /* conv_post + tanh, reference openvoice/models.py:287-289:
  * out[b][0][t] = tanh( sum_{c,j} w[c][j] * lrelu(x[b][c][t+j-(K-1)/2], in_slope) ), no bias.
  * w is the dense [C][K] DEVICE weight. */
@@ -622,7 +646,7 @@ int ov_conv1d_wino_pack_f32(const float* w, int Cout, int Cin, int K, float* dst
  * was `reserved`; the struct grew by one pointer at its end).  2.06: ov_polyphase_fir_f32.  2.07: ov_conv1d_wino_f32 (+ _supported, _chunk,
  * _pack_size, _pack_f32).  2.08: ov_conv1d_wino_f32 instances for Cout % 32 == 0 at K = 11 (one 32-row fragment per
  * workgroup; ov_conv1d_wino_chunk(11, 32) = 2 where 2.07 returned 0).  2.09: ov_conv1d_wino_params.out_slope (the field that
- * was `reserved0`: same size and offset, 0 = none).  2.10: ov_frame_hops_windows_f32, ov_stitch_window_cores_f32.  2.11: ov_frame_hops_multi_f32.  2.12: ov_carry_rows_f32.  The Python binding
+ * was `reserved0`: same size and offset, 0 = none).  2.10: ov_frame_hops_windows_f32, ov_stitch_window_cores_f32.  2.11: ov_frame_hops_multi_f32.  2.12: ov_carry_rows_f32 (and, added later within 2.12 without a version change, ov_polyphase_fir_rows_f32).  The Python binding
  * refuses a library older than the entry points it calls (openvoice_amd/_lib.py MIN_VERSION). */
 int ov_version(void);
 /* The version THIS header describes.  Parameter structs grow at their END in minor versions (2.04, 2.05, 2.07 did): a

@@ -146,6 +146,7 @@ SIGNATURES = {
     "ov_sequence_mask_f32": (ctypes.c_int, [_fp, _fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp]),
     "ov_unpad_rows_f32": (ctypes.c_int, [_fp, _fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp]),
     "ov_polyphase_fir_f32": (ctypes.c_int, [_fp, _fp, _fp, ctypes.c_int64, ctypes.c_int64, _i, _i, _i, _fp]),
+    "ov_polyphase_fir_rows_f32": (ctypes.c_int, [_fp, _i, _fp, _i64, _fp, _i64, _fp, _i64, _i64, _fp]),
     "ov_layernorm_freq_f32": (ctypes.c_int, [_fp, _fp, _fp, _fp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                              ctypes.c_float, _fp]),
     "ov_conv2d_s2_relu_f32": (ctypes.c_int, [_fp, _fp, _fp, _fp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -211,7 +212,11 @@ def load():
             raise OvError(f"{LIB_PATH} is version {lib.ov_version()}, this package needs >= {MIN_VERSION}: rebuild it "
                           f"(make -C openvoice_amd/csrc)")
         for name, (restype, argtypes) in SIGNATURES.items():
-            fn = getattr(lib, name)
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:      # an additive symbol of this version missing: a library built from older source
+                raise OvError(f"{LIB_PATH} lacks {name}: it was built from older source, rebuild it "
+                              f"(make -C openvoice_amd/csrc)") from None
             fn.restype = restype
             fn.argtypes = argtypes
         exp = lib.ov_build_experiment()

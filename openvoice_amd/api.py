@@ -22,7 +22,7 @@ import re
 import numpy as np
 import torch
 
-from . import audio_io, longform, utils
+from . import audio_io, longform, rates, utils
 from .mel_processing import spectrogram_torch
 from .models import SynthesizerTrn
 
@@ -340,89 +340,133 @@ class ToneColorConverter(OpenVoiceBaseClass):
     def _windowed(self, window_frames, windows_per_launch=1):
         d = self.hps.data
         return longform.WindowedConverter(self.model, n_fft=d.filter_length, hop=d.hop_length, window_frames=window_frames,
-                                          windows_per_launch=windows_per_launch, graph=self.use_graphs)
+                                          windows_per_launch=windows_per_launch, graph=self.use_graphs,
+                                          model_sr=d.sampling_rate)
+
+    def _to_model_rate(self, audio_or_path, sr):
+        """(device waveform at the model rate, its rate before resampling or None): a path is decoded and resampled on
+        load as always; an array at ``sr`` Hz (None: the model rate) is resampled on the device."""
+        msr = self.hps.data.sampling_rate
+        if isinstance(audio_or_path, (str, os.PathLike)):
+            return audio_io.load_to_device(audio_or_path, msr, self.device)
+        y = torch.as_tensor(audio_or_path, dtype=torch.float32).reshape(-1).to(self.device)
+        return y if sr is None or int(sr) == int(msr) else audio_io.resample_on_device(y, sr, msr)
+
+    def _finish(self, o, message, out_sr):
+        """Converted device waveform at the model rate -> host audio at ``out_sr`` (None: the model rate).  The watermark
+        hook runs at the model rate, before the rate conversion."""
+        msr = self.hps.data.sampling_rate
+        resample = out_sr is not None and int(out_sr) != int(msr)
+        if self.watermark_model is None:
+            return (audio_io.resample_on_device(o, msr, out_sr) if resample else o).cpu().numpy()
+        audio = self.add_watermark(o.cpu().numpy(), message)
+        if resample:
+            audio = audio_io.resample_on_device(torch.from_numpy(audio).to(self.device), msr, out_sr).cpu().numpy()
+        return audio
 
     def convert_long(self, audio_or_path, src_se, tgt_se, output_path=None, tau=0.3, message="default",
                      window_frames=longform.DEFAULT_WINDOW_FRAMES, windows_per_launch=longform.DEFAULT_WINDOWS_PER_LAUNCH,
-                     noise=None):
+                     noise=None, sr=None, out_sr=None):
         """``convert`` for a recording of any length: overlapping windows of ``window_frames`` frames, up to
         ``windows_per_launch`` of them per launch (``longform.WindowedConverter``); device memory is bounded by the window,
-        not by the file.  ``audio_or_path``: a file path, or a 1-D float32 waveform at the model rate (host or device).
-        ``noise``: ``[1, 192, >= T]`` or None -- then ``torch.randn(1, 192, T)`` on the device, the draw of a seeded
-        one-pass ``convert``.  Same return value / file output as ``convert``."""
-        hps = self.hps
-        if isinstance(audio_or_path, (str, os.PathLike)):
-            y = audio_io.load_to_device(audio_or_path, hps.data.sampling_rate, self.device)
-        else:
-            y = torch.as_tensor(audio_or_path, dtype=torch.float32).reshape(-1).to(self.device)
+        not by the file.  ``audio_or_path``: a file path, or a 1-D float32 waveform (host or device) at ``sr`` Hz (None:
+        the model rate; otherwise resampled on the device first).  ``noise``: ``[1, 192, >= T]`` or None -- then
+        ``torch.randn(1, 192, T)`` on the device, the draw of a seeded one-pass ``convert``; T counts frames at the model
+        rate.  ``out_sr``: the rate of the returned / written audio (None: the model rate).  Otherwise the same return
+        value / file output as ``convert``."""
+        sr, out_sr = rates.check_rate(sr, "sr"), rates.check_rate(out_sr, "out_sr")
+        y = self._to_model_rate(audio_or_path, sr)
         o = self._windowed(window_frames, windows_per_launch).convert(y, src_se, tgt_se, tau=tau, noise=noise)
-        audio = o.cpu().numpy()
-        audio = self.add_watermark(audio, message)
+        audio = self._finish(o, message, out_sr)
         if output_path is None:
             return audio
-        audio_io.write(output_path, audio, hps.data.sampling_rate)
+        audio_io.write(output_path, audio, self.hps.data.sampling_rate if out_sr is None else out_sr)
 
-    def stream(self, src_se, tgt_se, tau=0.3, window_frames=longform.DEFAULT_STREAM_WINDOW_FRAMES, noise=None):
+    def stream(self, src_se, tgt_se, tau=0.3, window_frames=longform.DEFAULT_STREAM_WINDOW_FRAMES, noise=None, sr_in=None,
+               sr_out=None):
         """A ``longform.ConversionStream``: ``push(samples)`` -> newly finished converted samples (device tensor, maybe
-        empty), ``close()`` -> the rest, ``latency_samples`` = ``(window_frames - 1) * hop + n_fft - (n_fft - hop) / 2``.
-        Input at ``hps.data.sampling_rate`` (no resampling inside the stream); ``noise`` ``[1, 192, >= T]`` makes it
-        reproducible.  The output equals ``convert_long(..., windows_per_launch=1)`` of the whole input, bit for bit."""
-        return self._windowed(window_frames, 1).stream(src_se, tgt_se, tau=tau, noise=noise)
+        empty), ``close()`` -> the rest, ``latency_samples`` = ``(window_frames - 1) * hop + n_fft - (n_fft - hop) / 2``
+        at the model rate.  ``sr_in`` / ``sr_out``: the rate of the pushes / of the output (None: the model rate); the
+        stream resamples inside, carrying the filter state across pushes, and ``latency_samples`` (output samples) /
+        ``latency_seconds`` then include the resamplers' waits.  ``noise`` ``[1, 192, >= T]`` makes it reproducible.  The
+        output equals ``convert_long(..., windows_per_launch=1)`` of the whole input, bit for bit -- with rates, of the
+        input resampled to the model rate, and resampled to ``sr_out`` after (``audio_io.resample_on_device``)."""
+        return self._windowed(window_frames, 1).stream(src_se, tgt_se, tau=tau, noise=noise, sr_in=sr_in, sr_out=sr_out)
 
     # ---- many streams and recordings in shared launches -------------------------------------------------------------
     def stream_pool(self, tau=0.3, window_frames=longform.DEFAULT_STREAM_WINDOW_FRAMES,
                     max_windows_per_launch=longform.DEFAULT_POOL_WINDOWS_PER_LAUNCH):
-        """A ``longform.StreamPool``: many live streams (``open(src_se, tgt_se, noise=None)`` -> handle, ``push(h,
-        samples)``, ``close(h)``), whose ready windows one ``step()`` converts together, up to
-        ``max_windows_per_launch`` per launch -> ``{handle: newly finished samples}``.  Each stream's output equals a
-        ``stream(...)`` fed the same samples with the same noise.  One ``tau`` for the whole pool."""
+        """A ``longform.StreamPool``: many live streams (``open(src_se, tgt_se, noise=None, sr_in=None, sr_out=None)`` ->
+        handle, ``push(h, samples)``, ``close(h)``), whose ready windows one ``step()`` converts together, up to
+        ``max_windows_per_launch`` per launch -> ``{handle: newly finished samples}``; streams at rates of their own are
+        resampled in one launch per direction and step.  Each stream's output equals a ``stream(...)`` fed the same
+        samples with the same noise and rates.  One ``tau`` for the whole pool."""
         return self._windowed(window_frames, 1).stream_pool(tau=tau, max_windows_per_launch=max_windows_per_launch)
 
     # ---- low-latency live streams ------------------------------------------------------------------------------------
-    def live_stream(self, src_se, tgt_se, tau=0.3, chunk_frames=15, noise=None):
+    def live_stream(self, src_se, tgt_se, tau=0.3, chunk_frames=15, noise=None, sr_in=None, sr_out=None):
         """A ``live.LiveStream``: the conversion as a cascade of units that carry their recent input as state.
         ``push(samples)`` -> newly finished samples, ``close()`` -> the rest, ``latency_samples`` =
         ``live.live_latency_samples`` (1.45 s at 15 frames).  ``chunk_frames``: a positive multiple of 15 (the Winograd
         grid).  The fp32 generator only (ValueError with use_bf16_generator / enable_split_bf16x3); never graph-captured.
-        With ``noise`` ``[1, 192, >= T]`` the output equals ``convert_long`` of the whole input."""
+        ``sr_in`` / ``sr_out``: the rate of the pushes / of the output (None: the model rate); ``latency_samples`` (in
+        output samples) and ``latency_seconds`` then include the resamplers' waits (``rates.stream_latency``).  With
+        ``noise`` ``[1, 192, >= T]`` the output equals ``convert_long`` of the whole input (resampled to the model rate
+        before and to ``sr_out`` after by ``audio_io.resample_on_device``)."""
         from . import live
         d = self.hps.data
         return live.LiveStream(self.model, src_se, tgt_se, tau=tau, chunk_frames=chunk_frames, noise=noise,
-                               n_fft=d.filter_length, hop=d.hop_length)
+                               n_fft=d.filter_length, hop=d.hop_length, sr_in=sr_in, sr_out=sr_out,
+                               model_sr=d.sampling_rate)
 
     def live_pool(self, tau=0.3, chunk_frames=15, max_streams_per_launch=32):
-        """A ``live.LivePool``: many live streams (``open`` / ``push`` / ``close``), every stream with a ready chunk
-        converted by one ``step()`` in launches of up to ``max_streams_per_launch`` rows per unit.  Each stream equals
-        its solo ``live_stream``.  One ``tau`` for the pool."""
+        """A ``live.LivePool``: many live streams (``open(src_se, tgt_se, noise=None, sr_in=None, sr_out=None)`` /
+        ``push`` / ``close``), every stream with a ready chunk converted by one ``step()`` in launches of up to
+        ``max_streams_per_launch`` rows per unit; streams at rates of their own are resampled in one launch per direction
+        and step.  Each stream equals its solo ``live_stream``.  One ``tau`` for the pool."""
         from . import live
         d = self.hps.data
         return live.LivePool(self.model, tau=tau, chunk_frames=chunk_frames, max_streams_per_launch=max_streams_per_launch,
-                             n_fft=d.filter_length, hop=d.hop_length)
+                             n_fft=d.filter_length, hop=d.hop_length, model_sr=d.sampling_rate)
 
     def convert_many(self, items, src_se, tgt_se, tau=0.3, window_frames=longform.DEFAULT_WINDOW_FRAMES,
                      windows_per_launch=longform.DEFAULT_MANY_WINDOWS_PER_LAUNCH, noise=None, output_paths=None,
-                     message="default"):
+                     message="default", sr=None, out_sr=None):
         """``convert_long`` of many recordings with their windows packed ACROSS recordings into launches of up to
         ``windows_per_launch`` (``longform.WindowedConverter.convert_many``).  ``items``: file paths (any rate, decoded
-        and resampled like ``convert_long``) or 1-D waveforms at the model rate.  ``src_se`` / ``tgt_se``: one
-        ``[1, 256, 1]`` for every item, or a list with one per item.  ``noise``: None or a list of ``[1, 192, >= T_i]``.
-        Returns a list of numpy arrays (watermark hook applied per item), or writes ``output_paths[i]`` instead.  Each
-        item equals ``convert_long`` of it with the same ``window_frames`` and noise."""
+        and resampled like ``convert_long``) or 1-D waveforms at ``sr`` Hz (None: the model rate; one rate, or a list
+        with one per item).  ``out_sr``: the rate of the results (None: the model rate; one, or one per item).  The
+        array items are resampled to the model rate in ONE launch, and the results to ``out_sr`` in one more
+        (``rates.resample_many``).  ``src_se`` / ``tgt_se``: one ``[1, 256, 1]`` for every item, or a list with one per
+        item.  ``noise``: None or a list of ``[1, 192, >= T_i]``.  Returns a list of numpy arrays (watermark hook applied
+        per item, at the model rate), or writes ``output_paths[i]`` (at its ``out_sr``) instead.  Each item equals
+        ``convert_long`` of it with the same ``window_frames``, noise and rates."""
         hps = self.hps
+        msr = hps.data.sampling_rate
         items = list(items)
         n = len(items)
         per_item = lambda se: list(se) if isinstance(se, (list, tuple)) else [se] * n
         srcs, tgts = per_item(src_se), per_item(tgt_se)
+        srs = [rates.check_rate(r, "sr") for r in per_item(sr)]
+        out_srs = [rates.check_rate(r, "out_sr") for r in per_item(out_sr)]
         if output_paths is not None and len(output_paths) != n:
             raise ValueError("convert_many: one output path per item")
-        waves = [audio_io.load_to_device(x, hps.data.sampling_rate, self.device) if isinstance(x, (str, os.PathLike))
+        if len(srs) != n or len(out_srs) != n:
+            raise ValueError("convert_many: one sr / out_sr per item")
+        waves = [audio_io.load_to_device(x, msr, self.device) if isinstance(x, (str, os.PathLike))
                  else torch.as_tensor(x, dtype=torch.float32).reshape(-1).to(self.device) for x in items]
+        paths = [isinstance(x, (str, os.PathLike)) for x in items]
+        waves = rates.resample_many(waves, [(None, None) if p else (r, msr) for p, r in zip(paths, srs)], self.device)
         outs = self._windowed(window_frames, windows_per_launch).convert_many(waves, srcs, tgts, tau=tau, noises=noise)
-        audios = [self.add_watermark(o.cpu().numpy(), message) for o in outs]
+        if self.watermark_model is None:
+            outs = rates.resample_many(outs, [(msr, r) for r in out_srs], self.device)
+            audios = [o.cpu().numpy() for o in outs]
+        else:
+            audios = [self._finish(o, message, r) for o, r in zip(outs, out_srs)]
         if output_paths is None:
             return audios
-        for path, audio in zip(output_paths, audios):
-            audio_io.write(path, audio, hps.data.sampling_rate)
+        for path, audio, r in zip(output_paths, audios, out_srs):
+            audio_io.write(path, audio, msr if r is None else r)
 
     # ---- optional watermark hook (third-party model; behaviour of the reference's openvoice/api.py:162-201) ----------
     # The message travels as 32-bit groups, group n in the 16 000-sample window that starts at sample 32 000 n (every other

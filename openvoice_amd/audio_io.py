@@ -152,6 +152,17 @@ def resample_kaiser_best(x, sr_in, sr_out):
 _device_phases = {}
 
 
+def device_phases(sr_in, sr_out, device):
+    """``(h, P, Q, taps)`` of ``kaiser_best_phases`` with h a float64 tensor on ``device``, computed once per (rate pair,
+    device) and kept resident (``resample_on_device`` and the stream resamplers of ``rates`` share it)."""
+    import torch
+    key = (int(sr_in), int(sr_out), str(torch.device(device)))
+    if key not in _device_phases:
+        h, P, Q, taps = kaiser_best_phases(sr_in, sr_out)
+        _device_phases[key] = (torch.from_numpy(h).to(device), P, Q, taps)
+    return _device_phases[key]
+
+
 def resample_on_device(x, sr_in, sr_out):
     """The same resampler on the GPU (``ov_polyphase_fir_f32``): ``x`` a float32 DEVICE tensor [N] -> float32 device tensor
     [ceil(N * sr_out / sr_in)]; the phase weights are computed once per (rate pair, device) on the host and kept
@@ -160,11 +171,7 @@ def resample_on_device(x, sr_in, sr_out):
     from . import _lib
     if int(sr_in) == int(sr_out) or x.numel() == 0:
         return x
-    key = (int(sr_in), int(sr_out), str(x.device))
-    if key not in _device_phases:
-        h, P, Q, taps = kaiser_best_phases(sr_in, sr_out)
-        _device_phases[key] = (torch.from_numpy(h).to(x.device), P, Q, taps)
-    h, P, Q, taps = _device_phases[key]
+    h, P, Q, taps = device_phases(sr_in, sr_out, x.device)
     x = x.to(torch.float32).contiguous()
     n_in = int(x.numel())
     n_res, n_out = n_in * P // Q, -(-n_in * P // Q)           # resampy's sample count, librosa's fixed length

@@ -153,25 +153,70 @@ __global__ __launch_bounds__(256) void frame_hops_kernel(const float* __restrict
     if (u0 + lane < U) hops[((int64_t)b * hop + c) * ld + u0 + lane] = tile[lane * HS + c];
 }
 
-// Polyphase FIR over a mono waveform (the resampler of the audio boundary, see ov_polyphase_fir_f32): output t reads
-// 2 * taps input samples starting at (t * Q) / P - taps + 1 with the weights of phase t % P.  One thread per output
-// sample, float64 accumulation (the host restatement this is checked against computes in float64); the 2 * taps
-// weights of a phase and the overlapping input windows of neighbouring threads come out of L1 / L2 -- 57 MFLOP for a
-// 10 s file, not worth a tile.
+// One output of the polyphase FIR (the resampler of the audio boundary, see ov_polyphase_fir_f32), shared by the
+// whole-waveform kernel and the record-driven one so the two cannot drift apart: output t reads 2 * taps input samples
+// starting at (t * Q) / P - taps + 1 with the weights of phase t % P, skips input indices outside [0, n_in), accumulates
+// in float64 in j order and rounds once to float32.  load(i) returns input sample i (only called for 0 <= i < n_in).
+template <typename Load>
+__device__ __forceinline__ float polyphase_output(int64_t t, const double* __restrict__ h, int64_t n_in, int64_t P,
+                                                  int64_t Q, int taps, Load load) {
+  const int64_t n = (t * Q) / P;                  // input sample at or before the output's position
+  const double* __restrict__ w = h + (t % P) * (2 * taps);
+  const int64_t first = n - taps + 1;
+  double acc = 0.0;
+  for (int j = 0; j < 2 * taps; ++j) {
+    const int64_t i = first + j;
+    if (i >= 0 && i < n_in) acc += w[j] * (double)load(i);
+  }
+  return (float)acc;
+}
+
+// Polyphase FIR over a mono waveform: one thread per output sample, float64 accumulation (the host restatement this is
+// checked against computes in float64); the 2 * taps weights of a phase and the overlapping input windows of
+// neighbouring threads come out of L1 / L2 -- 57 MFLOP for a 10 s file, not worth a tile.
 __global__ __launch_bounds__(256) void polyphase_fir_kernel(const float* __restrict__ x, const double* __restrict__ h,
                                                             float* __restrict__ y, int64_t n_in, int64_t n_out, int P,
                                                             int Q, int taps) {
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (t >= n_out) return;
-  const int64_t n = (t * Q) / P;                  // input sample at or before the output's position
-  const double* __restrict__ w = h + (int64_t)(t % P) * (2 * taps);
-  const int64_t first = n - taps + 1;
-  double acc = 0.0;
-  for (int j = 0; j < 2 * taps; ++j) {
-    const int64_t i = first + j;
-    if (i >= 0 && i < n_in) acc += w[j] * (double)x[i];
+  y[t] = polyphase_output(t, h, n_in, P, Q, taps, [=](int64_t i) { return x[i]; });
+}
+
+// Record-driven polyphase FIR (ov_polyphase_fir_rows_f32): blockIdx.y = record, the record's outputs strided over
+// gridDim.x blocks of 256 threads.  Record (int64, see the header): src_off, src_base, src_end, n_total, t0, n_out,
+// dst_off, h_off, P, Q, taps.  Every record is checked against the three extents before anything is read or written.
+__global__ __launch_bounds__(256) void polyphase_fir_rows_kernel(const int64_t* __restrict__ records,
+                                                                 const float* __restrict__ src, int64_t src_elems,
+                                                                 const double* __restrict__ h, int64_t h_elems,
+                                                                 float* __restrict__ dst, int64_t dst_elems) {
+  const int64_t* rec = records + 11 * (int64_t)blockIdx.y;
+  const int64_t so = rec[0], base = rec[1], end = rec[2], total = rec[3], t0 = rec[4], n_out = rec[5], d_o = rec[6],
+                h_off = rec[7], P = rec[8], Q = rec[9], taps = rec[10];
+  const int64_t kRate = int64_t(1) << 20, kIdx = int64_t(1) << 40, kOff = int64_t(1) << 61;   // t * Q stays < 2^61
+  if (P <= 0 || Q <= 0 || taps <= 0 || P > kRate || Q > kRate || taps > kRate || t0 < 0 || n_out <= 0 ||
+      t0 > kIdx || n_out > kIdx || so < 0 || base < 0 || end < base || end > kIdx || total < -1 || total > kIdx ||
+      d_o < 0 || h_off < 0 || so > kOff || d_o > kOff || h_off > kOff)
+    return;
+  if (d_o + n_out > dst_elems || h_off + P * 2 * taps > h_elems) return;     // writes (or weights) out of range: nothing
+  const int64_t n_in = total < 0 ? kIdx + 2 * kRate : total;                // an unfinished input: no right end yet
+  const int64_t n_res = total < 0 ? kIdx + 2 * kRate : (total * P) / Q;     // outputs past resampy's count are padding
+  // the input indices the record's outputs read (those below n_res): [lo, hi) must lie in the valid window and the arena
+  const int64_t t_last = (t0 + n_out < n_res ? t0 + n_out : n_res) - 1;
+  bool reads_ok = true;
+  if (t_last >= t0) {
+    int64_t lo = (t0 * Q) / P - taps + 1, hi = (t_last * Q) / P + taps + 1;
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > n_in ? n_in : hi;
+    reads_ok = lo >= hi || (lo >= base && hi <= end && so + (hi - base) <= src_elems);
   }
-  y[t] = (float)acc;
+  const double* __restrict__ hw = h + h_off;
+  const float* __restrict__ x = src + so;
+  for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < n_out; k += (int64_t)gridDim.x * 256) {
+    const int64_t t = t0 + k;
+    float v = 0.f;
+    if (reads_ok && t < n_res) v = polyphase_output(t, hw, n_in, P, Q, (int)taps, [=](int64_t i) { return x[i - base]; });
+    dst[d_o + k] = v;
+  }
 }
 
 static conv_launch_fn find_variant(int K, int dil, int tile, int chunk, int vec, int epi, int nld) {
@@ -342,6 +387,20 @@ int ov_polyphase_fir_f32(const float* x, const double* h, float* y, int64_t n_in
   if ((n_out + 255) / 256 > INT32_MAX) return OV_E_BADARG;
   hipLaunchKernelGGL(polyphase_fir_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), x, h, y, n_in, n_out, P, Q, taps);
+  return hipGetLastError() == hipSuccess ? OV_OK : OV_E_LAUNCH;
+}
+
+int ov_polyphase_fir_rows_f32(const int64_t* records, int n_records, const float* src_base, int64_t src_elems,
+                              const double* h_base, int64_t h_elems, float* dst_base, int64_t dst_elems, int64_t max_out,
+                              ov_stream_t stream) {
+  if (!records || !src_base || !h_base || !dst_base || n_records <= 0 || n_records > 65535 || src_elems <= 0 ||
+      h_elems <= 0 || dst_elems <= 0 || max_out <= 0)
+    return OV_E_BADARG;
+  // one block per 256 outputs of the longest record, at most 256 per record (longer records stride)
+  const int64_t bx = (max_out + 255) / 256;
+  dim3 grid((unsigned)(bx < 256 ? bx : 256), n_records);
+  hipLaunchKernelGGL(polyphase_fir_rows_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), records, src_base,
+                     src_elems, h_base, h_elems, dst_base, dst_elems);
   return hipGetLastError() == hipSuccess ? OV_OK : OV_E_LAUNCH;
 }
 

@@ -26,12 +26,16 @@ Device side, a ``LivePool`` keeps each stream's unit states in one arena slot pe
 history shift never overlaps itself).  For every unit and launch, ``ov_carry_rows_f32`` gathers the ready streams'
 buffers into batch rows (and shifts their kept history into the other half) in one launch, the unit runs on the batch,
 and a second carry scatters the new columns into the next unit's state.  ``LiveStream`` is a pool of one.
+
+A stream opened with ``sr_in`` / ``sr_out`` (``rates``) takes its pushes at ``sr_in`` and returns samples at ``sr_out``: a
+step first resamples the new input of every such stream to the model rate in one launch, runs the rounds, then
+resamples every stream's new output in one more launch.
 """
 import math
 
 import torch
 
-from . import _lib
+from . import _lib, rates
 from .longform import launch_ladder, stream_end_frames, winograd_grid_frames
 from .params import ENC_Q_KERNEL, ENC_Q_LAYERS, FLOW_KERNEL, FLOW_LAYERS, N_FLOWS
 
@@ -254,7 +258,7 @@ class LivePool:
     Live units run eagerly, never from a captured graph."""
 
     def __init__(self, model, tau=0.3, chunk_frames=DEFAULT_CHUNK_FRAMES,
-                 max_streams_per_launch=DEFAULT_LIVE_STREAMS_PER_LAUNCH, n_fft=1024, hop=256):
+                 max_streams_per_launch=DEFAULT_LIVE_STREAMS_PER_LAUNCH, n_fft=1024, hop=256, model_sr=rates.MODEL_RATE):
         self.model, self.tau = model, float(tau)
         self.cfg = model.model_cfg
         self.chunk = check_chunk(self.cfg, chunk_frames)
@@ -275,6 +279,10 @@ class LivePool:
         self._streams, self._retired, self._next = {}, set(), 0
         self._free_slots, self._slots = [], 0
         self.mem = None
+        self.model_sr = int(model_sr)
+        self._rin, self._rout = rates.ResamplerBank(self.device), rates.ResamplerBank(self.device)
+        self._rin_owner = {}        # input resampler key -> stream
+        self._rout_ending = []      # output resampler keys of streams that finished in this step
 
     # ---- memory layout --------------------------------------------------------------------------------------------
     def _layout(self):
@@ -346,7 +354,10 @@ class LivePool:
     def active(self):
         return list(self._streams)
 
-    def open(self, src_se, tgt_se, noise=None):
+    def open(self, src_se, tgt_se, noise=None, sr_in=None, sr_out=None):
+        """A new stream -> its handle.  ``sr_in`` / ``sr_out``: the rate of its pushes / of its output (None or the
+        model rate: no resampler in that direction)."""
+        sr_in, sr_out = rates.check_rate(sr_in, "sr_in"), rates.check_rate(sr_out, "sr_out")
         if not self._free_slots:                 # the arena doubles: streams already open keep their slots
             grown = max(1, 2 * self._slots)
             self._free_slots = list(range(grown - 1, self._slots - 1, -1)) + self._free_slots
@@ -355,8 +366,22 @@ class LivePool:
         slot = self._free_slots.pop()
         h = self._next
         self._next += 1
-        self._streams[h] = _Live(self, slot, src_se, tgt_se, noise)
+        st = _Live(self, slot, src_se, tgt_se, noise)
+        st.sr_in, st.sr_out = sr_in, sr_out
+        st.rin = st.rout = None
+        if sr_in is not None and sr_in != self.model_sr:
+            st.rin = self._rin.open(sr_in, self.model_sr)
+            self._rin_owner[st.rin] = st
+        if sr_out is not None and sr_out != self.model_sr:
+            st.rout = self._rout.open(self.model_sr, sr_out)
+        self._streams[h] = st
         return h
+
+    def latency_of(self, h):
+        """``(seconds, samples)``: the latency bound of stream h at its own rates (``rates.stream_latency``; samples in
+        its output rate, ``latency_samples`` when it resamples nothing)."""
+        st = self._stream(h)
+        return rates.stream_latency(self.latency_samples, self.model_sr, st.sr_in, st.sr_out)
 
     def _stream(self, h):
         st = self._streams.get(h)
@@ -369,7 +394,10 @@ class LivePool:
         st = self._stream(h)
         if st.closed:
             raise RuntimeError(f"push() after close() on stream {h!r}")
-        st.append(torch.as_tensor(samples, dtype=torch.float32).reshape(-1).to(self.device))
+        if st.rin is not None:                  # resampled to the model rate by the next step()
+            self._rin.push(st.rin, rates.owned_samples(samples, self.device))
+        else:
+            st.append(torch.as_tensor(samples, dtype=torch.float32).reshape(-1).to(self.device))
 
     def close(self, h):
         """End of h's input; too short an input raises ValueError here and retires h (the others are untouched)."""
@@ -377,19 +405,32 @@ class LivePool:
         if st.closed:
             raise RuntimeError(f"close() called twice on stream {h!r}")
         st.closed = True
+        n = st.n
+        if st.rin is not None:                  # the model-rate samples the input resampler has still to deliver
+            n += self._rin.final_count(st.rin) - self._rin.emitted(st.rin)
+            self._rin.end(st.rin)
         try:
-            st.T = stream_end_frames(st.n, self.n_fft, self.hop)
+            st.T = stream_end_frames(n, self.n_fft, self.hop)
             if st.noise is not None and st.noise.shape[2] < st.T:
                 raise ValueError(f"noise has {st.noise.shape[2]} frames, the stream needs {st.T}")
         except ValueError:
             self._retire(h)
             raise
 
-    def _retire(self, h):
+    def _retire(self, h, finished=False):
+        """``finished``: h ran to its end, so its output resampler (if any) still delivers its tail in this step."""
         st = self._streams.pop(h)
         st.buf, st.len = st.buf[:0], 0
         self._free_slots.append(st.slot)
         self._retired.add(h)
+        if st.rin is not None:
+            self._rin.drop(st.rin)
+            self._rin_owner.pop(st.rin, None)
+        if st.rout is not None:
+            if finished:
+                self._rout_ending.append(st.rout)     # ended after this step's last output is queued
+            else:
+                self._rout.drop(st.rout)
 
     # ---- stepping -------------------------------------------------------------------------------------------------
     def _carry(self, recs, dst=None):
@@ -544,8 +585,15 @@ class LivePool:
 
     @torch.no_grad()
     def step(self):
-        """Rounds until no stream has a ready chunk; closed streams run to their end and are retired."""
-        res = {}
+        """Rounds until no stream has a ready chunk; closed streams run to their end and are retired.  Streams with an
+        input rate of their own first receive their new input at the model rate (one resampler launch for all of
+        them); streams with an output rate of their own get theirs resampled after the rounds (one more launch)."""
+        for key, y in self._rin.step().items():
+            self._rin_owner[key].append(y)
+        res, routs = {}, {}
+        for h, st in self._streams.items():
+            if st.rout is not None:
+                routs[h] = st.rout
         while True:
             ready = [(h, st, st.ready()) for h, st in self._streams.items()]
             ready = [r for r in ready if r[2] is not None]
@@ -555,19 +603,32 @@ class LivePool:
                 res.setdefault(h, []).append(o)
             for h, st, _ in ready:
                 if st.closed and st.cas.done:
-                    self._retire(h)
-        return {h: (v[0] if len(v) == 1 else torch.cat(v)) for h, v in res.items()}
+                    self._retire(h, finished=True)
+        out = {h: (v[0] if len(v) == 1 else torch.cat(v)) for h, v in res.items()}
+        if routs:
+            for h, key in routs.items():
+                if h in out:
+                    self._rout.push(key, out.pop(h))
+            for key in self._rout_ending:
+                self._rout.end(key)
+            self._rout_ending.clear()
+            ys = self._rout.step()
+            out.update({h: ys[key] for h, key in routs.items() if key in ys})
+        return out
 
 
 class LiveStream:
     """One live stream (a ``LivePool`` of one): ``push(samples)`` -> newly finished samples (device tensor, possibly
-    empty), ``close()`` -> the rest, ``latency_samples`` the bound no output sample's delay exceeds."""
+    empty), ``close()`` -> the rest, ``latency_samples`` the bound no output sample's delay exceeds (in output samples;
+    ``latency_seconds`` the same bound in seconds).  ``sr_in`` / ``sr_out``: rates of the pushes / of the output (None:
+    the model rate)."""
 
     def __init__(self, model, src_se, tgt_se, tau=0.3, chunk_frames=DEFAULT_CHUNK_FRAMES, noise=None, n_fft=1024,
-                 hop=256):
-        self._pool = LivePool(model, tau=tau, chunk_frames=chunk_frames, max_streams_per_launch=1, n_fft=n_fft, hop=hop)
-        self._h = self._pool.open(src_se, tgt_se, noise=noise)
-        self.latency_samples = self._pool.latency_samples
+                 hop=256, sr_in=None, sr_out=None, model_sr=rates.MODEL_RATE):
+        self._pool = LivePool(model, tau=tau, chunk_frames=chunk_frames, max_streams_per_launch=1, n_fft=n_fft, hop=hop,
+                              model_sr=model_sr)
+        self._h = self._pool.open(src_se, tgt_se, noise=noise, sr_in=sr_in, sr_out=sr_out)
+        self.latency_seconds, self.latency_samples = self._pool.latency_of(self._h)
         self._closed = False
 
     def _out(self, res):

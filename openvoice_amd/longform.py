@@ -23,7 +23,7 @@ import math
 
 import torch
 
-from . import _lib
+from . import _lib, rates
 from .engine import GENERATOR_MARGIN, generator_margin_frames
 from .params import ENC_Q_KERNEL, ENC_Q_LAYERS, FLOW_KERNEL, FLOW_LAYERS, N_FLOWS
 
@@ -161,8 +161,9 @@ class WindowedConverter:
     captures at most three shapes: full batches, the last partial batch, and the single-window case)."""
 
     def __init__(self, model, n_fft=1024, hop=256, window_frames=DEFAULT_WINDOW_FRAMES,
-                 windows_per_launch=DEFAULT_WINDOWS_PER_LAUNCH, graph=False):
+                 windows_per_launch=DEFAULT_WINDOWS_PER_LAUNCH, graph=False, model_sr=rates.MODEL_RATE):
         self.model = model
+        self.model_sr = int(model_sr)
         self.cfg = model.model_cfg
         self.n_fft, self.hop, self.pad = int(n_fft), int(hop), (int(n_fft) - int(hop)) // 2
         self.window_frames = int(window_frames)
@@ -304,8 +305,8 @@ class WindowedConverter:
             self._launch(wave, N, plan_dev[i0:i1], firsts_dev[i0:i1], Tw, src_se, tgt_se, tau, nz, out, 0)
         return out
 
-    def stream(self, src_se, tgt_se, tau=0.3, noise=None):
-        return ConversionStream(self, src_se, tgt_se, tau=tau, noise=noise)
+    def stream(self, src_se, tgt_se, tau=0.3, noise=None, sr_in=None, sr_out=None):
+        return ConversionStream(self, src_se, tgt_se, tau=tau, noise=noise, sr_in=sr_in, sr_out=sr_out)
 
     def stream_pool(self, tau=0.3, max_windows_per_launch=DEFAULT_POOL_WINDOWS_PER_LAUNCH):
         return StreamPool(self, tau=tau, max_windows_per_launch=max_windows_per_launch)
@@ -314,14 +315,19 @@ class WindowedConverter:
 class _StreamState:
     """Bookkeeping of one stream on the window grid, shared by ``ConversionStream`` (one window per launch) and
     ``StreamPool`` (many streams per launch): the buffered tail of the input, the next regular window, the readiness
-    rule, the end-of-input plan and the noise."""
+    rule, the end-of-input plan, the noise, and the rates of the input / output (``sr_in`` / ``sr_out``, None: the
+    model rate)."""
 
-    def __init__(self, conv, src_se, tgt_se, noise=None):
+    def __init__(self, conv, src_se, tgt_se, noise=None, sr_in=None, sr_out=None):
         self.conv, self.src_se, self.tgt_se = conv, src_se, tgt_se
         self.dev = conv._device()
         c = conv
         self._Tw, self._core, self._ctx = c.window_frames, c.core, c.context
-        self._latency = (self._Tw - 1) * c.hop + c.n_fft - c.pad
+        self.sr_in, self.sr_out = rates.check_rate(sr_in, "sr_in"), rates.check_rate(sr_out, "sr_out")
+        # (Tw - 1) * hop + n_fft - pad at the model rate; the resamplers' waits on top (rates.stream_latency)
+        self.latency_seconds, self._latency = rates.stream_latency((self._Tw - 1) * c.hop + c.n_fft - c.pad, c.model_sr,
+                                                                   self.sr_in, self.sr_out)
+        self.rin = self.rout = None
         self._buf = torch.empty(0, dtype=torch.float32, device=self.dev)
         self._len = 0               # valid samples in _buf
         self._base = 0              # file index of _buf[0]; a multiple of hop
@@ -383,13 +389,14 @@ class _StreamState:
         self._len += n
         self._n += n
 
-    def _tail_plan(self):
+    def _tail_plan(self, n=None):
         """At the end of the input: ``[(record, Tw)]`` of the windows still to run -- the regular windows of the plan not
         yet run (those whose last frames reach into the end's reflect padding are only now defined) and the last
         window, aligned to the end (``T`` frames when ``T <= Tw``).  Raises ValueError for input shorter than the reflect
-        padding or one frame, like ``spectrogram_torch``."""
+        padding or one frame, like ``spectrogram_torch``.  ``n``: the input's total length, when samples are still to
+        be appended (an input resampler's tail); the samples received otherwise."""
         c = self.conv
-        T = stream_end_frames(self._n, c.n_fft, c.hop)
+        T = stream_end_frames(self._n if n is None else n, c.n_fft, c.hop)
         plan, k, emitted = [], self._k, self._emitted
         if T > self._Tw:
             while k * self._core + self._Tw < T:
@@ -414,11 +421,19 @@ class ConversionStream(_StreamState):
 
     ``latency_samples``: input samples that arrive before the first output sample leaves, and the upper bound of any
     sample's delay: ``(Tw - 1) * hop + n_fft - pad``.  Device memory stays bounded: the waveform and noise buffers are
-    trimmed as windows finish."""
+    trimmed as windows finish.
 
-    def __init__(self, conv, src_se, tgt_se, tau=0.3, noise=None):
-        super().__init__(conv, src_se, tgt_se, noise)
+    ``sr_in`` / ``sr_out``: the rate of the pushes / of the output (None: the model rate).  Pushes then pass through a
+    ``rates.StreamResampler`` to the model rate and the output through another one, one launch each per push;
+    ``latency_samples`` (in output samples) and ``latency_seconds`` include their waits (``rates.stream_latency``)."""
+
+    def __init__(self, conv, src_se, tgt_se, tau=0.3, noise=None, sr_in=None, sr_out=None):
+        super().__init__(conv, src_se, tgt_se, noise, sr_in=sr_in, sr_out=sr_out)
         self.tau = tau
+        if self.sr_in is not None and self.sr_in != conv.model_sr:
+            self.rin = rates.StreamResampler(self.sr_in, conv.model_sr, self.dev)
+        if self.sr_out is not None and self.sr_out != conv.model_sr:
+            self.rout = rates.StreamResampler(conv.model_sr, self.sr_out, self.dev)
 
     def _run(self, rec, Tw):
         """One window of the stream: its core samples as a fresh device tensor.  The buffer starts ``_base`` samples
@@ -440,7 +455,8 @@ class ConversionStream(_StreamState):
     def push(self, samples):
         if self._closed:
             raise RuntimeError("push() after close()")
-        self._append(torch.as_tensor(samples, dtype=torch.float32).reshape(-1).to(self.dev))
+        x = torch.as_tensor(samples, dtype=torch.float32).reshape(-1).to(self.dev)
+        self._append(x if self.rin is None else self.rin.push(x))
         outs = []
         while self._n >= self._need(self._k):
             rec = self._regular(self._k)
@@ -448,17 +464,22 @@ class ConversionStream(_StreamState):
             self._k += 1
             self._trim(rec[0] + 1)      # every later window (regular or the last one) starts after this one
         if not outs:
-            return torch.empty(0, dtype=torch.float32, device=self.dev)
-        return outs[0] if len(outs) == 1 else torch.cat(outs)
+            y = torch.empty(0, dtype=torch.float32, device=self.dev)
+        else:
+            y = outs[0] if len(outs) == 1 else torch.cat(outs)
+        return y if self.rout is None else self.rout.push(y)
 
     @torch.no_grad()
     def close(self):
         if self._closed:
             raise RuntimeError("close() called twice")
         self._closed = True
+        if self.rin is not None:
+            self._append(self.rin.close())
         outs = [self._run(rec, Tw) for rec, Tw in self._tail_plan()]
         self._buf, self._len = self._buf[:0], 0
-        return outs[0] if len(outs) == 1 else torch.cat(outs)
+        y = outs[0] if len(outs) == 1 else torch.cat(outs)
+        return y if self.rout is None else self.rout.close(y)
 
 
 class StreamPool:
@@ -477,7 +498,11 @@ class StreamPool:
     Launch sizes come from a fixed ladder (``launch_ladder``: 1, 2, 4, ..., max_windows_per_launch); a partial launch
     is padded with copies of one of its windows whose output is dropped, and the engine keeps one workspace per ladder
     size resident (``ConverterEngine.resident_workspaces`` is raised to len(ladder) + 1, the one spare for the T-frame
-    final windows of streams shorter than a window).  ``tau`` is one launch scalar for the whole pool."""
+    final windows of streams shorter than a window).  ``tau`` is one launch scalar for the whole pool.
+
+    ``open(..., sr_in=None, sr_out=None)``: the stream's pushes / output at rates of their own.  A ``step()`` then first
+    resamples the new input of every such stream to the model rate in ONE launch (``rates.ResamplerBank``) and, after the
+    windows, the new output of every such stream in one more; ``latency_of(h)`` is the stream's own bound."""
 
     def __init__(self, conv, tau=0.3, max_windows_per_launch=DEFAULT_POOL_WINDOWS_PER_LAUNCH):
         self.conv, self.tau = conv, tau
@@ -486,6 +511,10 @@ class StreamPool:
         self._streams = {}          # handle -> _StreamState, in handle order
         self._next = 0
         self._retired = set()
+        dev = conv._device()
+        self._rin, self._rout = rates.ResamplerBank(dev), rates.ResamplerBank(dev)
+        self._rin_owner = {}        # input resampler key -> stream
+        self._rout_ending = []      # output resampler keys of streams that finished in this step
         engine = getattr(conv.model, "engine", None)
         if callable(engine):
             eng = engine()
@@ -503,11 +532,23 @@ class StreamPool:
         c = self.conv
         return (c.window_frames - 1) * c.hop + c.n_fft - c.pad
 
-    def open(self, src_se, tgt_se, noise=None):
+    def open(self, src_se, tgt_se, noise=None, sr_in=None, sr_out=None):
+        st = _StreamState(self.conv, src_se, tgt_se, noise, sr_in=sr_in, sr_out=sr_out)
+        msr = self.conv.model_sr
+        if st.sr_in is not None and st.sr_in != msr:
+            st.rin = self._rin.open(st.sr_in, msr)
+            self._rin_owner[st.rin] = st
+        if st.sr_out is not None and st.sr_out != msr:
+            st.rout = self._rout.open(msr, st.sr_out)
         h = self._next
         self._next += 1
-        self._streams[h] = _StreamState(self.conv, src_se, tgt_se, noise)
+        self._streams[h] = st
         return h
+
+    def latency_of(self, h):
+        """``(seconds, samples)``: stream h's latency bound at its own rates (samples in its output rate)."""
+        st = self._stream(h)
+        return st.latency_seconds, st.latency_samples
 
     def _stream(self, h):
         st = self._streams.get(h)
@@ -520,7 +561,10 @@ class StreamPool:
         st = self._stream(h)
         if st._closed:
             raise RuntimeError(f"push() after close() on stream {h!r}")
-        st._append(torch.as_tensor(samples, dtype=torch.float32).reshape(-1).to(st.dev))
+        if st.rin is not None:                  # resampled to the model rate by the next step()
+            self._rin.push(st.rin, rates.owned_samples(samples, st.dev))
+        else:
+            st._append(torch.as_tensor(samples, dtype=torch.float32).reshape(-1).to(st.dev))
 
     def close(self, h):
         """End of h's input.  Input shorter than the reflect padding or one frame raises ValueError here and retires h
@@ -529,20 +573,36 @@ class StreamPool:
         if st._closed:
             raise RuntimeError(f"close() called twice on stream {h!r}")
         st._closed = True
+        n = None
+        if st.rin is not None:                  # the model-rate samples the input resampler has still to deliver
+            n = st._n + self._rin.final_count(st.rin) - self._rin.emitted(st.rin)
+            self._rin.end(st.rin)
         try:
-            st._tail = st._tail_plan()
+            st._tail = st._tail_plan(n)
         except ValueError:
             self._retire(h)
             raise
 
-    def _retire(self, h):
+    def _retire(self, h, finished=False):
+        """``finished``: h ran its tail, so its output resampler (if any) still delivers its own in this step."""
         st = self._streams.pop(h)
         st._buf, st._len = st._buf[:0], 0
         self._retired.add(h)
+        if st.rin is not None:
+            self._rin.drop(st.rin)
+            self._rin_owner.pop(st.rin, None)
+        if st.rout is not None:
+            if finished:
+                self._rout_ending.append(st.rout)     # ended after this step's last output is queued
+            else:
+                self._rout.drop(st.rout)
 
     @torch.no_grad()
     def step(self):
         c = self.conv
+        for key, y in self._rin.step().items():
+            self._rin_owner[key]._append(y)
+        routs = {h: st.rout for h, st in self._streams.items() if st.rout is not None}
         sources, jobs, spans, acc = [], [], {}, 0
         for h, st in self._streams.items():
             if st._closed:
@@ -575,7 +635,16 @@ class StreamPool:
             st = self._streams[h]
             st._emitted = hi
             if st._closed:
-                self._retire(h)
+                self._retire(h, finished=True)
             else:
                 st._trim(f0 + 1)        # every later window (regular or the last one) starts after this one
+        if routs:
+            for h, key in routs.items():
+                if h in outs:
+                    self._rout.push(key, outs.pop(h))
+            for key in self._rout_ending:
+                self._rout.end(key)
+            self._rout_ending.clear()
+            ys = self._rout.step()
+            outs.update({h: ys[key] for h, key in routs.items() if key in ys})
         return outs

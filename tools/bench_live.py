@@ -4,8 +4,11 @@ tools/bench_streams.py: N streams of synthetic speech-like audio arriving in 100
 each (chunk, N): wall ms per 100 ms tick (pushes + conversions + a device sync), the aggregate real-time factor, the
 latency bound and the peak device allocation; the windowed pool at Tw = 255 frames is measured in the same run as the
 comparison row.
+With ``--sr-in`` / ``--sr-out`` every live stream takes its pushes (100 ms of audio each) at that rate and returns its output
+at that rate (openvoice_amd/rates.py: one resampler launch per direction and step); the model-rate live rows are then
+measured in the same run as the baseline.
 Measurement tool: python tools/bench_live.py [--streams 1 8 32 128] [--chunks 15 30 60] [--max-streams-per-launch 32]
-                                             [--min-ticks 20] [--out FILE]"""
+                                             [--min-ticks 20] [--sr-in HZ] [--sr-out HZ] [--out FILE]"""
 import argparse
 import json
 import math
@@ -19,17 +22,20 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tools.bench_streams import HOP, NFFT, SR, TICK, run as run_windowed, speechlike  # noqa: E402
 
 
-def run_live(model, chunk, N, M, min_ticks, dev, wave, ses):
+def run_live(model, chunk, N, M, min_ticks, dev, wave, ses, sr_in=None, sr_out=None):
     from openvoice_amd import live
     torch.cuda.empty_cache()
     torch.cuda.reset_peak_memory_stats(dev)
     pool = live.LivePool(model, tau=0.3, chunk_frames=chunk, max_streams_per_launch=M, n_fft=NFFT, hop=HOP)
     latency = pool.latency_samples
+    r_in, r_out = sr_in or SR, sr_out or SR
+    push_n = r_in // 10                           # input samples per 100 ms push
     gen = torch.Generator().manual_seed(N * 7 + chunk)
     offs = [int(torch.randint(0, wave.numel() // 4, (1,), generator=gen)) for _ in range(N)]
     # random phases within one chunk period, so chunks spread over ticks as they would for independent users
-    pos = [int(torch.randint(0, chunk * HOP, (1,), generator=gen)) for _ in range(N)]
-    hs = [pool.open(*ses[i % len(ses)]) for i in range(N)]
+    pos = [int(torch.randint(0, chunk * HOP, (1,), generator=gen)) * r_in // SR for _ in range(N)]
+    hs = [pool.open(*ses[i % len(ses)], sr_in=sr_in, sr_out=sr_out) for i in range(N)]
+    lat_s = float(pool.latency_of(hs[0])[0])
     for i, h in enumerate(hs):
         pool.push(h, wave[offs[i]:offs[i] + pos[i]])
     warm = math.ceil(latency / TICK) + 3          # past the first output of every stream: the steady state
@@ -40,16 +46,19 @@ def run_live(model, chunk, N, M, min_ticks, dev, wave, ses):
             torch.cuda.synchronize(dev)
             t0, out_samples = time.perf_counter(), 0
         for i, h in enumerate(hs):
-            pool.push(h, wave[offs[i] + pos[i]:offs[i] + pos[i] + TICK])
-            pos[i] += TICK
+            pool.push(h, wave[offs[i] + pos[i]:offs[i] + pos[i] + push_n])
+            pos[i] += push_n
         out_samples += sum(o.numel() for o in pool.step().values())
     torch.cuda.synchronize(dev)
     ms = (time.perf_counter() - t0) * 1e3 / ticks
-    return {"what": "live", "mode": "live_pool", "chunk_frames": chunk, "streams": N, "ticks": ticks,
-            "max_streams_per_launch": M, "out_s_per_s": round(out_samples / SR / (ticks / 10.0), 2),
-            "ms_per_tick": round(ms, 2), "real_time_factor": round(N * 100.0 / ms, 2), "real_time": ms <= 100.0,
-            "peak_gib": round(torch.cuda.max_memory_allocated(dev) / 2**30, 3), "latency_s": round(latency / SR, 3),
-            "state_mib_per_stream": round(pool.state_bytes_per_stream() / 2**20, 3)}
+    rec = {"what": "live", "mode": "live_pool", "chunk_frames": chunk, "streams": N, "ticks": ticks,
+           "max_streams_per_launch": M, "out_s_per_s": round(out_samples / r_out / (ticks / 10.0), 2),
+           "ms_per_tick": round(ms, 2), "real_time_factor": round(N * 100.0 / ms, 2), "real_time": ms <= 100.0,
+           "peak_gib": round(torch.cuda.max_memory_allocated(dev) / 2**30, 3), "latency_s": round(lat_s, 3),
+           "state_mib_per_stream": round(pool.state_bytes_per_stream() / 2**20, 3)}
+    if sr_in or sr_out:
+        rec.update(sr_in=r_in, sr_out=r_out, resampler_launches=pool._rin.launches + pool._rout.launches)
+    return rec
 
 
 def main():
@@ -59,6 +68,8 @@ def main():
     ap.add_argument("--max-streams-per-launch", type=int, default=32)
     ap.add_argument("--min-ticks", type=int, default=20)
     ap.add_argument("--no-windowed", action="store_true", help="skip the windowed Tw = 255 comparison rows")
+    ap.add_argument("--sr-in", type=int, default=None, help="rate of the pushes (default: the model rate)")
+    ap.add_argument("--sr-out", type=int, default=None, help="rate of the output (default: the model rate)")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
     from openvoice_amd.models import SynthesizerTrn
@@ -81,9 +92,16 @@ def main():
         lines.append(rec)
 
     emit({"what": "setup", "tick_samples": TICK, "max_streams_per_launch": M, "device": torch.cuda.get_device_name(dev)})
+    rated = args.sr_in is not None or args.sr_out is not None
+    wave_in = wave
+    if args.sr_in is not None and args.sr_in != SR:
+        from openvoice_amd import audio_io
+        wave_in = audio_io.resample_on_device(wave.to(dev), SR, args.sr_in).cpu()
     for chunk in args.chunks:
         for N in args.streams:
-            emit(run_live(model, chunk, N, M, args.min_ticks, dev, wave, ses))
+            if rated:                             # the model-rate row of the same run, then the resampled one
+                emit(run_live(model, chunk, N, M, args.min_ticks, dev, wave, ses))
+            emit(run_live(model, chunk, N, M, args.min_ticks, dev, wave_in, ses, args.sr_in, args.sr_out))
     if not args.no_windowed:
         eng.__dict__.pop("_live_ws", None)         # the windowed rows' peak memory without the live workspaces
         for N in args.streams:
