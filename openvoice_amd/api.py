@@ -127,8 +127,8 @@ class BaseSpeakerTTS(OpenVoiceBaseClass):
         for i, s in enumerate(seqs):
             x[i, :s.numel()] = s
         sid = torch.full((len(seqs),), int(speaker_id), dtype=torch.long)
-        # padded batch: the generator computes length + 16 frames per sentence, not the longest one's (the samples
-        # returned below are bit-identical either way)
+        # padded batch: the generator computes length + margin (16-20) frames per sentence, not the longest one's (the
+        # samples returned below are bit-identical either way)
         o, _, y_mask, _ = self.model.infer(x.to(device), lengths.to(device), sid=sid.to(device), noise_scale=noise_scale,
                                            noise_scale_w=noise_scale_w, length_scale=1.0 / speed, skip_padding=True)
         frames = y_mask[:, 0].sum(1).long().cpu().tolist()
@@ -274,8 +274,8 @@ class ToneColorConverter(OpenVoiceBaseClass):
             o_hat = self.model.voice_conversion(spec, spec_lengths, sid_src=src_se, sid_tgt=tgt_se, tau=tau,
                                                 noise=noise, graph=True, skip_padding=ragged)[0].clone()
         else:
-            # ragged batch: the generator skips what lies beyond length + 16 frames of each utterance (the samples
-            # within the returned lengths are bit-identical to the full computation; the padded tail is zero)
+            # ragged batch: the generator skips what lies beyond length + margin (16-20) frames of each utterance (the
+            # samples within the returned lengths are bit-identical to the full computation; the padded tail is zero)
             o_hat = self.model.voice_conversion(spec, spec_lengths, sid_src=src_se, sid_tgt=tgt_se, tau=tau,
                                                 noise=noise, skip_padding=ragged)[0]
         return o_hat, spec_lengths * hop

@@ -75,8 +75,13 @@ int ov_conv1d_wino_f32(const ov_conv1d_wino_params* pin, ov_stream_t stream) {
       (q.out_ld & 3) || (q.x_bstride & 3) || (q.out_bstride & 3) || (q.res && (q.res_bstride & 3)) ||
       (q.add && (q.add_bstride & 3)))
     return OV_E_ALIGN;
-  // 32-bit element offsets inside one utterance
+  // 32-bit element offsets inside one utterance; the helper waves address a chunk's CI staged rows as 32-bit BYTE offsets
   if ((int64_t)q.Cin * q.x_ld >= (1LL << 31) || (int64_t)q.Cout * q.out_ld >= (1LL << 31)) return OV_E_BADARG;
+  if ((int64_t)ov_conv1d_wino_chunk(q.K, q.Cout) * q.x_ld >= (1LL << 30)) return OV_E_BADARG;
+  // utterances must not overlap (a smaller stride would be read and written by two work items at once)
+  if (q.B > 1 && (q.x_bstride < (int64_t)q.Cin * q.x_ld || q.out_bstride < (int64_t)q.Cout * q.out_ld ||
+                  (q.res && q.res_bstride < (int64_t)q.Cout * q.out_ld) || (q.add && q.add_bstride < (int64_t)q.Cout * q.out_ld)))
+    return OV_E_BADARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (q.frags < 0 || q.frags > 2) return OV_E_BADARG;
   const int nf = q.frags ? q.frags : 2;

@@ -86,7 +86,7 @@ def validate_config(cfg):
             "of whole 32-row fragments)")
 
 
-def generator_margin_frames(cfg, conv_pre_kernel=7, conv_post_kernel=7):
+def generator_margin_frames(cfg, conv_pre_kernel=7, conv_post_kernel=7, chain_reach=None):
     """Frames beyond an utterance's end that can still influence its last sample: an UPPER BOUND of the generator's
     one-sided receptive field from the configuration (reference: openvoice/models.py:225-291 -- conv_pre, per stage a
     ConvTranspose1d of kernel k_u and stride u followed by the MRF whose widest ResBlock1 reaches
@@ -94,14 +94,18 @@ def generator_margin_frames(cfg, conv_pre_kernel=7, conv_post_kernel=7):
     dilation), conv_post), rounded up plus one frame of slack.  The transposed-conv term charges (k_u - u + 1) / spf
     frames per stage, more than the ceil((k_u - u) / 2 / u) + 1 inputs a stage really reaches back: the bound is loose
     by design.  15 for the released V1 / V2 configurations (``ConverterEngine`` uses max(GENERATOR_MARGIN = 16, this):
-    tests/test_host_algebra_cpu.py::test_generator_margin_released_configs)."""
+    tests/test_host_algebra_cpu.py::test_generator_margin_released_configs).  ``chain_reach(i, k, dilations)``, when
+    given, replaces the ResBlock term by the samples one chain of stage ``i`` really reaches forward with the kernels that
+    run it (``limit_margin_frames``)."""
     import math
     reach = (conv_pre_kernel - 1) / 2.0                      # frames
     spf = 1                                                  # samples per frame after the stage
-    for u, ku in zip(cfg["upsample_rates"], cfg["upsample_kernel_sizes"]):
+    if chain_reach is None:
+        chain_reach = lambda i, k, d: (k - 1) // 2 * (sum(d) + len(d))
+    for i, (u, ku) in enumerate(zip(cfg["upsample_rates"], cfg["upsample_kernel_sizes"])):
         spf *= u
         reach += (ku - u + 1) / 2.0 / spf * 2                # a transposed conv reaches ceil((k_u - u) / 2) + 1 inputs back
-        widest = max((k - 1) // 2 * (sum(d) + len(d)) for k, d in
+        widest = max(chain_reach(i, k, list(d)) for k, d in
                      zip(cfg["resblock_kernel_sizes"], cfg["resblock_dilation_sizes"]))
         reach += widest / spf
     reach += (conv_post_kernel - 1) / 2.0 / spf
@@ -317,12 +321,77 @@ WINO_MIN_ITEMS = 136
 SPLIT_MIN_CHANNELS = 128
 
 
-def wino_items(cout, dil, B, L):
-    """Work items of one ov_conv1d_wino_f32 launch (csrc/conv1d_wino.h: 256 columns per matrix wave at dilation 1,
+def _wino_mw(cout):
+    return 4 if cout % 128 == 0 else (2 if cout % 64 == 0 else 1)
+
+
+def wino_ncol(cout, dil):
+    """Output columns of one ov_conv1d_wino_f32 N-block (csrc/conv1d_wino.h: 256 columns per matrix wave at dilation 1,
     4 * (64 // dil) * dil at dilation dil; 4 / MW column sub-blocks per workgroup)."""
-    mw = 4 if cout % 128 == 0 else (2 if cout % 64 == 0 else 1)
-    ncol = (256 if dil == 1 else 4 * (64 // dil) * dil) * (4 // mw)
-    return B * ((L + ncol - 1) // ncol) * (cout // (32 * mw))
+    return (256 if dil == 1 else 4 * (64 // dil) * dil) * (4 // _wino_mw(cout))
+
+
+def wino_items(cout, dil, B, L):
+    """Work items of one ov_conv1d_wino_f32 launch: (utterance, N-block, M-block)."""
+    ncol = wino_ncol(cout, dil)
+    return B * ((L + ncol - 1) // ncol) * (cout // (32 * _wino_mw(cout)))
+
+
+# Columns per work item of the direct kernel (csrc/conv1d_mfma.h N_BLK): the launcher picks 128, 256 or 512 by row count
+# and device size.  Under a column limit a launch computes whole items, so the smallest is what skip_padding can rely on.
+DIRECT_MIN_NCOL = 128
+
+
+def conv_reach(family, K, dil=1):
+    """(left, right): output column t of a stride-1 'same' K-tap conv run by kernel ``family`` can depend, in floating
+    point and NaN propagation included, on input columns t - left .. t + right only.
+    'direct' (ov_conv1d_f32), 'pair' (ov_resblock_pair_f32, per conv) and 'split3' (ov_conv1d_split3): the taps,
+    (K - 1) / 2 * dil each way.  'wino' (ov_conv1d_wino_f32): an F(4, 3) tile computes the 4 outputs r + dil (4j + i)
+    from the 3 (G - 1) + 6 inputs r + dil (4j + m) - PAD dil, PAD = (K - 1) / 2 + lead (wino.LEAD_TAPS), and the inputs
+    reach outputs they cancel out of only in exact arithmetic: wider than the taps.  The window's first input enters point
+    0 alone (Bt row 0), which only output 0 reads (At column 0), its last one point infinity alone, which only output 3
+    reads; every other input reaches all 4 outputs.  So K = 3: 3 dil each way, K = 7: 6 dil, K = 11: 7 dil back and 8 dil
+    ahead (tests/test_gpu_wino.py measures it, NaN propagation included)."""
+    if family in ("direct", "pair", "split3"):
+        r = (K - 1) // 2 * dil
+        return r, r
+    if family == "wino":
+        from . import wino
+        G = (K + 2) // 3
+        pad = (K - 1) // 2 + wino.LEAD_TAPS[K]
+        return (pad + 2) * dil, (3 * (G - 1) + 4 - pad) * dil
+    raise ValueError(f"unknown conv family {family!r}")
+
+
+def resblock_families(C, K, dils, B, L, use_winograd=True, fuse_pairs=True):
+    """Kernel family of each conv of one ResBlock1 chain (C channels, kernel K, one (dilated, plain) pair per entry of
+    ``dils``) in a (B, L) launch of the fp32 generator: [(family of conv 1, family of conv 2)] with 'pair' (both convs in
+    one fused launch), 'wino' or 'direct'.  The policy ConverterEngine._mrf runs -- PAIR_POLICY, wino_policy,
+    WINO_MIN_ITEMS -- and the one limit_margin_frames prices; nothing else restates it."""
+    from . import wino
+    if fuse_pairs and L % 4 == 0 and all((C, K) in PAIR_POLICY and pair_supported(C, K, d) for d in dils):
+        return [("pair", "pair")] * len(dils)
+    fam = lambda d: ("wino" if use_winograd and L % 4 == 0 and wino.supported(C, C, K, d) and wino_policy(C, K, d)
+                     and wino_items(C, d, B, L) >= WINO_MIN_ITEMS else "direct")
+    return [(fam(d), fam(1)) for d in dils]
+
+
+def limit_margin_frames(cfg, B, T, use_winograd=True, fuse_pairs=True):
+    """Frames beyond an utterance's length that the fp32 generator computes under ``skip_padding`` in a (B, T) launch:
+    the receptive field of ``generator_margin_frames`` with every ResBlock conv charged the reach of the kernel that runs
+    it (conv_reach of resblock_families), at least GENERATOR_MARGIN.  The columns beyond the computed ones hold stale
+    scratch; a Winograd conv reads 2-3 dil columns further than its taps, so a direct-only launch keeps 16 while one with
+    Winograd stages needs more (tests/test_host_algebra_cpu.py simulates every launch of decode() column by column)."""
+    ch0, rates = cfg["upsample_initial_channel"], cfg["upsample_rates"]
+
+    def chain_reach(i, k, dils):
+        C, L = ch0 >> (i + 1), T
+        for u in rates[:i + 1]:
+            L *= u
+        fams = resblock_families(C, k, dils, B, L, use_winograd, fuse_pairs)
+        return sum(conv_reach(f1, k, d)[1] + conv_reach(f2, k, 1)[1] for (f1, f2), d in zip(fams, dils))
+
+    return max(GENERATOR_MARGIN, generator_margin_frames(cfg), generator_margin_frames(cfg, chain_reach=chain_reach))
 
 
 def wn_fused_row_order(hidden):
@@ -736,7 +805,7 @@ class ConverterEngine:
         replaces the reference's ``torch.randn_like`` draw (models.py:220); when omitted it is drawn
         from torch's generator on the device.  ``skip_padding``: the generator -- 98 % of the work, and unmasked in
         the reference, so a padded batch costs as if every utterance had the longest length -- computes only the
-        first ``length + GENERATOR_MARGIN`` frames of each utterance (length-aware work lists,
+        first ``length + limit_margin(B, T)`` frames of each utterance (length-aware work lists,
         ``ov_conv1d_params.col_limit``); every sample of the first ``length`` frames is bit-identical to the full
         computation, and everything beyond them in ``o_hat`` is zero instead of the reference's bias-driven junk."""
         dev = self.device
@@ -953,15 +1022,24 @@ class ConverterEngine:
         av = acc[:B * ch * L].view(B, ch, L)
         timed("split_layout", 0.0, lambda: split3.from_planes(ops[0], ops[1], ops[2], in_slope=1.0, scale=1.0 / nk, out=av))
 
+    def limit_margin(self, B, T):
+        """``limit_margin_frames`` of this engine's configuration for a (B, T) launch under the CURRENT
+        ``use_winograd`` / ``fuse_pairs`` (they may be switched after construction); at least ``generator_margin``."""
+        key = (int(B), int(T), bool(self.use_winograd), bool(self.fuse_pairs))
+        cache = self.__dict__.setdefault("_limit_margins", {})
+        if key not in cache:
+            cache[key] = max(self.generator_margin, limit_margin_frames(self.cfg, *key))
+        return cache[key]
+
     def frame_limits(self, lengths, T):
         """Two int32 [B] device vectors (``ov_frame_limits_i32``, no host sync): the frames of each utterance the
         generator must COMPUTE so that its first ``lengths[b]`` frames are unaffected by what lies beyond
-        (``length + GENERATOR_MARGIN``), and the frames it KEEPS (``length``): ``conv_post`` writes zeros beyond them, so
-        the whole of ``o_hat`` is defined -- what lies between the two is computed from neighbours that were skipped
+        (``length + limit_margin(B, T)``), and the frames it KEEPS (``length``): ``conv_post`` writes zeros beyond them,
+        so the whole of ``o_hat`` is defined -- what lies between the two is computed from neighbours that were skipped
         and must not leak into the result."""
         B = lengths.shape[0]
         lim = torch.empty(2, B, dtype=torch.int32, device=self.device)
-        _lib.call("ov_frame_limits_i32", lengths, lim[0], B, int(T), self.generator_margin)
+        _lib.call("ov_frame_limits_i32", lengths, lim[0], B, int(T), self.limit_margin(B, T))
         _lib.call("ov_frame_limits_i32", lengths, lim[1], B, int(T), 0)
         return lim
 
@@ -996,11 +1074,12 @@ class ConverterEngine:
         def chain(j, pairs):
             t1_, ra_ = scratch[j if concurrent else 0]
             cur = u
-            fused = self.fuse_pairs and L % 4 == 0 and all(
-                (ch, c1.K) in PAIR_POLICY and pair_supported(ch, c1.K, c1.dil) for c1, _ in pairs)
-            # Winograd-domain convs where an instance exists and wino_policy() picks it; they carry the same
-            # length-aware work lists (skip_padding) as the direct kernels
-            wn = self.wino_resblocks[i][j] if (self.use_winograd and L % 4 == 0) else None
+            # fused pairs, or Winograd-domain convs where an instance exists, wino_policy() picks it and the launch has
+            # WINO_MIN_ITEMS items; all carry the same length-aware work lists (skip_padding)
+            fams = resblock_families(ch, pairs[0][0].K, [c1.dil for c1, _ in pairs], B, L, self.use_winograd,
+                                     self.fuse_pairs)
+            fused = fams[0][0] == "pair"
+            wn = self.wino_resblocks[i][j]
             for n, (c1, c2) in enumerate(pairs):
                 last = n == len(pairs) - 1
                 if last and concurrent and j > 0:
@@ -1012,11 +1091,7 @@ class ConverterEngine:
                     dst = acc if last else (t1_ if cur is ra_ else ra_)
                     self._pair(c1, c2, cur, dst, bs, B, L, add, scale, **lim(rate))
                 else:
-                    w1, w2 = wn[n] if wn is not None else (None, None)
-                    if w1 is not None and wino_items(ch, w1.dil, B, L) < WINO_MIN_ITEMS:
-                        w1 = None           # too few items for one workgroup per CU: the direct kernel's small tiles
-                    if w2 is not None and wino_items(ch, 1, B, L) < WINO_MIN_ITEMS:
-                        w2 = None
+                    w1, w2 = (w if f == "wino" else None for w, f in zip(wn[n], fams[n]))
                     # t1 is read by c2 only, which activates it: a Winograd c1 stores it activated (the same
                     # values, modules.py:298-301) and c2 -- either kernel -- stages it as is
                     if w1 is not None:

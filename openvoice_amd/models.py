@@ -101,8 +101,8 @@ class SynthesizerTrn(nn.Module):
         reference's ``randn_like`` draw (optional).  ``graph=True`` replays the launch sequence of this
         (B, T, tau) shape from a captured HIP graph (``engine.GraphedConversion``); the returned tensors are
         then static buffers, valid until the next graphed call of the same shape.  ``skip_padding=True`` (ragged
-        batches): the generator computes only ``length + 16`` frames per utterance -- valid samples bit-identical,
-        the padded tail of ``o_hat`` zero (``ConverterEngine.voice_conversion``)."""
+        batches): the generator computes only ``length + limit_margin`` (16-20) frames per utterance -- valid samples
+        bit-identical, the padded tail of ``o_hat`` zero (``ConverterEngine.voice_conversion``)."""
         eng = self.engine()
         if self.n_speakers != 0:
             eng = eng.core      # a TTS checkpoint also carries enc_q / flow / dec

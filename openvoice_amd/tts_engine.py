@@ -135,7 +135,8 @@ class TtsEngine:
         """Same contract as the reference (models.py:467-490): returns
         ``(o [B,1,256*Ty'], attn [B,1,Ty,Tx], y_mask [B,1,Ty], (z, z_p, m_p, logs_p) [B,192,Ty])``.
         ``noise_w`` [B,2,Tx] / ``noise_z`` [B,192,>=Ty] replace the reference's two RNG draws when given.
-        ``skip_padding``: the generator computes only ``y_length + 16`` frames of each utterance of a padded batch
+        ``skip_padding``: the generator computes only ``y_length + core.limit_margin(B, Ty)`` frames (16-20) of each
+        utterance of a padded batch
         (valid samples bit-identical, the padded tail of ``o`` zero; ``ConverterEngine.voice_conversion``)."""
         dev = self.device
         tokens = tokens.to(dev, torch.int64).contiguous()

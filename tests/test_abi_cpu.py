@@ -85,6 +85,38 @@ def test_bad_arguments_are_rejected_without_a_gpu():
     assert lib.ov_conv1d_pack_size(0, 1, 1) == 0
 
 
+def test_wino_rejects_wrapping_rows_and_overlapping_utterances_without_a_gpu():
+    """``ov_conv1d_wino_f32`` refuses a chunk of CI staged rows of 2^30 floats or more (the helper waves address them as
+    32-bit byte offsets) and, when B > 1, batch strides smaller than C x ld.  No call here can launch a kernel: every one
+    asks for a dilated launch with one fragment per wave, which has no instance -- the dispatcher returns
+    OV_E_UNSUPPORTED after the argument checks and before any launch -- so an otherwise equal call proves the checks let
+    it through, and a check that regressed shows as OV_E_UNSUPPORTED, not as a launch on made-up addresses."""
+    import ctypes
+    lib = _lib.load()
+    E_BADARG, E_UNSUPPORTED = -1, -2
+    assert lib.ov_conv1d_wino_chunk(3, 128) == 16 and lib.ov_conv1d_wino_supported(16, 128, 3, 3) == 1
+
+    def params(**kw):
+        p = _lib.ConvWinoParams()
+        p.x, p.w, p.bias, p.out = 0x10000, 0x20000, 0x30000, 0x40000     # never dereferenced: no call reaches a launch
+        p.B, p.Cin, p.Cout, p.L, p.K, p.dil, p.frags, p.in_slope, p.scale = 1, 16, 128, 256, 3, 3, 1, 0.1, 1.0
+        p.x_bstride, p.out_bstride = 16 * 256, 128 * 256
+        for k, v in kw.items():
+            setattr(p, k, v)
+        assert p.dil != 1 and p.frags == 1          # the one combination the dispatcher refuses before launching
+        return ctypes.byref(p)
+
+    assert lib.ov_conv1d_wino_f32(params(), None) == E_UNSUPPORTED
+    assert lib.ov_conv1d_wino_f32(params(x_ld=1 << 26, x_bstride=16 << 26), None) == E_BADARG       # 16 x 2^26 rows
+    assert lib.ov_conv1d_wino_f32(params(x_ld=(1 << 26) - 4, x_bstride=16 << 26), None) == E_UNSUPPORTED
+    assert lib.ov_conv1d_wino_f32(params(B=2, x_bstride=16 * 256 - 4), None) == E_BADARG
+    assert lib.ov_conv1d_wino_f32(params(B=2, out_bstride=128 * 256 - 4), None) == E_BADARG
+    assert lib.ov_conv1d_wino_f32(params(B=2, res=0x50000, res_bstride=0), None) == E_BADARG
+    assert lib.ov_conv1d_wino_f32(params(B=2, add=0x60000, add_bstride=4), None) == E_BADARG
+    assert lib.ov_conv1d_wino_f32(params(B=2, res=0x50000, res_bstride=128 * 256, add=0x60000, add_bstride=128 * 256),
+                                  None) == E_UNSUPPORTED
+
+
 def test_bf16_params_struct_matches_header_field_order():
     header = open(os.path.join(REPO, "include", "openvoice_amd.h")).read()
     body = header[header.index("typedef struct ov_conv1d_bf16_params {"):header.index("} ov_conv1d_bf16_params;")]

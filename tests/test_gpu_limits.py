@@ -220,3 +220,158 @@ def test_one_minute_utterances(synth_sd):
     err = (o.cpu() - o_ref).abs().max().item()
     print("60 s utterances vs oracle:", err)
     assert err <= 1e-3
+
+
+# ---- skip_padding on poisoned scratch ----------------------------------------------------------------------------------
+# The decoder scratch (ws["dec"], the concurrent chains' dec_extra) comes from torch.empty, and conv_pre's output ws["pre"]
+# is written by earlier calls: under skip_padding the columns beyond each launch's last block keep whatever an earlier
+# call left there.  These tests fill that scratch with NaN and
+# run the limited conversion FIRST, so that a kernel reading one column too far (a Winograd tile reaches 2-3 dil columns
+# beyond its taps: engine.conv_reach) shows as a NaN or a changed bit inside an utterance.
+# Lengths: the ones whose limit ends a 128-column block of conv_pre and the stage-0 transposed conv with the receptive-field
+# margin of 16 frames (111 / 112 / 239 / 240 ... mod 128: the least slack in tests/test_host_algebra_cpu.py's simulated
+# decode), 752, 96, 1 and T.
+_POISON_T = 861
+_POISON_LENGTHS = [861, 752, 624, 240, 111, 96, 112, 1, 239, 367, 368, 495, 496, 623, 751, 300]
+
+
+def _poison(eng, B, T):
+    """NaN into every buffer a limited generator launch writes only in part: conv_pre's output (its T valid columns; the
+    pad columns [T, Tp) are never read) and every decoder scratch buffer of the (B, T) workspace, the concurrent chains'
+    included."""
+    ws = eng._workspace(B, T)
+    ws["pre"][:, :, :T].fill_(float("nan"))
+    nk = len(eng.cfg["resblock_kernel_sizes"])
+    for t in list(ws["dec"]) + eng._chain_scratch(ws, 2 * (nk - 1)):
+        t.fill_(float("nan"))
+
+
+def _assert_all_stages_winograd(B, T):
+    """Every generator stage of this launch runs Winograd-domain convs (stage 0 all of them): the policy cannot quietly
+    fall back to the direct kernel and make the test vacuous."""
+    from openvoice_amd.engine import WINO_MIN_ITEMS, resblock_families, wino_items
+    cfg = CONVERTER_MODEL_CONFIG
+    ch, L = cfg["upsample_initial_channel"], T
+    for i, u in enumerate(cfg["upsample_rates"]):
+        ch, L = ch // 2, L * u
+        fams = [f for k, d in zip(cfg["resblock_kernel_sizes"], cfg["resblock_dilation_sizes"])
+                for pair in resblock_families(ch, k, list(d), B, L) for f in pair]
+        assert "wino" in fams, (i, fams)
+        if i == 0:
+            assert set(fams) == {"wino"} and all(wino_items(ch, d, B, L) >= WINO_MIN_ITEMS for d in (1, 3, 5)), fams
+
+
+def _assert_kept_samples_equal(o_skip, o_full, lengths):
+    assert torch.isfinite(o_skip).all(), "NaN from the poisoned scratch reached the output"
+    for b, n in enumerate(lengths):
+        assert torch.equal(o_skip[b, :, :256 * n], o_full[b, :, :256 * n]), f"utterance {b} (length {n}): kept samples changed"
+        assert (o_skip[b, :, 256 * n:] == 0).all(), f"utterance {b}: tail not zero"
+
+
+def _vc_case(B, T, seed):
+    gen = torch.Generator().manual_seed(seed)
+    spec = (torch.rand(B, 513, T, generator=gen) * torch.linspace(3, 0.05, 513)[None, :, None]).to(DEV)
+    g1, g2 = (0.3 * torch.randn(1, 256, 1, generator=gen)).to(DEV), (0.3 * torch.randn(B, 256, 1, generator=gen)).to(DEV)
+    noise = torch.randn(B, 192, T, generator=gen).to(DEV)
+    return spec, g1, g2, noise
+
+
+@pytest.mark.parametrize("B,chains", [(8, 3), (16, 1)])
+def test_skip_padding_on_poisoned_scratch(synth_sd, B, chains):
+    """B = 8 at the benchmark length: 432 Winograd items at stage 0, and the three ResBlock chains on their own streams
+    with their own scratch (chain_streams, B <= chain_streams_max_batch); B = 16: the serial chains.  The limited
+    conversion runs first on NaN scratch; its kept samples equal the full conversion's bit for bit, its tail is zero."""
+    T = _POISON_T
+    _assert_all_stages_winograd(B, T)
+    lengths = _POISON_LENGTHS[:B]
+    spec, g1, g2, noise = _vc_case(B, T, seed=B)
+    model = _model(synth_sd)
+    eng = model.engine()
+    eng.chain_streams = chains
+    _poison(eng, B, T)
+    lt = torch.tensor(lengths, device=DEV)
+    o_skip = model.voice_conversion(spec, lt, g1, g2, tau=0.3, noise=noise, skip_padding=True)[0]
+    o_full = model.voice_conversion(spec, lt, g1, g2, tau=0.3, noise=noise)[0]
+    torch.cuda.synchronize()
+    _assert_kept_samples_equal(o_skip, o_full, lengths)
+
+
+def test_skip_padding_on_poisoned_scratch_graph_and_oracle(synth_sd):
+    """The captured graph of a skip_padding conversion replayed on NaN scratch (decoder buffers and the graph's own static
+    output): kept samples equal the eager full conversion's, and two utterances against the float64 oracle."""
+    from oracle import vc_oracle
+    B, T = 8, _POISON_T
+    _assert_all_stages_winograd(B, T)
+    lengths = _POISON_LENGTHS[:B]
+    spec, g1, g2, noise = _vc_case(B, T, seed=88)
+    model = _model(synth_sd)
+    eng = model.engine()
+    lt = torch.tensor(lengths, device=DEV)
+    g = eng.graphed(B, T, 0.3, 1, B, skip_padding=True)       # captured (its warm-up runs the full lengths)
+    _poison(eng, B, T)
+    g.out[0].fill_(float("nan"))
+    o_graph = model.voice_conversion(spec, lt, g1, g2, tau=0.3, noise=noise, graph=True, skip_padding=True)[0].clone()
+    o_full = model.voice_conversion(spec, lt, g1, g2, tau=0.3, noise=noise)[0]
+    torch.cuda.synchronize()
+    _assert_kept_samples_equal(o_graph, o_full, lengths)
+    rows = [1, 4]                                                # lengths 752 and 111; utterances are independent
+    torch.set_num_threads(min(16, os.cpu_count() or 1))
+    with torch.no_grad():
+        o_ref = vc_oracle.voice_conversion(synth_sd, CONVERTER_MODEL_CONFIG, spec[rows].cpu(), lt[rows].cpu(), g1.cpu(),
+                                           g2[rows].cpu(), 0.3, noise[rows].cpu(), zero_g=True)[0]
+    for r, b in enumerate(rows):
+        n = 256 * lengths[b]
+        err = (o_graph[b, :, :n].cpu().double() - o_ref[r, :, :n].double()).abs().max().item()
+        assert err <= 1e-3, (b, err)
+
+
+def test_convert_batch_ragged_on_poisoned_scratch(synth_sd, tmp_path):
+    """``ToneColorConverter.convert_batch`` on a ragged list (skip_padding by default) of 8 utterances, run on NaN
+    scratch: every sample within the returned lengths equals the full conversion of the same padded batch."""
+    import json
+    from openvoice_amd import api
+    from openvoice_amd.utils import default_converter_hparams
+    hps = default_converter_hparams("v2")
+    cfg = {"_version_": "v2", "data": dict(hps.data.items()), "model": dict(hps.model.items())}
+    (tmp_path / "config.json").write_text(json.dumps(cfg))
+    torch.save({"model": synth_sd}, tmp_path / "checkpoint.pth")
+    tcc = api.ToneColorConverter(str(tmp_path / "config.json"), device=DEV, enable_watermark=False)
+    tcc.load_ckpt(str(tmp_path / "checkpoint.pth"))
+    gen = torch.Generator().manual_seed(12)
+    waves = [0.3 * torch.randn(256 * max(n, 2), generator=gen) for n in _POISON_LENGTHS[:8]]   # (>= the reflect padding)
+    src, tgt = (0.3 * torch.randn(1, 256, 1, generator=gen)).to(DEV), (0.3 * torch.randn(1, 256, 1, generator=gen)).to(DEV)
+    specs = [tcc._spec(w.to(DEV).reshape(1, -1))[0] for w in waves]
+    frames = [s.shape[1] for s in specs]
+    spec = torch.zeros(8, specs[0].shape[0], max(frames), device=DEV)
+    for i, s in enumerate(specs):
+        spec[i, :, :s.shape[1]] = s
+    noise = torch.randn(8, 192, max(frames), generator=gen).to(DEV)
+    _poison(tcc.model.engine(), 8, max(frames))
+    o_skip, n_skip = tcc.convert_batch(waves, src, tgt, tau=0.3, noise=noise)
+    o_full = tcc.model.voice_conversion(spec, torch.tensor(frames, device=DEV), src, tgt, tau=0.3, noise=noise)[0]
+    torch.cuda.synchronize()
+    assert n_skip.tolist() == [256 * f for f in frames]
+    _assert_kept_samples_equal(o_skip, o_full, frames)
+
+
+def test_tts_infer_skip_padding_on_poisoned_scratch(synth_tts_sd):
+    """Batched TTS at the configs[3] batch (16): ``infer(skip_padding=True)`` on NaN decoder scratch keeps every sample
+    within each utterance's frames equal to the padded computation's."""
+    model = SynthesizerTrn(68, 513, n_speakers=10, **CONVERTER_MODEL_CONFIG)
+    model.load_state_dict(synth_tts_sd, strict=True)
+    model = model.to(DEV).eval()
+    B, Tx = 16, 64
+    gen = torch.Generator().manual_seed(23)
+    tokens = torch.randint(0, 68, (B, Tx), generator=gen)
+    lengths = torch.randint(Tx // 2, Tx + 1, (B,), generator=gen)
+    kw = dict(sid=(torch.arange(B) % 10).to(DEV), noise_scale=0.667, noise_scale_w=0.6, length_scale=1.0,
+              noise_w=torch.randn(B, 2, Tx, generator=gen).to(DEV), noise_z=torch.randn(B, 192, 16 * Tx, generator=gen).to(DEV))
+    o_full, _, y_mask, _ = model.infer(tokens.to(DEV), lengths.to(DEV), **kw)
+    torch.cuda.synchronize()
+    frames = y_mask[:, 0].sum(1).long().tolist()
+    assert len(set(frames)) > 1, "the batch must be ragged in frames for this test to mean anything"
+    _poison(model.engine().core, B, max(frames))
+    o_skip, _, y_mask2, _ = model.infer(tokens.to(DEV), lengths.to(DEV), skip_padding=True, **kw)
+    torch.cuda.synchronize()
+    assert torch.equal(y_mask, y_mask2) and o_full.shape == o_skip.shape
+    _assert_kept_samples_equal(o_skip, o_full, frames)

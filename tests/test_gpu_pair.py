@@ -182,3 +182,31 @@ def test_three_fused_pairs_match_the_reference_resblock1_module(golden_dir, name
         cur = nxt
     err = (cur.float().cpu().transpose(1, 2) - rec["out"]).abs().max().item()
     assert err <= 3e-2 * rec["out"].abs().max().item(), err
+
+
+@pytest.mark.parametrize("c,k,d", [s for s in SHAPES if pair_supported(*s)])
+def test_pair_nan_reaches_no_further_than_conv_reach(c, k, d):
+    """A NaN at input column q of a fused pair changes outputs within the two convs' reach only (engine.conv_reach('pair')
+    of each: (K - 1) / 2 * dil, then (K - 1) / 2), every other output bit-identical to the clean launch; q at step edges
+    (NT = 256 / 128 columns less P2), inside a step and next to L, and some q reaches the bound both ways."""
+    from openvoice_amd.engine import conv_reach
+    B, L = 1, 900
+    _, c1, c2 = _layers(c, k, d, seed=k + d)
+    x = _rand(B, c, L, seed=c + k + d).to(DEV)
+    clean = torch.empty(B, c, L, device=DEV)
+    launch_pair(c1, c2, x, c * L, clean, c * L, B, L)
+    reach = conv_reach("pair", k, d)[1] + conv_reach("pair", k, 1)[1]
+    cols = torch.arange(L, device=DEV)
+    seen = [0, 0]
+    p2 = (k - 1) // 2
+    for q in (0, 1, 128 - p2, 256 - p2 - 1, 256 - p2, 300, 450, L - 2, L - 1):
+        xp = x.clone()
+        xp[0, :, q] = float("nan")
+        out = torch.empty(B, c, L, device=DEV)
+        launch_pair(c1, c2, xp, c * L, out, c * L, B, L)
+        outside = (cols < q - reach) | (cols > q + reach)
+        assert torch.equal(out[0][:, outside], clean[0][:, outside]), (q, reach)
+        hit = torch.nonzero(torch.isnan(out[0]).any(0)).flatten()
+        assert hit.numel() and torch.isnan(out[0, :, q]).all(), q
+        seen = [max(seen[0], q - int(hit.min())), max(seen[1], int(hit.max()) - q)]
+    assert seen == [reach, reach], (seen, reach)

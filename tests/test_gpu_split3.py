@@ -210,3 +210,33 @@ def test_split3_full_size_properties(c, k, d, L):
     perm = torch.randperm(B, generator=torch.Generator().manual_seed(1)).to(DEV)
     assert torch.equal(run(planes(x[perm, s:])), base[:, perm])
     assert torch.equal(run(planes(4.0 * x[:, s:])).float(), 4.0 * base.float())
+
+
+@pytest.mark.parametrize("k,d", KD)
+def test_split3_nan_reaches_no_further_than_conv_reach(k, d):
+    """A NaN at input column q of ov_conv1d_split3 changes outputs within engine.conv_reach('split3', k, d) -- its taps --
+    only, every other output bit-identical to the clean launch, and some q reaches the bound both ways."""
+    from openvoice_amd.engine import conv_reach
+    c, B, L = 128, 1, 700
+    _, _, layer = _layer(c, k, d, seed=k + d)
+    x = _rand(B, c, L, seed=3 * k + d)
+
+    def run(xin):
+        out = torch.empty((3, B, L, c), dtype=torch.bfloat16, device=DEV)
+        launch_conv_split3(layer, to_planes(xin.to(DEV), SLOPE), out)
+        return _value(out)[0]
+
+    clean = run(x)
+    left, right = conv_reach("split3", k, d)
+    cols = torch.arange(L, device=DEV)
+    seen = [0, 0]
+    for q in (0, 1, 63, 64, 127, 128, 300, L - 2, L - 1):
+        xp = x.clone()
+        xp[0, :, q] = float("nan")
+        out = run(xp)
+        outside = (cols < q - right) | (cols > q + left)
+        assert torch.equal(out[:, outside], clean[:, outside]), (q, left, right)
+        hit = torch.nonzero(torch.isnan(out).any(0)).flatten()
+        assert hit.numel() and torch.isnan(out[:, q]).all(), q
+        seen = [max(seen[0], q - int(hit.min())), max(seen[1], int(hit.max()) - q)]
+    assert seen == [right, left], (seen, right, left)

@@ -109,12 +109,13 @@ def test_wino_64_and_32_row_layer_limits_and_workgroup_counts(C, K, dil):
 @pytest.mark.parametrize("frags", [1, 2])
 @pytest.mark.parametrize("K", [3, 7, 11])
 def test_wino_residual_running_sum_scale_and_padded_rows(K, frags):
-    """out = (conv + bias + res + add) * scale with x rows 8 floats longer than L and out rows 4 longer; pad columns of
-    out stay untouched."""
+    """out = (conv + bias + res + add) * scale with x rows 8 floats longer than L (NaN in those pad columns) and out rows 4
+    longer; pad columns of out stay untouched."""
     from openvoice_amd import wino
     C, B, L, xld, old = 128, 2, 520, 528, 524
     w, b, _, _, wn, gen = _setup(C, K, B, L, seed=K)
     x = torch.randn(B, C, xld, generator=gen).to(DEV)
+    x[:, :, L:] = float("nan")                   # pad columns are never read: NaN there changes nothing
     res = torch.randn(B, C, old, generator=gen).to(DEV)
     add = torch.randn(B, C, old, generator=gen).to(DEV)
     out = torch.full((B, C, old), 7.0, device=DEV)
@@ -170,6 +171,14 @@ def test_wino_refuses_what_it_cannot_run():
         wino.launch_conv_wino(wn, x, 128 * 256, x, 128 * 256, 1, 256)            # out aliases x
     with pytest.raises(_lib.OvError):
         wino.launch_conv_wino(wn, x, 128 * 254, out, 128 * 254, 1, 254)          # L % 4
+    x2 = torch.randn(2, 128, 256, device=DEV)
+    out2 = torch.empty(2, 128, 256, device=DEV)
+    with pytest.raises(_lib.OvError):
+        wino.launch_conv_wino(wn, x2, 128 * 256 - 4, out2, 128 * 256, 2, 256)   # utterances of x overlap
+    with pytest.raises(_lib.OvError):
+        wino.launch_conv_wino(wn, x2, 128 * 256, out2, 128 * 252, 2, 256)       # utterances of out overlap
+    # (a chunk of CI rows of 2^30 floats or more is refused too: tests/test_abi_cpu.py checks it without a device, since a
+    # launch that got through would read far beyond any allocation)
     assert wino.supported(128, 128, 11, 3) and not wino.supported(128, 128, 11, 2) and not wino.supported(32, 32, 7, 1)
     assert wino.supported(32, 32, 11, 1) and not wino.supported(48, 48, 11, 1)
 
@@ -193,3 +202,63 @@ def test_wino_length_aware_work_list(K, dil):
             done = min(L, (cols + ncol - 1) // ncol * ncol)
             assert torch.equal(out[bi, :, :done], full[bi, :, :done]), (bi, cols)
             assert torch.isnan(out[bi, :, done:]).all(), (bi, cols)
+
+
+# every (C, K, dil) the generator runs in the Winograd domain (engine.wino_policy over the released stages 256 / 128 / 64 / 32)
+_ENGINE_WINO = [(c, k, d) for c in (256, 128, 64) for k in (3, 7, 11) for d in (1, 3, 5)] + [(32, 11, 1)]
+
+
+@pytest.mark.parametrize("C,K,dil", _ENGINE_WINO)
+def test_wino_nan_reaches_no_further_than_conv_reach(C, K, dil):
+    """engine.conv_reach('wino', K, dil) = (left, right): a NaN at input column q changes outputs in [q - right, q + left]
+    only; every other output is bit-identical to the clean launch.  q at the start, inside and at the edges of N-blocks and
+    tiles, every phase of a tile, and next to L; the NaN must reach the output at q itself, and some phase the bound."""
+    from openvoice_amd import engine, wino
+    from openvoice_amd.engine import conv_reach, wino_policy
+    assert wino_policy(C, K, dil) and wino.supported(C, C, K, dil)
+    B, L = 2, 1100
+    w, b, x, _, wn, _ = _setup(C, K, B, L, seed=C + 3 * K + dil, dil=dil)
+    clean = torch.empty(B, C, L, device=DEV)
+    wino.launch_conv_wino(wn, x, C * L, clean, C * L, B, L, in_slope=0.1)
+    left, right = conv_reach("wino", K, dil)
+    ncol = engine.wino_ncol(C, dil)
+    cols = torch.arange(L, device=DEV)
+    seen = [0, 0]
+    edges = {0, 1, 5, ncol - 1, ncol, ncol + 2, 2 * ncol - 3, L - 2, L - 1} | set(range(500, 500 + 4 * dil))   # every tile phase
+    for q in sorted(c for c in edges if c < L):
+        xp = x.clone()
+        xp[1, :, q] = float("nan")
+        out = torch.empty(B, C, L, device=DEV)
+        wino.launch_conv_wino(wn, xp, C * L, out, C * L, B, L, in_slope=0.1)
+        outside = (cols < q - right) | (cols > q + left)
+        assert torch.equal(out[0], clean[0]), q
+        assert torch.equal(out[1][:, outside], clean[1][:, outside]), (q, left, right)
+        assert torch.isnan(out[1, :, q]).all(), q
+        hit = torch.nonzero(torch.isnan(out[1]).any(0)).flatten()
+        seen = [max(seen[0], q - int(hit.min())), max(seen[1], int(hit.max()) - q)]
+    assert seen == [right, left], (seen, right, left)        # and the bound is tight: some tile phase reaches it
+
+
+@pytest.mark.parametrize("K,dil", [(3, 1), (7, 3), (11, 5), (11, 1)])
+def test_direct_nan_reaches_no_further_than_conv_reach(K, dil):
+    """The direct kernel (ov_conv1d_f32): a NaN at input column q changes outputs within conv_reach('direct') = its taps,
+    and some q reaches that bound both ways."""
+    from openvoice_amd.engine import conv_reach, launch_conv
+    C, B, L = 128, 1, 700
+    w, b, x, direct, _, _ = _setup(C, K, B, L, seed=K + dil, dil=dil)
+    clean = torch.empty(B, C, L, device=DEV)
+    launch_conv(direct, x, 0, C * L, clean, 0, C * L, B, L, in_slope=0.1)
+    left, right = conv_reach("direct", K, dil)
+    cols = torch.arange(L, device=DEV)
+    seen = [0, 0]
+    for q in (0, 127, 128, 300, L - 1):
+        xp = x.clone()
+        xp[0, :, q] = float("nan")
+        out = torch.empty(B, C, L, device=DEV)
+        launch_conv(direct, xp, 0, C * L, out, 0, C * L, B, L, in_slope=0.1)
+        outside = (cols < q - right) | (cols > q + left)
+        assert torch.equal(out[0][:, outside], clean[0][:, outside]), (q, left, right)
+        assert torch.isnan(out[0, :, q]).all()
+        hit = torch.nonzero(torch.isnan(out[0]).any(0)).flatten()
+        seen = [max(seen[0], q - int(hit.min())), max(seen[1], int(hit.max()) - q)]
+    assert seen == [right, left], (seen, right, left)      # the taps: the bound is reached

@@ -178,3 +178,102 @@ def test_validate_config_names_the_unsupported_field():
         with pytest.raises(OvError) as e:
             validate_config(dict(base, **change))
         assert repr(field) in str(e.value) and why in str(e.value), (change, str(e.value))
+
+
+def _exact_after(e_in, computed, right, L):
+    """Exactly computed prefix of a conv's output: the columns it computes whose inputs up to ``right`` columns ahead
+    are themselves exact (a fully exact input is read with its 'same' zero padding beyond L)."""
+    import numpy as np
+    return np.where(e_in >= L, computed, np.clip(np.minimum(computed, e_in - right), 0, None))
+
+
+def _roundup(cols, block, L):
+    import numpy as np
+    return np.minimum(L, -(-cols // block) * block)
+
+
+# ov_resblock_pair_f32 output columns per step (csrc/conv1d_pair.hip: NT = 256 at C = 32, 128 at C = 64)
+_PAIR_NT = {32: 256, 64: 128}
+
+
+def _skip_padding_exact_samples(cfg, B, T, lengths, margin):
+    """Walk decode()'s launches under ``frame_limits`` (limit = min(length + margin, T) frames, each launch computing
+    whole blocks up to limit x rate columns) and return, per utterance, whether every one of its first 256 x length
+    output samples is computed from exactly computed columns only -- never from the stale decoder scratch beyond a
+    launch's last block.  The kernel family of every ResBlock conv comes from engine.resblock_families (the policy
+    _mrf runs), its reach from engine.conv_reach; direct launches are charged their smallest block (DIRECT_MIN_NCOL: a
+    wider one only computes more), Winograd launches wino_ncol, fused pairs their steps of NT columns."""
+    import numpy as np
+    from openvoice_amd.engine import DIRECT_MIN_NCOL, conv_reach, resblock_families, wino_ncol
+    n = np.asarray(lengths, dtype=np.int64)
+    lim = np.minimum(n + margin, T)
+    L = T
+    e = _roundup(lim, DIRECT_MIN_NCOL, L)                            # conv_pre (K = 7) on the fully computed z_hat
+    ch, rate = cfg["upsample_initial_channel"], 1
+    for u in cfg["upsample_rates"]:
+        # ConvTranspose1d as a 3-tap phase conv on the L input columns (limit x rate of them), stride u
+        e_in = _exact_after(e, _roundup(lim * rate, DIRECT_MIN_NCOL, L), 1, L)
+        ch, rate, L = ch // 2, rate * u, L * u
+        e_u = e_in * u
+        acc = None
+        for k, dils in zip(cfg["resblock_kernel_sizes"], cfg["resblock_dilation_sizes"]):
+            cur = e_u
+            cols = np.minimum(L, lim * rate)
+            for (f1, f2), d in zip(resblock_families(ch, k, list(dils), B, L), dils):
+                if f1 == "pair":
+                    nt, p2 = _PAIR_NT[ch], (k - 1) // 2
+                    done = np.where(cols > 0, np.minimum(L, -(-(cols + p2) // nt) * nt - p2), 0)
+                    reach = conv_reach("pair", k, d)[1] + conv_reach("pair", k, 1)[1]
+                    cur = np.minimum(cur, _exact_after(cur, done, reach, L))
+                    continue
+                blk = lambda f, dd: wino_ncol(ch, dd) if f == "wino" else DIRECT_MIN_NCOL
+                t1 = _exact_after(cur, _roundup(cols, blk(f1, d), L), conv_reach(f1, k, d)[1], L)
+                cur = np.minimum(cur, _exact_after(t1, _roundup(cols, blk(f2, 1), L), conv_reach(f2, k, 1)[1], L))
+            acc = cur if acc is None else np.minimum(acc, cur)       # the running sum: one addend per chain
+        e = acc
+    return (e >= L) | (e - 3 >= np.minimum(L, n * rate))            # conv_post (K = 7) keeps 256 x length samples
+
+
+def test_skip_padding_margin_keeps_every_kept_sample_exact():
+    """``engine.limit_margin_frames`` (the margin ``frame_limits`` passes to ``ov_frame_limits_i32``): for every batch
+    size that changes the launch policy, every T up to 900 frames and every length 1..T, no kept sample of a
+    ``skip_padding`` conversion reads a column of stale scratch -- the Winograd convs charged their tile reach, the fused
+    pairs and direct kernels their taps (released configuration, and one with wider kernels and dilations, which the
+    policy leaves on the direct kernels)."""
+    import numpy as np
+    from openvoice_amd.engine import limit_margin_frames
+    from openvoice_amd.utils import CONVERTER_MODEL_CONFIG
+    big = dict(CONVERTER_MODEL_CONFIG, resblock_kernel_sizes=[3, 7, 13], resblock_dilation_sizes=[[1, 3, 7]] * 3)
+    for cfg in (CONVERTER_MODEL_CONFIG, big):
+        for B in (1, 2, 3, 4, 8, 16, 32):
+            for T in range(1, 901):
+                ok = _skip_padding_exact_samples(cfg, B, T, np.arange(1, T + 1), limit_margin_frames(cfg, B, T))
+                assert ok.all(), (cfg["resblock_kernel_sizes"], B, T, (np.flatnonzero(~ok) + 1)[:8].tolist())
+
+
+def test_limit_margin_prices_the_kernels_that_run():
+    """``limit_margin_frames`` follows the launch policy: batch 1 at the benchmark length runs generator stage 0 on the
+    direct kernel and keeps the receptive-field margin (GENERATOR_MARGIN = 16 frames), as does an engine with the
+    Winograd-domain convs switched off; batch 8 runs every stage-0 conv in the Winograd domain, whose tiles reach 2-3 dil
+    columns beyond the taps (engine.conv_reach), and computes more frames.  The simulated decode keeps every kept sample
+    exact at both, and shows that 16 frames leave no slack once Winograd convs run."""
+    import numpy as np
+    from openvoice_amd.engine import GENERATOR_MARGIN, conv_reach, limit_margin_frames, resblock_families
+    from openvoice_amd.utils import CONVERTER_MODEL_CONFIG as cfg
+    T = 861
+    assert [conv_reach("wino", k, 1) for k in (3, 7, 11)] == [(3, 3), (6, 6), (7, 8)]
+    assert conv_reach("wino", 11, 5) == (35, 40) and conv_reach("direct", 11, 5) == conv_reach("pair", 11, 5) == (25, 25)
+    assert resblock_families(256, 11, [1, 3, 5], 1, 8 * T) == [("direct", "direct")] * 3
+    assert resblock_families(256, 11, [1, 3, 5], 8, 8 * T) == [("wino", "wino")] * 3
+    assert resblock_families(32, 7, [1, 3, 5], 8, 256 * T) == [("pair", "pair")] * 3
+    assert limit_margin_frames(cfg, 1, T) == limit_margin_frames(cfg, 8, T, use_winograd=False) == GENERATOR_MARGIN
+    assert limit_margin_frames(cfg, 8, T) > GENERATOR_MARGIN
+    for B in (1, 8):
+        assert _skip_padding_exact_samples(cfg, B, T, np.arange(1, T + 1), limit_margin_frames(cfg, B, T)).all()
+    # why the margin grows: at a Winograd batch the receptive-field 16 frames are exact with no slack (one frame less
+    # loses kept samples, e.g. length 113 at T = 513), where the direct kernels of batch 1 have a frame to spare
+    lengths = np.arange(1, 514)
+    assert _skip_padding_exact_samples(cfg, 4, 513, lengths, GENERATOR_MARGIN).all()
+    lost = np.flatnonzero(~_skip_padding_exact_samples(cfg, 4, 513, lengths, GENERATOR_MARGIN - 1)) + 1
+    assert 113 in lost.tolist(), lost
+    assert _skip_padding_exact_samples(cfg, 1, 513, lengths, GENERATOR_MARGIN - 1).all()

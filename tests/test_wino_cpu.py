@@ -82,15 +82,34 @@ def test_weight_packer_sub_record_order(cout, cin, k):
 def test_kernel_index_algebra_reproduces_the_conv(k, cin, L, cout):
     """One M-block (128 rows), the helper / matrix wave arithmetic of conv1d_wino_kernel replayed with numpy indexing
     exactly as the kernel forms its addresses (fp32 transforms, float64 accumulation so that only indices are on trial)."""
-    lib = _lib.load()
-    ci_chunk = lib.ov_conv1d_wino_chunk(k, cout)
-    G, pad, off0, wstart, nb128 = geo(k)
     slope = 0.1
-    nmt = cout // 32          # (a 64-row layer: two row fragments x two column sub-blocks per workgroup -- at dilation 1
-    gen = torch.Generator().manual_seed(5)   # the sub-blocks are consecutive 128-column ranges, so the same replay holds)
+    gen = torch.Generator().manual_seed(5)
     w = torch.randn(cout, cin, k, generator=gen) * (cin * k) ** -0.5
     x = torch.randn(cin, L, generator=gen).numpy()
     bias = torch.randn(cout, generator=gen).numpy()
+    out = _replay(k, x, w, bias, cout, slope)
+    xa = np.where(x > 0, x, slope * x)
+    cpad = (k - 1) // 2                                    # the conv's own 'same' padding (`pad` counts the leading zero taps too)
+    xp = np.pad(xa, ((0, 0), (cpad, cpad)))
+    ref = bias[:, None] + sum(w.numpy()[:, :, j].astype(np.float64) @ xp[:, j:j + L] for j in range(k))
+    assert np.abs(out - ref).max() < 2e-5, np.abs(out - ref).max()
+
+
+def _mul(m, v):
+    """m @ v with the products of zero coefficients left out (as the compiled transforms do: a zero coefficient is no
+    instruction, so a NaN it would multiply goes nowhere); m [r, c], v [..., c]."""
+    return np.where(m != 0, m * v[..., None, :], 0).sum(-1)
+
+
+def _replay(k, x, w, bias, cout, slope, sparse=False):
+    """The dilation-1 kernel replayed; ``sparse``: the transforms skip zero coefficients (see _mul) instead of
+    multiplying them."""
+    lib = _lib.load()
+    cin, L = x.shape
+    ci_chunk = lib.ov_conv1d_wino_chunk(k, cout)
+    G, pad, off0, wstart, nb128 = geo(k)
+    nmt = cout // 32          # (a 64-row layer: two row fragments x two column sub-blocks per workgroup -- at dilation 1
+    #                           the sub-blocks are consecutive 128-column ranges, so the same replay holds)
     packed = pack(w)
     nchunks, kr = cin // ci_chunk, ci_chunk * G
     npair = kr // 4
@@ -123,7 +142,7 @@ def test_kernel_index_algebra_reproduces_the_conv(k, cin, L, cout):
                     for g in range(G):
                         o = off0 - wstart + 3 * g
                         dst = 12 * ((g * npr + pr) * NT + tl) + 6 * ch
-                        V[dst:dst + 6] = bt @ win[o:o + 6]
+                        V[dst:dst + 6] = _mul(bt, win[o:o + 6]) if sparse else bt @ win[o:o + 6]
                         if g == 0 and wino.LEAD_TAPS[k]:
                             V[dst] = np.nan                # the helpers do not store the points of products never issued
                         if g == G - 1 and 3 * G - k - wino.LEAD_TAPS[k]:
@@ -143,17 +162,13 @@ def test_kernel_index_algebra_reproduces_the_conv(k, cin, L, cout):
                         for half in range(2):              # lane (half, n) -> B[k = half][n] at (s NT + n) 12 + 6 half + q
                             b = V[12 * s * NT + 6 * half + q: 12 * (s + 1) * NT: 12]
                             y[wave, q] += np.outer(a[32 * half:32 * half + 32].astype(np.float64), b.astype(np.float64))
-        o = np.einsum("ip,wprn->wrni", at, y)              # [wave][row][tile n][i]
+        o = _mul(at, np.moveaxis(y, 1, -1)) if sparse else np.einsum("ip,wprn->wrni", at, y)   # [wave][row][tile n][i]
         for wave in range(nmt):
             for n in range(32):
                 col = t0 + 4 * n
                 if col < L:
                     out[32 * wave:32 * wave + 32, col:col + 4] = o[wave, :, n, :]
-    xa = np.where(x > 0, x, slope * x)
-    cpad = (k - 1) // 2                                    # the conv's own 'same' padding (`pad` counts the leading zero taps too)
-    xp = np.pad(xa, ((0, 0), (cpad, cpad)))
-    ref = bias[:, None] + sum(w.numpy()[:, :, j].astype(np.float64) @ xp[:, j:j + L] for j in range(k))
-    assert np.abs(out - ref).max() < 2e-5, np.abs(out - ref).max()
+    return out
 
 
 @pytest.mark.parametrize("k,dil,cin,L,cout", [(11, 3, 8, 300, 128), (11, 5, 8, 244, 128), (7, 5, 8, 100, 128), (3, 3, 16, 256, 128),
@@ -163,7 +178,24 @@ def test_dilated_kernel_index_algebra_reproduces_the_conv(k, dil, cin, L, cout):
     4 J dil-column block; raw rows start PADA columns before the block; a tile reads 3 (G - 1) + 6 inputs dil apart; the
     outputs leave through an 8-row x 256-column stage and are stored 16 bytes per lane.  Replayed with the kernel's
     own index formulas."""
+    slope = 0.1
+    gen = torch.Generator().manual_seed(7)
+    w = torch.randn(cout, cin, k, generator=gen) * (cin * k) ** -0.5
+    x = torch.randn(cin, L, generator=gen).numpy()
+    bias = torch.randn(cout, generator=gen).numpy()
+    out = _replay_dilated(k, dil, x, w, bias, cout, slope)
+    xa = np.where(x > 0, x, slope * x)
+    cpad = (k - 1) // 2 * dil
+    xp = np.pad(xa, ((0, 0), (cpad, cpad)))
+    ref = bias[:, None] + sum(w.numpy()[:, :, j].astype(np.float64) @ xp[:, j * dil:j * dil + L] for j in range(k))
+    assert not np.isnan(out).any()
+    assert np.abs(out - ref).max() < 2e-5, np.abs(out - ref).max()
+
+
+def _replay_dilated(k, dil, x, w, bias, cout, slope, sparse=False):
+    """The dilated kernel replayed (``sparse`` as in _replay)."""
     lib = _lib.load()
+    cin, L = x.shape
     ci_chunk = lib.ov_conv1d_wino_chunk(k, cout)
     G = (k + 2) // 3
     NTS = 64                       # tiles per sub-block (one matrix wave's two fragments)
@@ -176,12 +208,7 @@ def test_dilated_kernel_index_algebra_reproduces_the_conv(k, dil, cin, L, cout):
     pada = (padd + 3) // 4 * 4
     nv = 3 * (G - 1) + 6
     rw = (pada - padd + dil - 1 + dil * (4 * (J - 1) + nv - 1) + 1 + 3) // 4 * 4 + (NB - 1) * ncols
-    slope = 0.1
     nmt = cout // 32
-    gen = torch.Generator().manual_seed(7)
-    w = torch.randn(cout, cin, k, generator=gen) * (cin * k) ** -0.5
-    x = torch.randn(cin, L, generator=gen).numpy()
-    bias = torch.randn(cout, generator=gen).numpy()
     packed = pack(w)
     nchunks, kr = cin // ci_chunk, ci_chunk * G
     npair = kr // 4
@@ -215,7 +242,7 @@ def test_dilated_kernel_index_algebra_reproduces_the_conv(k, dil, cin, L, cout):
                     assert win.size == nv
                     for g in range(G):
                         dst = 12 * ((g * npr + pr) * NT + tile) + 6 * ch
-                        V[dst:dst + 6] = bt @ win[3 * g: 3 * g + 6]
+                        V[dst:dst + 6] = _mul(bt, win[3 * g: 3 * g + 6]) if sparse else bt @ win[3 * g: 3 * g + 6]
                         if g == 0 and wino.LEAD_TAPS[k]:
                             V[dst] = np.nan                # (points of products never issued are not stored)
                         if g == G - 1 and 3 * G - k - wino.LEAD_TAPS[k]:
@@ -234,7 +261,7 @@ def test_dilated_kernel_index_algebra_reproduces_the_conv(k, dil, cin, L, cout):
                         for half in range(2):
                             b = V[12 * s * NT + 6 * half + q: 12 * (s + 1) * NT: 12]
                             y[wave, q] += np.outer(a[32 * half:32 * half + 32].astype(np.float64), b.astype(np.float64))
-        o = np.einsum("ip,wprn->wrni", at, y)              # [row fragment][row][tile][i]
+        o = _mul(at, np.moveaxis(y, 1, -1)) if sparse else np.einsum("ip,wprn->wrni", at, y)   # [fragment][row][tile][i]
         for sub in range(NB):                              # each matrix wave stages its own sub-block
             stage = np.full((nmt, 32, 256), np.nan)        # (the kernel walks it 8 rows at a time)
             for tl in range(NTS):
@@ -248,9 +275,40 @@ def test_dilated_kernel_index_algebra_reproduces_the_conv(k, dil, cin, L, cout):
                 col = t0 + sub * ncols + 4 * lane
                 if 4 * lane < ncols and col < L:
                     out[:, col:col + 4] = stage[:, :, 4 * lane:4 * lane + 4].reshape(cout, 4)
-    xa = np.where(x > 0, x, slope * x)
-    cpad = (k - 1) // 2 * dil
-    xp = np.pad(xa, ((0, 0), (cpad, cpad)))
-    ref = bias[:, None] + sum(w.numpy()[:, :, j].astype(np.float64) @ xp[:, j * dil:j * dil + L] for j in range(k))
-    assert not np.isnan(out).any()
-    assert np.abs(out - ref).max() < 2e-5, np.abs(out - ref).max()
+    return out
+
+
+@pytest.mark.parametrize("dil", [1, 3, 5])
+@pytest.mark.parametrize("k", [3, 7, 11])
+def test_emulated_nan_reach_is_conv_reach(k, dil):
+    """One input column q set to NaN, replayed through the kernel's own index algebra at every phase of a tile, at block
+    edges and next to L: the NaN outputs lie within engine.conv_reach('wino', k, dil) = (left, right), i.e. in
+    [q - right, q + left], and some phase reaches both ends.  That holds with the transforms skipping their zero
+    coefficients, as the compiled kernel does (tests/test_gpu_wino.py measures the same bound on the device).  With dense
+    transforms -- 0 x NaN = NaN in Bt and At -- the first and last input of a tile's window would reach all 4 outputs
+    and the reach would be one dil wider each way: the full window, 3 (G - 1) + 6 inputs."""
+    from openvoice_amd.engine import conv_reach
+    cout = 128
+    cin = _lib.load().ov_conv1d_wino_chunk(k, cout)
+    gen = torch.Generator().manual_seed(11 * k + dil)
+    w = torch.randn(cout, cin, k, generator=gen) * (cin * k) ** -0.5
+    bias = torch.randn(cout, generator=gen).numpy()
+    L = 600
+    x0 = torch.randn(cin, L, generator=gen).numpy()
+    left, right = conv_reach("wino", k, dil)
+    block = 128 if dil == 1 else 4 * (64 // dil) * dil
+    phases = set(range(260, 260 + 4 * dil)) | {0, 1, block - 1, block, L - 2, L - 1}
+    seen = {False: [0, 0], True: [0, 0]}
+    for sparse in (True, False):
+        for q in sorted(phases):
+            x = x0.copy()
+            x[cin // 2, q] = np.nan
+            out = _replay(k, x, w, bias, cout, 0.1, sparse) if dil == 1 else _replay_dilated(k, dil, x, w, bias, cout, 0.1, sparse)
+            hit = np.flatnonzero(np.isnan(out).any(0))
+            assert hit.size and q in hit, q
+            back, ahead = q - hit.min(), hit.max() - q
+            if sparse:
+                assert back <= right and ahead <= left, (q, back, ahead, right, left)
+            seen[sparse] = [max(seen[sparse][0], back), max(seen[sparse][1], ahead)]
+    assert seen[True] == [right, left], (seen, right, left)
+    assert seen[False] == [right + dil, left + dil], (seen, right, left)
