@@ -294,6 +294,43 @@ int ov_stitch_window_cores_f32(const float* o_hat, const int64_t* windows, int W
 int ov_carry_rows_f32(const int64_t* records, int n_records, const float* src_base, int64_t src_elems, float* dst_base,
                       int64_t dst_elems, ov_stream_t stream);
 
+/* Silence removal ahead of the tone-colour embedding (openvoice_amd/vad.py, se_extractor.split_audio_vad): the
+ * procedure of reference openvoice/se_extractor.py:77-97 -- voice-activity segments, concatenated active audio -- with
+ * a deterministic energy detector standing in for the third-party network the reference calls (se_extractor.py:80-86:
+ * get_vad_segments(..., min_speech_duration=0.1, min_silence_duration=1)).  Three record-driven launches serve R
+ * recordings that lie in one float32 pool: records is a DEVICE int64 [R][2] of (base, n_samples); recording r is
+ * pool[base, base + n_samples) and has T_r = ceil(n_samples / H) frames; the per-frame tables have ldT >= max T_r
+ * columns.  Host checks of all three (OV_E_BADARG): null pointers, R outside [1, 65535], H not a positive multiple of 4,
+ * ldT <= 0, pool_len / out_len <= 0.  The kernels check every record: base < 0, n_samples <= 0, base + n_samples >
+ * pool_len or T_r > ldT make the recording empty (energies 0, nothing kept, nothing copied).  64-bit pool offsets.
+ * Additive symbols of ABI 2.12 (no version change).
+ *
+ * Frame energy (stands in for the detector's per-window speech probability, se_extractor.py:80-86):
+ *   energy[r][t] = mean of x[n]^2 over the samples n in [t H, min(n_samples, t H + 2 H)),  t < T_r  (0 for t >= T_r).
+ * 16-byte loads when the pool is 16-byte aligned and base % 4 == 0, scalars otherwise; a frame's sum is formed in one
+ * fixed order either way, so it does not depend on R or on where the recording lies in the pool. */
+int ov_vad_frame_energy_f32(const float* pool, int64_t pool_len, const int64_t* records, int R, int H, int ldT,
+                            float* energy, ov_stream_t stream);
+/* The keep / drop decision per frame (stands in for the segment rules of get_vad_segments, se_extractor.py:80-88), one
+ * workgroup per recording, prefix / suffix scans over the frame axis, any T_r:
+ *   raw-active  e[t] > max(floor_lin, max_t e[t] * range_lin);
+ *   a silent run between two raw-active frames shorter than min_silence_frames becomes active;
+ *   then an active run shorter than min_speech_frames becomes silent;
+ *   then every remaining run grows by pad_frames on each side, clipped to [0, T_r).
+ * mask [R][ldT] (1 = kept), offsets [R][ldT] = the kept samples before frame t (a frame holds min(H, n_samples - t H)),
+ * n_active [R] = the kept samples of the recording.  Additional host checks: min_silence_frames <= 0,
+ * min_speech_frames <= 0, pad_frames < 0, a negative or NaN floor_lin / range_lin (OV_E_BADARG). */
+int ov_vad_segments_i32(const float* energy, const int64_t* records, int R, int H, int ldT, float floor_lin,
+                        float range_lin, int min_silence_frames, int min_speech_frames, int pad_frames, int32_t* mask,
+                        int64_t* offsets, int64_t* n_active, ov_stream_t stream);
+/* The concatenation of the kept audio (se_extractor.py:90-94: audio_active += audio[start:end]):
+ *   out[out_bases[r] + offsets[r][t] + j] = pool[base_r + t H + j],  j < min(H, n_samples - t H), for every kept frame.
+ * out_bases is a DEVICE int64 [R].  16-byte copies when both buffers are 16-byte aligned and base and out_base are
+ * multiples of 4.  A frame whose destination would leave [0, out_len) copies nothing. */
+int ov_vad_compact_f32(const float* pool, int64_t pool_len, const int64_t* records, int R, int H, int ldT,
+                       const int32_t* mask, const int64_t* offsets, const int64_t* out_bases, float* out,
+                       int64_t out_len, ov_stream_t stream);
+
 /* Rate conversion at the audio boundary, reference openvoice/api.py:123,144 (``librosa.load(path, sr=...)`` = resampy's
  * kaiser_best band-limited sinc interpolation): a polyphase FIR over a mono waveform,
  *   y[t] = sum_{j < 2 taps} h[t % P][j] * x[(t * Q) / P - taps + 1 + j]        (x = 0 outside [0, n_in))
@@ -646,7 +683,7 @@ int ov_conv1d_wino_pack_f32(const float* w, int Cout, int Cin, int K, float* dst
  * was `reserved`; the struct grew by one pointer at its end).  2.06: ov_polyphase_fir_f32.  2.07: ov_conv1d_wino_f32 (+ _supported, _chunk,
  * _pack_size, _pack_f32).  2.08: ov_conv1d_wino_f32 instances for Cout % 32 == 0 at K = 11 (one 32-row fragment per
  * workgroup; ov_conv1d_wino_chunk(11, 32) = 2 where 2.07 returned 0).  2.09: ov_conv1d_wino_params.out_slope (the field that
- * was `reserved0`: same size and offset, 0 = none).  2.10: ov_frame_hops_windows_f32, ov_stitch_window_cores_f32.  2.11: ov_frame_hops_multi_f32.  2.12: ov_carry_rows_f32 (and, added later within 2.12 without a version change, ov_polyphase_fir_rows_f32).  The Python binding
+ * was `reserved0`: same size and offset, 0 = none).  2.10: ov_frame_hops_windows_f32, ov_stitch_window_cores_f32.  2.11: ov_frame_hops_multi_f32.  2.12: ov_carry_rows_f32 (and, added later within 2.12 without a version change, ov_polyphase_fir_rows_f32 and ov_vad_frame_energy_f32, ov_vad_segments_i32, ov_vad_compact_f32: additive symbols, which the Python binding looks up by name when it loads the library).  The Python binding
  * refuses a library older than the entry points it calls (openvoice_amd/_lib.py MIN_VERSION). */
 int ov_version(void);
 /* The version THIS header describes.  Parameter structs grow at their END in minor versions (2.04, 2.05, 2.07 did): a

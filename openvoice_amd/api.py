@@ -211,25 +211,35 @@ class ToneColorConverter(OpenVoiceBaseClass):
         d = self.hps.data
         return spectrogram_torch(y, d.filter_length, d.sampling_rate, d.hop_length, d.win_length, center=False)
 
-    def extract_se(self, ref_wav_list, se_save_path=None):
+    def extract_se(self, ref_wav_list, se_save_path=None, vad=False):
         """Mean reference-encoder embedding over the given audio files -> ``[1, gin, 1]``
         (reference: openvoice/api.py:114-139, which runs one spectrogram + one ``ref_enc`` call per file).  Here the
         files of equal length -- the ~10 s pieces ``se_extractor.get_se`` cuts a recording into -- are stacked into ONE
         ``[N, samples]`` spectrogram launch pair and ONE ``ref_enc`` launch sequence (the kernels take N); files of
-        other lengths keep the per-file path.  The mean runs over files in the caller's order either way."""
+        other lengths keep the per-file path.  The mean runs over files in the caller's order either way.
+        ``vad=True`` (opt-in) removes silence from every file first (``extract_se_from_audio``)."""
         if isinstance(ref_wav_list, str):
             ref_wav_list = [ref_wav_list]
         # (decoded on the host, resampled -- where the file's rate differs -- by the device kernel: audio_io.load_to_device)
         audios = [audio_io.load_to_device(f, self.hps.data.sampling_rate, self.device) for f in ref_wav_list]
-        gs = self.extract_se_from_audio(audios)
+        gs = self.extract_se_from_audio(audios, vad=vad)
         if se_save_path is not None:
             os.makedirs(os.path.dirname(se_save_path), exist_ok=True)
             torch.save(gs.cpu(), se_save_path)
         return gs
 
     @torch.no_grad()
-    def extract_se_from_audio(self, audios):
-        """``extract_se`` on decoded float32 waveforms (list of 1-D arrays / tensors at the model's sampling rate)."""
+    def extract_se_from_audio(self, audios, vad=False):
+        """``extract_se`` on decoded float32 waveforms (list of 1-D arrays / tensors at the model's sampling rate).
+        ``vad=True`` first removes silence from every item on the device, all items in one set of launches
+        (``openvoice_amd.vad.remove_silence_many``, the detector ``se_extractor.get_se`` applies); off by default."""
+        if vad:
+            from . import vad as vad_mod
+            d = self.hps.data
+            audios, _ = vad_mod.remove_silence_many(
+                [torch.as_tensor(a, dtype=torch.float32).to(self.device) for a in audios], d.sampling_rate, d.hop_length)
+            if any(len(a) == 0 for a in audios):
+                raise ValueError("extract_se(vad=True): an input holds no frame above the detector's threshold")
         groups = {}
         for i, a in enumerate(audios):
             groups.setdefault(len(a), []).append(i)

@@ -398,6 +398,9 @@ TORCH_LIBRARY(openvoice_amd, m) {
   bind_device<&ov_frame_hops_windows_f32>(m, "frame_hops_windows_f32");
   bind_device<&ov_frame_hops_multi_f32>(m, "frame_hops_multi_f32");
   bind_device<&ov_carry_rows_f32>(m, "carry_rows_f32");
+  bind_device<&ov_vad_frame_energy_f32>(m, "vad_frame_energy_f32");
+  bind_device<&ov_vad_segments_i32>(m, "vad_segments_i32");
+  bind_device<&ov_vad_compact_f32>(m, "vad_compact_f32");
   bind_device<&ov_stitch_window_cores_f32>(m, "stitch_window_cores_f32");
   bind_device<&ov_conv_post_tanh_f32>(m, "conv_post_tanh_f32");
   bind_device<&ov_conv_post_tanh_limited_f32>(m, "conv_post_tanh_limited_f32");

@@ -2,13 +2,19 @@
 
 Keeps the reference signature and return value (reference: openvoice/se_extractor.py:129-152):
 ``get_se(audio_path, vc_model, target_dir='processed', vad=True) -> (se [1,gin,1], audio_name)``.
-The reference first cuts the recording into ~10 s WAV files with a third-party VAD (silero via
-whisper_timestamped, se_extractor.py:77-116) or ASR (faster_whisper, :19-74) and then calls
-``vc_model.extract_se`` on the pieces.  Those third-party models are out of scope (SURVEY.md
-section 2 row 8): here the recording is cut into equal pieces of about ``split_seconds`` -- the same
-``num_splits = round(dur / 10)`` rule the reference applies after VAD (se_extractor.py:99-103) --
-without removing silence, written under ``target_dir/<name>/wavs`` like the reference, and passed
-to ``extract_se``.
+
+``vad=True`` (the default) follows the reference's ``split_audio_vad`` (se_extractor.py:77-116): everything a
+voice-activity detector calls silence is removed, what is left is concatenated, and only then are the
+``num_splits = round(dur / 10)`` equal pieces cut (se_extractor.py:99-115) that ``vc_model.extract_se`` averages over,
+written under ``target_dir/<name>/wavs`` like the reference.  The reference's detector is a third-party network (silero
+through whisper_timestamped) whose weights are out of scope; the PROCEDURE is honoured with
+the deterministic energy detector of ``openvoice_amd/vad.py``, which runs on the device (three HIP launches) with the
+reference's ``min_speech_duration = 0.1`` and ``min_silence_duration = 1``.  Parity with silero's decisions is not
+claimed and cannot be pinned offline.  A recording without a frame below the detector's threshold is cut into exactly
+the pieces ``split_audio_equal`` cuts.
+
+``vad=False`` selects the reference's ASR splitter (faster_whisper, se_extractor.py:19-74), which stays out of scope:
+``split_audio_equal`` stands in for it and cuts the raw recording into equal pieces, pauses included.
 """
 import base64
 import hashlib
@@ -47,12 +53,41 @@ def split_audio_equal(audio_path, audio_name, target_dir, sampling_rate, split_s
     return wavs_folder
 
 
+def split_audio_vad(audio_path, audio_name, target_dir, split_seconds=10.0, sampling_rate=None, device=None,
+                    hop_length=None):
+    """reference: openvoice/se_extractor.py:77-116, with the energy detector of ``vad.remove_silence`` on ``device``.
+    ``sampling_rate`` / ``hop_length`` default to the converter's (22 050 Hz / 256), ``device`` to ``cuda:0``."""
+    from . import vad
+    from .utils import default_converter_hparams
+    data = default_converter_hparams("v2").data
+    sr = int(sampling_rate or data.sampling_rate)
+    audio = audio_io.load_to_device(audio_path, sr, device or "cuda:0")
+    active, segments = vad.remove_silence(audio, sr, int(hop_length or data.hop_length))
+    print([(s / sr, e / sr) for s, e in segments])
+    audio_active = active.cpu().numpy()
+    audio_dur = len(audio_active) / float(sr)
+    print(f"after vad: dur = {audio_dur}")
+    wavs_folder = os.path.join(target_dir, audio_name, "wavs")
+    os.makedirs(wavs_folder, exist_ok=True)
+    num_splits = int(np.round(audio_dur / split_seconds))
+    assert num_splits > 0, "input audio is too short"
+    bounds = np.linspace(0, len(audio_active), num_splits + 1).astype(np.int64)
+    for i in range(num_splits):
+        audio_io.write(os.path.join(wavs_folder, f"{audio_name}_seg{i}.wav"), audio_active[bounds[i]:bounds[i + 1]], sr)
+    return wavs_folder
+
+
 def get_se(audio_path, vc_model, target_dir="processed", vad=True):
     version = vc_model.version
     print("OpenVoice version:", version)
     audio_name = f"{os.path.basename(audio_path).rsplit('.', 1)[0]}_{version}_{hash_numpy_array(audio_path)}"
     se_path = os.path.join(target_dir, audio_name, "se.pth")
-    wavs_folder = split_audio_equal(audio_path, audio_name, target_dir, vc_model.hps.data.sampling_rate)
+    data = vc_model.hps.data
+    if vad:
+        wavs_folder = split_audio_vad(audio_path, audio_name, target_dir, sampling_rate=data.sampling_rate,
+                                      device=vc_model.device, hop_length=data.hop_length)
+    else:
+        wavs_folder = split_audio_equal(audio_path, audio_name, target_dir, data.sampling_rate)
     audio_segs = sorted(glob(f"{wavs_folder}/*.wav"))
     if len(audio_segs) == 0:
         raise NotImplementedError("No audio segments found!")
