@@ -293,6 +293,26 @@ int ov_stitch_window_cores_f32(const float* o_hat, const int64_t* windows, int W
  * multiples of 4, as scalars otherwise; 64-bit offsets.  ABI 2.12. */
 int ov_carry_rows_f32(const int64_t* records, int n_records, const float* src_base, int64_t src_elems, float* dst_base,
                       int64_t dst_elems, ov_stream_t stream);
+/* The two layout hand-overs of a live generator unit that runs the bf16 channels-last kernels (openvoice_amd/live.py,
+ * generator="bf16"): the live arena and the carries stay fp32 channels-first, the bf16 generator reads and writes dense
+ * channels-last bf16.  The fp32 side is B rows of `bs` elements, each [C][ld] with L valid columns; the bf16 side is a
+ * dense [B][L][C] tensor.  One launch per direction serves every row of a unit's batch.
+ *   ov_rows_f32_to_cl_bf16:  dst[(b * L + l) * C + c] = bf16(src[b * src_bs + c * src_ld + l]),  round to nearest
+ *     even with NaN -> 0x7fc0 and the infinities kept: the same bits as torch's
+ *     `x[..., :L].transpose(1, 2).to(torch.bfloat16).contiguous()` on a strided view, which it replaces
+ *     (GeneratorBf16.decode does that on a dense tensor, two torch launches);
+ *   ov_cl_bf16_to_rows_f32:  dst[b * dst_bs + c * dst_ld + l] = f32(src[(b * L + l) * C + c]),  exact; columns >= L and
+ *     everything between the rows are left as they were.  Replaces `dst[:, :, :L].copy_(src.transpose(1, 2))`.
+ * Both are transposes tiled through LDS (32 channels x 64 columns, rows padded by one float: no bank conflicts on either
+ * side), with 64-bit offsets.  The fp32 side moves as 16-byte vectors when its base is 16-byte aligned and ld and bs
+ * are multiples of 4 (a vector that would cross column L moves as scalars: any L >= 1), as scalars otherwise; the bf16
+ * side as 16-byte vectors when its base is 16-byte aligned.  Host checks (OV_E_BADARG): null pointers, B outside
+ * [1, 65535], C not a positive multiple of 32 (or > 32 * 65535), L < 1, ld < L, bs < C * ld.
+ * Additive symbols of ABI 2.12 (no version change). */
+int ov_rows_f32_to_cl_bf16(const float* src, int64_t src_bs, int src_ld, uint16_t* dst, int B, int C, int L,
+                           ov_stream_t stream);
+int ov_cl_bf16_to_rows_f32(const uint16_t* src, float* dst, int64_t dst_bs, int dst_ld, int B, int C, int L,
+                           ov_stream_t stream);
 
 /* Silence removal ahead of the tone-colour embedding (openvoice_amd/vad.py, se_extractor.split_audio_vad): the
  * procedure of reference openvoice/se_extractor.py:77-97 -- voice-activity segments, concatenated active audio -- with
@@ -683,7 +703,7 @@ int ov_conv1d_wino_pack_f32(const float* w, int Cout, int Cin, int K, float* dst
  * was `reserved`; the struct grew by one pointer at its end).  2.06: ov_polyphase_fir_f32.  2.07: ov_conv1d_wino_f32 (+ _supported, _chunk,
  * _pack_size, _pack_f32).  2.08: ov_conv1d_wino_f32 instances for Cout % 32 == 0 at K = 11 (one 32-row fragment per
  * workgroup; ov_conv1d_wino_chunk(11, 32) = 2 where 2.07 returned 0).  2.09: ov_conv1d_wino_params.out_slope (the field that
- * was `reserved0`: same size and offset, 0 = none).  2.10: ov_frame_hops_windows_f32, ov_stitch_window_cores_f32.  2.11: ov_frame_hops_multi_f32.  2.12: ov_carry_rows_f32 (and, added later within 2.12 without a version change, ov_polyphase_fir_rows_f32 and ov_vad_frame_energy_f32, ov_vad_segments_i32, ov_vad_compact_f32: additive symbols, which the Python binding looks up by name when it loads the library).  The Python binding
+ * was `reserved0`: same size and offset, 0 = none).  2.10: ov_frame_hops_windows_f32, ov_stitch_window_cores_f32.  2.11: ov_frame_hops_multi_f32.  2.12: ov_carry_rows_f32 (and, added later within 2.12 without a version change, ov_polyphase_fir_rows_f32 and ov_vad_frame_energy_f32, ov_vad_segments_i32, ov_vad_compact_f32, ov_rows_f32_to_cl_bf16, ov_cl_bf16_to_rows_f32: additive symbols, which the Python binding looks up by name when it loads the library).  The Python binding
  * refuses a library older than the entry points it calls (openvoice_amd/_lib.py MIN_VERSION). */
 int ov_version(void);
 /* The version THIS header describes.  Parameter structs grow at their END in minor versions (2.04, 2.05, 2.07 did): a

@@ -414,30 +414,35 @@ class ToneColorConverter(OpenVoiceBaseClass):
         return self._windowed(window_frames, 1).stream_pool(tau=tau, max_windows_per_launch=max_windows_per_launch)
 
     # ---- low-latency live streams ------------------------------------------------------------------------------------
-    def live_stream(self, src_se, tgt_se, tau=0.3, chunk_frames=15, noise=None, sr_in=None, sr_out=None):
+    def live_stream(self, src_se, tgt_se, tau=0.3, chunk_frames=15, noise=None, sr_in=None, sr_out=None,
+                    generator="fp32"):
         """A ``live.LiveStream``: the conversion as a cascade of units that carry their recent input as state.
         ``push(samples)`` -> newly finished samples, ``close()`` -> the rest, ``latency_samples`` =
         ``live.live_latency_samples`` (1.45 s at 15 frames).  ``chunk_frames``: a positive multiple of 15 (the Winograd
-        grid).  The fp32 generator only (ValueError with use_bf16_generator / enable_split_bf16x3); never graph-captured.
+        grid).  ``generator``: ``"fp32"`` (default) or ``"bf16"`` -- the kernels of the generator units of THIS stream
+        (posterior encoder and flow stay fp32; same latency and state); the engine-wide switches stay off (ValueError
+        with use_bf16_generator / enable_split_bf16x3).  Never graph-captured.
         ``sr_in`` / ``sr_out``: the rate of the pushes / of the output (None: the model rate); ``latency_samples`` (in
         output samples) and ``latency_seconds`` then include the resamplers' waits (``rates.stream_latency``).  With
         ``noise`` ``[1, 192, >= T]`` the output equals ``convert_long`` of the whole input (resampled to the model rate
-        before and to ``sr_out`` after by ``audio_io.resample_on_device``)."""
+        before and to ``sr_out`` after by ``audio_io.resample_on_device``), with ``generator="bf16"`` the one made with
+        ``use_bf16_generator``."""
         from . import live
         d = self.hps.data
         return live.LiveStream(self.model, src_se, tgt_se, tau=tau, chunk_frames=chunk_frames, noise=noise,
                                n_fft=d.filter_length, hop=d.hop_length, sr_in=sr_in, sr_out=sr_out,
-                               model_sr=d.sampling_rate)
+                               model_sr=d.sampling_rate, generator=generator)
 
-    def live_pool(self, tau=0.3, chunk_frames=15, max_streams_per_launch=32):
+    def live_pool(self, tau=0.3, chunk_frames=15, max_streams_per_launch=32, generator="fp32"):
         """A ``live.LivePool``: many live streams (``open(src_se, tgt_se, noise=None, sr_in=None, sr_out=None)`` /
         ``push`` / ``close``), every stream with a ready chunk converted by one ``step()`` in launches of up to
         ``max_streams_per_launch`` rows per unit; streams at rates of their own are resampled in one launch per direction
-        and step.  Each stream equals its solo ``live_stream``.  One ``tau`` for the pool."""
+        and step.  Each stream equals its solo ``live_stream``.  One ``tau`` and one ``generator`` (``"fp32"`` or
+        ``"bf16"``) for the pool; pools of both kinds may be open on one converter at once."""
         from . import live
         d = self.hps.data
         return live.LivePool(self.model, tau=tau, chunk_frames=chunk_frames, max_streams_per_launch=max_streams_per_launch,
-                             n_fft=d.filter_length, hop=d.hop_length, model_sr=d.sampling_rate)
+                             n_fft=d.filter_length, hop=d.hop_length, model_sr=d.sampling_rate, generator=generator)
 
     def convert_many(self, items, src_se, tgt_se, tau=0.3, window_frames=longform.DEFAULT_WINDOW_FRAMES,
                      windows_per_launch=longform.DEFAULT_MANY_WINDOWS_PER_LAUNCH, noise=None, output_paths=None,

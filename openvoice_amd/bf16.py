@@ -228,28 +228,121 @@ class GeneratorBf16:
             self._ws[key] = dict(pre=f(B * T * self.cfg["upsample_initial_channel"]), dec=[f(B * biggest) for _ in range(nbuf)])
         return self._ws[key]
 
+    def _stage_flags(self, i):
+        """``(act, fused, mean_act)`` of stage i, a function of the configuration and of ``fuse_pairs`` / ``act_hbm``:
+        ``act`` -- the stage keeps its tensors activated in HBM (second-generation pairs); ``fused[j]`` -- ResBlock j
+        runs first-generation fused pairs; ``mean_act`` -- the stage stores its output, the MRF mean, activated."""
+        ch = self.cfg["upsample_initial_channel"] >> (i + 1)
+        nk = len(self.cfg["resblock_kernel_sizes"])
+        act = (self.act_hbm and self.fuse_pairs and
+               all(pair2_bf16_supported(ch, c1.K, c1.dil) for pairs in self.resblocks[i] for c1, _ in pairs))
+        fused = [self.fuse_pairs and all(pair_bf16_supported(ch, c1.K, c1.dil) for c1, _ in pairs)
+                 for pairs in self.resblocks[i]]
+        # can the launch that writes the MRF mean apply an activation?  (the first-generation fused pair cannot)
+        mean_act = i + 1 < len(self.ups) and (act or not fused[nk - 1])
+        return act, fused, mean_act
+
+    def stage_scratch_elems(self, i, B, L):
+        """Elements of each of the scratch buffers ``stage(i, ...)`` takes for ``B`` rows of ``L`` input columns."""
+        return B * L * self.ups[i]["stride"] * (self.cfg["upsample_initial_channel"] >> (i + 1))
+
+    @torch.no_grad()
+    def stage(self, i, x, out, B, L, cond=None, bufs=None, pre=None, side=None):
+        """Generator stage ``i`` on caller-given dense channels-last tensors: [conv_pre with the per-row ``cond`` bias
+        (stage 0)], the ConvTranspose, the MRF, [conv_post and tanh (last stage)] -- ``decode`` is a loop over it.
+
+        ``x``: bf16 [B, L, C_in].  Stage 0 takes the raw latent ([B, L, inter]) and ``cond`` [B, ch] fp32; a later stage
+        takes exactly what stage i - 1 stored: the MRF mean, activated (``lrelu(x)`` in bf16) when that stage's
+        ``_stage_flags`` say ``mean_act``, raw otherwise.  ``out``: bf16 [B, L * stride, C_in / 2], or fp32
+        [B, 1, L * stride] from the last stage.  ``bufs``: a list of flat bf16 scratch tensors of at least
+        ``stage_scratch_elems(i, B, L)`` elements each, none aliasing ``x`` or ``out`` -- 3 are taken from its end (4 by
+        the last stage; 2 more per further chain with ``side``); ``pre`` (stage 0): flat bf16 of B * L * ch elements.
+        ``side``: the HIP streams of ``chain_streams > 1`` (``decode`` passes them); a live unit leaves it None and its
+        launches go to the current stream in the serial order, whatever ``chain_streams`` says."""
+        from .engine import FINAL_LRELU_SLOPE, LRELU_SLOPE
+        nstage = len(self.ups)
+        s = self.ups[i]["stride"]
+        cin = self.cfg["upsample_initial_channel"] >> i
+        ch = cin // 2
+        nk = len(self.cfg["resblock_kernel_sizes"])
+        last_stage = i == nstage - 1
+        if i == 0:
+            p = pre[: B * L * cin].view(B, L, cin)
+            # every tensor a ConvTranspose reads is stored ACTIVATED by its producer (conv_pre here, the MRF mean below):
+            # its loaders then copy instead of unpacking / activating / re-packing every vector
+            _launch(self.conv_pre, x, p, L, bias=cond, bias_bstride=cin, out_slope=LRELU_SLOPE)
+            cur_x, cur_act = p, True                      # cur_act: cur_x holds lrelu(x) already
+        else:
+            cur_x, cur_act = x, self._stage_flags(i - 1)[2]
+        act, fused, mean_act = self._stage_flags(i)
+        concurrent = side is not None
+        u = bufs.pop()[: B * L * s * ch].view(B, L * s, ch)
+        _launch(self.ups[i]["conv"], cur_x, u, L, in_slope=1.0 if cur_act else LRELU_SLOPE, phase_s=s,
+                out_slope=LRELU_SLOPE if act else 1.0)
+        L *= s
+        acc = bufs.pop()[: B * L * ch].view(B, L, ch) if last_stage else out
+        nchains = nk if concurrent else 1
+        scratch = [tuple(bufs.pop()[: B * L * ch].view(B, L, ch) for _ in range(2)) for _ in range(nchains)]
+        cur = [u] * nk
+        npairs = len(self.resblocks[i][0])
+
+        def pair(j, n):
+            c1, c2 = self.resblocks[i][j][n]
+            t1, ra = scratch[j if concurrent else 0]
+            last = n == npairs - 1
+            add = acc if (last and j > 0) else None
+            scale = 1.0 / nk if (last and j == nk - 1) else 1.0
+            # the MRF mean feeds the next stage's ConvTranspose, which wants it activated; the last stage's feeds
+            # conv_post (its own slope, applied there); the chains' partial sums stay raw
+            mean_slope = LRELU_SLOPE if (last and j == nk - 1 and mean_act) else 1.0
+            if act:            # activated tensors between the launches
+                dst = acc if last else (t1 if cur[j] is ra else ra)
+                launch_pair2_bf16(c1, c2, cur[j], dst, add=add, scale=scale, slope=LRELU_SLOPE,
+                                  out_slope=mean_slope if last else LRELU_SLOPE)
+            elif fused[j]:       # one launch per pair, intermediate in LDS; out must not alias x: ra / t1 ping-pong
+                dst = acc if last else (t1 if cur[j] is ra else ra)
+                launch_pair_bf16(c1, c2, cur[j], dst, add=add, scale=scale, slope=LRELU_SLOPE)
+            else:
+                # t1 is consumed by c2 only, which activates it: store it activated (one rounding instead of
+                # two) and let c2's loaders copy it as is
+                _launch(c1, cur[j], t1, L, in_slope=LRELU_SLOPE, out_slope=LRELU_SLOPE)
+                dst = acc if last else ra
+                _launch(c2, t1, dst, L, in_slope=1.0, res=cur[j], add=add, scale=scale, out_slope=mean_slope)
+            cur[j] = dst
+
+        if not concurrent:
+            for j in range(nk):
+                for n in range(npairs):
+                    pair(j, n)
+        else:
+            main = torch.cuda.current_stream(self.device)
+            fork = torch.cuda.Event()
+            fork.record(main)
+            done = [None] * nk
+            for n in range(npairs):                 # round-robin over the chains: every queue has work early
+                for j in range(nk):
+                    with torch.cuda.stream(side[j]):
+                        if n == 0:
+                            side[j].wait_event(fork)
+                        if n == npairs - 1 and j > 0:
+                            side[j].wait_event(done[j - 1])      # the running sum is accumulated in chain order
+                        pair(j, n)
+                        if n == npairs - 1:
+                            done[j] = torch.cuda.Event()
+                            done[j].record(side[j])
+            main.wait_event(done[nk - 1])
+        if last_stage:
+            _lib.call("ov_conv_post_tanh_bf16", acc, self.post_w, out, B, ch, L, self.post_w.shape[1], FINAL_LRELU_SLOPE)
+
     @torch.no_grad()
     def decode(self, z, g):
         """``z`` [B, inter, T] fp32 (channels-first, as the flow produces it), ``g`` [B or 1, gin, 1] ->
         waveform [B, 1, T * prod(upsample_rates)] fp32."""
-        from .engine import FINAL_LRELU_SLOPE, LRELU_SLOPE
         dev = self.device
         B, C, T = z.shape
         ws = self._workspace(B, T)
         x = z.to(dev, torch.float32).transpose(1, 2).to(torch.bfloat16).contiguous()        # [B, T, C] bf16
-        g2 = g.to(dev, torch.float32).reshape(g.shape[0], -1)
-        g2 = g2.contiguous()
-        cond = torch.empty(g2.shape[0], self.cond_w.shape[0], dtype=torch.float32, device=dev)
-        _lib.call("ov_linear_f32", g2, self.cond_w, self.cond_b, cond, g2.shape[0], self.cond_w.shape[0],
-                  self.cond_w.shape[1])                                                      # dec.cond, T = 1 GEMV
-        cond = cond.expand(B, -1).contiguous()                                               # [B, 512] fp32
-        ch = self.cfg["upsample_initial_channel"]
-        pre = ws["pre"][: B * T * ch].view(B, T, ch)
-        # every tensor a ConvTranspose reads is stored ACTIVATED by its producer (conv_pre here, the MRF mean below):
-        # its loaders then copy instead of unpacking / activating / re-packing every vector
-        _launch(self.conv_pre, x, pre, T, bias=cond, bias_bstride=ch, out_slope=LRELU_SLOPE)
-        cur_x, L, cur_act = pre, T, True                  # cur_act: cur_x holds lrelu(x) already
-        free = list(ws["dec"])
+        cond = self.cond_rows(g).expand(B, -1).contiguous()                                  # [B, 512] fp32
         nk = len(self.cfg["resblock_kernel_sizes"])
         # The three ResBlocks of a stage (k = 3, 7, 11) are independent chains until the MRF sum.  In bf16 they bound
         # DIFFERENT resources -- the k = 3 convs HBM (3.4 TB/s at 33 % matrix-busy), the k = 11 convs the power-limited
@@ -257,74 +350,28 @@ class GeneratorBf16:
         # the sum keeps its order (chain j's last launch waits for chain j - 1's), so the result is bit-identical to
         # the serial order.  Not under graph capture (the engine captures on one stream).
         concurrent = self.chain_streams > 1 and nk > 1 and not torch.cuda.is_current_stream_capturing()
-        main = torch.cuda.current_stream(dev)
         side = self._side_streams(nk) if concurrent else None
+        ch, L = self.cfg["upsample_initial_channel"], T
+        cur_x, free = x, list(ws["dec"])
         for i, up in enumerate(self.ups):
             s = up["stride"]
-            cin, ch = ch, ch // 2
-            u = free.pop()[: B * L * s * ch].view(B, L * s, ch)
-            act = (self.act_hbm and self.fuse_pairs and
-                   all(pair2_bf16_supported(ch, c1.K, c1.dil) for pairs in self.resblocks[i] for c1, _ in pairs))
-            _launch(up["conv"], cur_x, u, L, in_slope=1.0 if cur_act else LRELU_SLOPE, phase_s=s,
-                    out_slope=LRELU_SLOPE if act else 1.0)
-            L *= s
-            acc = free.pop()[: B * L * ch].view(B, L, ch)
-            nchains = nk if concurrent else 1
-            scratch = [tuple(free.pop()[: B * L * ch].view(B, L, ch) for _ in range(2)) for _ in range(nchains)]
-            cur = [u] * nk
-            fused = [self.fuse_pairs and all(pair_bf16_supported(ch, c1.K, c1.dil) for c1, _ in pairs)
-                     for pairs in self.resblocks[i]]
-            # can the launch that writes the MRF mean apply an activation?  (the first-generation fused pair cannot)
-            mean_act = i + 1 < len(self.ups) and (act or not fused[nk - 1])
-            npairs = len(self.resblocks[i][0])
-
-            def pair(j, n):
-                c1, c2 = self.resblocks[i][j][n]
-                t1, ra = scratch[j if concurrent else 0]
-                last = n == npairs - 1
-                add = acc if (last and j > 0) else None
-                scale = 1.0 / nk if (last and j == nk - 1) else 1.0
-                # the MRF mean feeds the next stage's ConvTranspose, which wants it activated; the last stage's feeds
-                # conv_post (its own slope, applied there); the chains' partial sums stay raw
-                mean_slope = LRELU_SLOPE if (last and j == nk - 1 and mean_act) else 1.0
-                if act:            # activated tensors between the launches
-                    dst = acc if last else (t1 if cur[j] is ra else ra)
-                    launch_pair2_bf16(c1, c2, cur[j], dst, add=add, scale=scale, slope=LRELU_SLOPE,
-                                      out_slope=mean_slope if last else LRELU_SLOPE)
-                elif fused[j]:       # one launch per pair, intermediate in LDS; out must not alias x: ra / t1 ping-pong
-                    dst = acc if last else (t1 if cur[j] is ra else ra)
-                    launch_pair_bf16(c1, c2, cur[j], dst, add=add, scale=scale, slope=LRELU_SLOPE)
-                else:
-                    # t1 is consumed by c2 only, which activates it: store it activated (one rounding instead of
-                    # two) and let c2's loaders copy it as is
-                    _launch(c1, cur[j], t1, L, in_slope=LRELU_SLOPE, out_slope=LRELU_SLOPE)
-                    dst = acc if last else ra
-                    _launch(c2, t1, dst, L, in_slope=1.0, res=cur[j], add=add, scale=scale, out_slope=mean_slope)
-                cur[j] = dst
-
-            if not concurrent:
-                for j in range(nk):
-                    for n in range(npairs):
-                        pair(j, n)
+            ch //= 2
+            if i + 1 < len(self.ups):
+                out = free.pop(-2)[: B * L * s * ch].view(B, L * s, ch)     # the ups output takes the last one
             else:
-                fork = torch.cuda.Event()
-                fork.record(main)
-                done = [None] * nk
-                for n in range(npairs):                 # round-robin over the chains: every queue has work early
-                    for j in range(nk):
-                        with torch.cuda.stream(side[j]):
-                            if n == 0:
-                                side[j].wait_event(fork)
-                            if n == npairs - 1 and j > 0:
-                                side[j].wait_event(done[j - 1])      # the running sum is accumulated in chain order
-                            pair(j, n)
-                            if n == npairs - 1:
-                                done[j] = torch.cuda.Event()
-                                done[j].record(side[j])
-                main.wait_event(done[nk - 1])
+                out = torch.empty(B, 1, L * s, dtype=torch.float32, device=dev)
+            self.stage(i, cur_x, out, B, L, cond=cond if i == 0 else None, bufs=free, pre=ws["pre"], side=side)
+            L *= s
             # every scratch buffer except the one holding this stage's output is free again
-            free = [buf for buf in ws["dec"] if buf.data_ptr() != acc.data_ptr()]
-            cur_x, cur_act = acc, mean_act
-        o = torch.empty(B, 1, L, dtype=torch.float32, device=dev)
-        _lib.call("ov_conv_post_tanh_bf16", cur_x, self.post_w, o, B, ch, L, self.post_w.shape[1], FINAL_LRELU_SLOPE)
-        return o
+            free = [buf for buf in ws["dec"] if buf.data_ptr() != out.data_ptr()]
+            cur_x = out
+        return cur_x
+
+    def cond_rows(self, g):
+        """``g`` [rows, gin(, 1)] -> the conv_pre bias rows [rows, ch] fp32 (dec.cond + both biases), as ``decode``
+        computes them."""
+        g2 = g.to(self.device, torch.float32).reshape(g.shape[0], -1).contiguous()
+        cond = torch.empty(g2.shape[0], self.cond_w.shape[0], dtype=torch.float32, device=self.device)
+        _lib.call("ov_linear_f32", g2, self.cond_w, self.cond_b, cond, g2.shape[0], self.cond_w.shape[0],
+                  self.cond_w.shape[1])                                                      # dec.cond, T = 1 GEMV
+        return cond

@@ -1284,6 +1284,67 @@ class ConverterEngine:
             _lib.call("ov_conv_post_tanh_f32", acc, self.post_w, out, B, ch // 2, L * s, self.post_w.shape[1],
                       FINAL_LRELU_SLOPE)
 
+    # The same unit on the bf16 channels-last generator (``LivePool(generator="bf16")``).  The precision belongs to the
+    # pool that asks for it: nothing here reads or sets ``_bf16_on``, so fp32 and bf16 pools share one engine.
+    def _live_generator_bf16(self):
+        if self.generator_bf16 is None:
+            from .bf16 import GeneratorBf16
+            self.generator_bf16 = GeneratorBf16(self._state_dict_for_bf16, self.cfg, self.device)
+        return self.generator_bf16
+
+    @torch.no_grad()
+    @on_own_device
+    def live_cond_bf16(self, g_tgt):
+        """``g_tgt`` [rows, gin] -> the bf16 generator's conv_pre bias rows [rows, ch] (``GeneratorBf16.cond_rows``: the
+        launch ``decode`` issues, conv_pre's bias folded in -- not ``live_conds``' ``d``)."""
+        g_d = self._zeros_like_cached(g_tgt) if self.zero_g else g_tgt
+        return self._live_generator_bf16().cond_rows(g_d)
+
+    def live_workspace_bf16(self, key, B, width, stage):
+        """Scratch of one bf16 generator unit launch of ``B`` rows, ``width`` input columns at most, cached per
+        ``(key, B)`` like ``live_workspace`` (same counter, ``live_ws_builds``): the channels-last bf16 input and
+        output of the stage, the stage's own scratch buffers, and the conv_pre output (stage 0)."""
+        cache = self.__dict__.setdefault("_live_ws_bf16", {})
+        ws = cache.get((key, B))
+        if ws is not None:
+            assert ws["width"] >= width, "live unit wider than its workspace"
+            return ws
+        self.live_ws_builds = getattr(self, "live_ws_builds", 0) + 1
+        gen = self._live_generator_bf16()
+        f = lambda n: torch.empty(n, dtype=torch.bfloat16, device=self.device)
+        ch = self.cfg["upsample_initial_channel"] >> stage
+        last = stage == len(self.cfg["upsample_rates"]) - 1
+        n = gen.stage_scratch_elems(stage, B, width)
+        ws = dict(width=width, xin=f(B * width * (self.inter if stage == 0 else ch)), out=None if last else f(n),
+                  bufs=[f(n) for _ in range(4 if last else 3)], pre=f(B * width * ch) if stage == 0 else None)
+        cache[(key, B)] = ws
+        return ws
+
+    @torch.no_grad()
+    @on_own_device
+    def live_generator_stage_bf16(self, i, x, x_ld, x_bs, out, B, L, ws, cond_d=None):
+        """``live_generator_stage`` on the bf16 kernels, same contract: ``x`` [B rows of ``x_bs``][C_in][``x_ld``] fp32
+        with ``L`` columns -> ``out`` dense fp32 [B, C_out, L * stride] ([B, 1, L * stride] for the last stage).
+        ``ov_rows_f32_to_cl_bf16`` -> ``GeneratorBf16.stage`` -> ``ov_cl_bf16_to_rows_f32`` (the last stage writes fp32
+        itself); ``ws`` from ``live_workspace_bf16``, ``cond_d`` [B, ch] from ``live_cond_bf16`` (stage 0).  The tensor
+        between two stages is what ``GeneratorBf16.decode`` keeps there, widened to fp32 and rounded back without
+        loss.  Exactly ``L`` columns are launched: the bf16 launchers take any L >= 1."""
+        if getattr(self, "_bf16_on", False) or self._split3_on:
+            raise _lib.OvError("a live unit's generator is chosen by its pool (use_bf16_generator / split_bf16x3 are off)")
+        gen = self._live_generator_bf16()
+        ch = self.cfg["upsample_initial_channel"] >> i
+        cin = self.inter if i == 0 else ch
+        s = self.ups[i]["stride"]
+        xin = ws["xin"][: B * L * cin].view(B, L, cin)
+        _lib.call("ov_rows_f32_to_cl_bf16", x, x_bs, x_ld, xin, B, cin, L)
+        bufs = list(ws["bufs"])
+        if i == len(self.ups) - 1:
+            gen.stage(i, xin, out[: B * L * s].view(B, 1, L * s), B, L, cond=cond_d, bufs=bufs, pre=ws["pre"])
+            return
+        o = ws["out"][: B * L * s * (ch // 2)].view(B, L * s, ch // 2)
+        gen.stage(i, xin, o, B, L, cond=cond_d, bufs=bufs, pre=ws["pre"])
+        _lib.call("ov_cl_bf16_to_rows_f32", o, out, (ch // 2) * L * s, L * s, B, ch // 2, L * s)
+
     # ---- extract_se path -----------------------------------------------------------------------------
     @torch.no_grad()
     @on_own_device

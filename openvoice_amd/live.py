@@ -30,6 +30,13 @@ and a second carry scatters the new columns into the next unit's state.  ``LiveS
 A stream opened with ``sr_in`` / ``sr_out`` (``rates``) takes its pushes at ``sr_in`` and returns samples at ``sr_out``: a
 step first resamples the new input of every such stream to the model rate in one launch, runs the rounds, then
 resamples every stream's new output in one more launch.
+
+``generator="bf16"`` (pool or stream) runs the ``g`` units on the bf16 channels-last generator (``bf16.GeneratorBf16``)
+instead of the fp32 kernels; ``q``, ``f`` and ``r`` stay fp32.  The cascade, the reaches, the arena and the carries are
+the same -- state stays fp32 channels-first -- so each ``g`` unit changes layout on the way in
+(``ov_rows_f32_to_cl_bf16``) and on the way out (``ov_cl_bf16_to_rows_f32``; the last stage writes fp32 itself).  What
+one stage hands the next is a bf16 value held in fp32, so the arena adds no rounding: the stream computes the one-pass
+bf16 conversion.  The choice belongs to the pool, not to the engine: fp32 and bf16 pools run side by side on one model.
 """
 import math
 
@@ -43,6 +50,13 @@ DEFAULT_CHUNK_FRAMES = 15
 DEFAULT_LIVE_STREAMS_PER_LAUNCH = 32
 CONV_PRE_KERNEL = 7
 CONV_POST_KERNEL = 7
+GENERATORS = ("fp32", "bf16")
+
+
+def check_generator(generator):
+    if generator not in GENERATORS:
+        raise ValueError(f"generator must be 'fp32' or 'bf16', got {generator!r}")
+    return generator
 
 
 def _stage_tile(cfg):
@@ -204,6 +218,8 @@ class _Live:
         g_src = src_se.to(dev, torch.float32).reshape(1, -1)
         g_tgt = tgt_se.to(dev, torch.float32).reshape(1, -1)
         self.conds = eng.live_conds(g_src, g_tgt)
+        if pool.generator == "bf16":        # the bf16 generator's own conv_pre bias row (conv_pre's bias folded in)
+            self.conds["d16"] = eng.live_cond_bf16(g_tgt)
         K = len(pool.units)
         self.stored = [0] * K       # executor view: input columns stored = [s0, stored)
         self.s0 = [0] * K
@@ -255,11 +271,15 @@ class LivePool:
     every ready stream advances by one chunk per round, each unit runs its streams' buffers in launches of up to
     ``max_streams_per_launch`` rows grouped by buffer width (steady-state streams share one width; a stream's first
     rounds and its end run narrower), padded up to the ``launch_ladder`` sizes.  ``tau`` is one scalar for the pool.
-    Live units run eagerly, never from a captured graph."""
+    Live units run eagerly, never from a captured graph.  ``generator``: ``"fp32"`` (default) or ``"bf16"`` -- the
+    kernels of the ``g`` units (module docstring); everything else, the latency and the state size included, is the
+    same for both."""
 
     def __init__(self, model, tau=0.3, chunk_frames=DEFAULT_CHUNK_FRAMES,
-                 max_streams_per_launch=DEFAULT_LIVE_STREAMS_PER_LAUNCH, n_fft=1024, hop=256, model_sr=rates.MODEL_RATE):
+                 max_streams_per_launch=DEFAULT_LIVE_STREAMS_PER_LAUNCH, n_fft=1024, hop=256, model_sr=rates.MODEL_RATE,
+                 generator="fp32"):
         self.model, self.tau = model, float(tau)
+        self.generator = check_generator(generator)
         self.cfg = model.model_cfg
         self.chunk = check_chunk(self.cfg, chunk_frames)
         eng = model.engine()
@@ -516,7 +536,9 @@ class LivePool:
 
     def _launch(self, k, rows, B, L):
         u, eng, mem = self.units[k], self.engine, self.mem
-        ws = eng.live_workspace((u["name"], self.width[k]), B, self.width[k], stage=u["stage"])
+        bf16 = u["kind"] == "g" and self.generator == "bf16"
+        ws = (eng.live_workspace_bf16 if bf16 else eng.live_workspace)((u["name"], self.width[k]), B, self.width[k],
+                                                                       stage=u["stage"])
         R, ldi, ldo, C = self.rows[k], self.ld_in[k], self.ld_out[k], self.cout[k]
         x = mem[self.in_off[k]:]
         out = mem[self.out_off[k]:]
@@ -529,6 +551,9 @@ class LivePool:
             key = "src" if u["kind"] == "f" else "tgt"
             conds = [torch.cat([st.conds[key][f] for st, _ in rows]) for f in range(len(rows[0][0].conds[key]))]
             eng.live_flow(x, out, B, L, conds, u["kind"] == "r", ws)
+        elif bf16:
+            cond = cat([st.conds["d16"] for st, _ in rows]) if u["stage"] == 0 else None
+            eng.live_generator_stage_bf16(u["stage"], x, ldi, R * ldi, out, B, L, ws, cond_d=cond)
         else:
             cond = cat([st.conds["d"] for st, _ in rows]) if u["stage"] == 0 else None
             eng.live_generator_stage(u["stage"], x, ldi, R * ldi, out, B, L, ws, cond_d=cond)
@@ -621,12 +646,12 @@ class LiveStream:
     """One live stream (a ``LivePool`` of one): ``push(samples)`` -> newly finished samples (device tensor, possibly
     empty), ``close()`` -> the rest, ``latency_samples`` the bound no output sample's delay exceeds (in output samples;
     ``latency_seconds`` the same bound in seconds).  ``sr_in`` / ``sr_out``: rates of the pushes / of the output (None:
-    the model rate)."""
+    the model rate).  ``generator``: as for ``LivePool``."""
 
     def __init__(self, model, src_se, tgt_se, tau=0.3, chunk_frames=DEFAULT_CHUNK_FRAMES, noise=None, n_fft=1024,
-                 hop=256, sr_in=None, sr_out=None, model_sr=rates.MODEL_RATE):
+                 hop=256, sr_in=None, sr_out=None, model_sr=rates.MODEL_RATE, generator="fp32"):
         self._pool = LivePool(model, tau=tau, chunk_frames=chunk_frames, max_streams_per_launch=1, n_fft=n_fft, hop=hop,
-                              model_sr=model_sr)
+                              model_sr=model_sr, generator=generator)
         self._h = self._pool.open(src_se, tgt_se, noise=noise, sr_in=sr_in, sr_out=sr_out)
         self.latency_seconds, self.latency_samples = self._pool.latency_of(self._h)
         self._closed = False

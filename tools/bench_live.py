@@ -7,8 +7,11 @@ comparison row.
 With ``--sr-in`` / ``--sr-out`` every live stream takes its pushes (100 ms of audio each) at that rate and returns its output
 at that rate (openvoice_amd/rates.py: one resampler launch per direction and step); the model-rate live rows are then
 measured in the same run as the baseline.
+With ``--generator fp32 bf16`` every (chunk, N) row is measured once per generator, one after the other in the same run
+(``LivePool(generator=...)``: the kernels of the generator units; the records carry ``generator``).
 Measurement tool: python tools/bench_live.py [--streams 1 8 32 128] [--chunks 15 30 60] [--max-streams-per-launch 32]
-                                             [--min-ticks 20] [--sr-in HZ] [--sr-out HZ] [--out FILE]"""
+                                             [--min-ticks 20] [--sr-in HZ] [--sr-out HZ] [--generator fp32 bf16]
+                                             [--out FILE]"""
 import argparse
 import json
 import math
@@ -22,11 +25,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tools.bench_streams import HOP, NFFT, SR, TICK, run as run_windowed, speechlike  # noqa: E402
 
 
-def run_live(model, chunk, N, M, min_ticks, dev, wave, ses, sr_in=None, sr_out=None):
+def run_live(model, chunk, N, M, min_ticks, dev, wave, ses, sr_in=None, sr_out=None, generator="fp32"):
     from openvoice_amd import live
     torch.cuda.empty_cache()
     torch.cuda.reset_peak_memory_stats(dev)
-    pool = live.LivePool(model, tau=0.3, chunk_frames=chunk, max_streams_per_launch=M, n_fft=NFFT, hop=HOP)
+    pool = live.LivePool(model, tau=0.3, chunk_frames=chunk, max_streams_per_launch=M, n_fft=NFFT, hop=HOP,
+                         generator=generator)
     latency = pool.latency_samples
     r_in, r_out = sr_in or SR, sr_out or SR
     push_n = r_in // 10                           # input samples per 100 ms push
@@ -51,7 +55,7 @@ def run_live(model, chunk, N, M, min_ticks, dev, wave, ses, sr_in=None, sr_out=N
         out_samples += sum(o.numel() for o in pool.step().values())
     torch.cuda.synchronize(dev)
     ms = (time.perf_counter() - t0) * 1e3 / ticks
-    rec = {"what": "live", "mode": "live_pool", "chunk_frames": chunk, "streams": N, "ticks": ticks,
+    rec = {"what": "live", "mode": "live_pool", "generator": generator, "chunk_frames": chunk, "streams": N, "ticks": ticks,
            "max_streams_per_launch": M, "out_s_per_s": round(out_samples / r_out / (ticks / 10.0), 2),
            "ms_per_tick": round(ms, 2), "real_time_factor": round(N * 100.0 / ms, 2), "real_time": ms <= 100.0,
            "peak_gib": round(torch.cuda.max_memory_allocated(dev) / 2**30, 3), "latency_s": round(lat_s, 3),
@@ -70,6 +74,8 @@ def main():
     ap.add_argument("--no-windowed", action="store_true", help="skip the windowed Tw = 255 comparison rows")
     ap.add_argument("--sr-in", type=int, default=None, help="rate of the pushes (default: the model rate)")
     ap.add_argument("--sr-out", type=int, default=None, help="rate of the output (default: the model rate)")
+    ap.add_argument("--generator", nargs="+", choices=["fp32", "bf16"], default=["fp32"],
+                    help="the live pools' generator kernels; both: every row once per generator, in the same run")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
     from openvoice_amd.models import SynthesizerTrn
@@ -99,11 +105,13 @@ def main():
         wave_in = audio_io.resample_on_device(wave.to(dev), SR, args.sr_in).cpu()
     for chunk in args.chunks:
         for N in args.streams:
-            if rated:                             # the model-rate row of the same run, then the resampled one
-                emit(run_live(model, chunk, N, M, args.min_ticks, dev, wave, ses))
-            emit(run_live(model, chunk, N, M, args.min_ticks, dev, wave_in, ses, args.sr_in, args.sr_out))
+            for generator in args.generator:
+                if rated:                         # the model-rate row of the same run, then the resampled one
+                    emit(run_live(model, chunk, N, M, args.min_ticks, dev, wave, ses, generator=generator))
+                emit(run_live(model, chunk, N, M, args.min_ticks, dev, wave_in, ses, args.sr_in, args.sr_out, generator))
     if not args.no_windowed:
         eng.__dict__.pop("_live_ws", None)         # the windowed rows' peak memory without the live workspaces
+        eng.__dict__.pop("_live_ws_bf16", None)
         for N in args.streams:
             emit(run_windowed(model, eng, 255, N, "pool", M, args.min_ticks, dev, wave, ses))
         eng.resident_workspaces = 1
