@@ -242,6 +242,24 @@ int ov_wn_pack_f32(const float* w, int rows, int cin, int K, float* dst);
  * columns, that fill the compute units in whole rounds (width > 0: validated and returned; 0 = invalid). */
 int ov_wn_layer_tile(int B, int T, int width);
 
+/* The same layer (reference openvoice/modules.py:192-209, commons.py:100-107) with the k = 5 gate conv computed in the
+ * Winograd domain: two F(4, 3) groups (w0 w1 w2)(w3 w4 0), 11 products per 4 output columns where the direct form needs
+ * 20 (openvoice_amd/csrc/wn_layer_wino.hip); the 1x1 res/skip conv and the updates of h / skip as in ov_wn_layer_f32.
+ * Same parameter struct and argument rules, except: w_in = ov_wn_wino_pack_f32 of the dense [2H][H][5] in_layer weight
+ * with its rows in the gate order described above (b_in, cond, w_rs, b_rs as for ov_wn_layer_f32); one workgroup per
+ * (utterance, tile of ov_wn_layer_wino_tile() = 128 columns), `width` 0 or 128; row_split / acts are ignored (one launch
+ * always) and dbg must be NULL.  H = 192, K = 5 only (OV_E_UNSUPPORTED otherwise).  Results agree with ov_wn_layer_f32
+ * to fp32 rounding: the transforms round where the direct form does not (~3-5x its error against float64, measured). */
+int ov_wn_layer_wino_f32(const ov_wn_layer_params* p, ov_stream_t stream);
+/* Columns of one workgroup tile of ov_wn_layer_wino_f32. */
+int ov_wn_layer_wino_tile(void);
+/* Floats written by ov_wn_wino_pack_f32 (0 unless rows = 384, cin = 192, K = 5). */
+size_t ov_wn_wino_pack_size(int rows, int cin, int K);
+/* Dense HOST w[rows][cin][5] -> U_p[row][g][ci] = sum_k G[p][k] w[row][ci][3g + k] (float64, rounded once to fp32) in
+ * 16x16x4 A-fragment order, [wave][4 input channels][row fragment][3][lane][4]: a lane's 12 floats are group 0 points
+ * 0..5, group 1 points 0..4 and a zero; one zero record group closes the stream (HOST dst). */
+int ov_wn_wino_pack_f32(const float* w, int rows, int cin, int K, float* dst);
+
 /* Framing for the linear spectrogram, reference openvoice/mel_processing.py:54-58 (reflect pad) and the framing
  * step of torch.stft at :61-72: hops[b][c][u] = ypad[hop*u + c] for u < U, with ypad the waveform [B][N]
  * reflect-padded by `pad` samples on each side (zero beyond that).  hops is (B, hop, U) with rows ld apart.
@@ -703,7 +721,7 @@ int ov_conv1d_wino_pack_f32(const float* w, int Cout, int Cin, int K, float* dst
  * was `reserved`; the struct grew by one pointer at its end).  2.06: ov_polyphase_fir_f32.  2.07: ov_conv1d_wino_f32 (+ _supported, _chunk,
  * _pack_size, _pack_f32).  2.08: ov_conv1d_wino_f32 instances for Cout % 32 == 0 at K = 11 (one 32-row fragment per
  * workgroup; ov_conv1d_wino_chunk(11, 32) = 2 where 2.07 returned 0).  2.09: ov_conv1d_wino_params.out_slope (the field that
- * was `reserved0`: same size and offset, 0 = none).  2.10: ov_frame_hops_windows_f32, ov_stitch_window_cores_f32.  2.11: ov_frame_hops_multi_f32.  2.12: ov_carry_rows_f32 (and, added later within 2.12 without a version change, ov_polyphase_fir_rows_f32 and ov_vad_frame_energy_f32, ov_vad_segments_i32, ov_vad_compact_f32, ov_rows_f32_to_cl_bf16, ov_cl_bf16_to_rows_f32: additive symbols, which the Python binding looks up by name when it loads the library).  The Python binding
+ * was `reserved0`: same size and offset, 0 = none).  2.10: ov_frame_hops_windows_f32, ov_stitch_window_cores_f32.  2.11: ov_frame_hops_multi_f32.  2.12: ov_carry_rows_f32 (and, added later within 2.12 without a version change, ov_polyphase_fir_rows_f32 and ov_vad_frame_energy_f32, ov_vad_segments_i32, ov_vad_compact_f32, ov_rows_f32_to_cl_bf16, ov_cl_bf16_to_rows_f32: additive symbols, which the Python binding looks up by name when it loads the library; likewise ov_wn_layer_wino_f32, ov_wn_layer_wino_tile, ov_wn_wino_pack_size and ov_wn_wino_pack_f32).  The Python binding
  * refuses a library older than the entry points it calls (openvoice_amd/_lib.py MIN_VERSION). */
 int ov_version(void);
 /* The version THIS header describes.  Parameter structs grow at their END in minor versions (2.04, 2.05, 2.07 did): a

@@ -137,6 +137,10 @@ SIGNATURES = {
     "ov_wn_pack_size": (ctypes.c_size_t, [_i, _i, _i]),
     "ov_wn_pack_f32": (ctypes.c_int, [_fp, _i, _i, _i, _fp]),
     "ov_wn_layer_tile": (ctypes.c_int, [_i, _i, _i]),
+    "ov_wn_layer_wino_f32": (ctypes.c_int, [ctypes.POINTER(WnLayerParams), _fp]),
+    "ov_wn_layer_wino_tile": (ctypes.c_int, []),
+    "ov_wn_wino_pack_size": (ctypes.c_size_t, [_i, _i, _i]),
+    "ov_wn_wino_pack_f32": (ctypes.c_int, [_fp, _i, _i, _i, _fp]),
     "ov_conv_post_tanh_f32": (ctypes.c_int, [_fp, _fp, _fp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                              ctypes.c_int, ctypes.c_float, _fp]),
     "ov_conv_post_tanh_limited_f32": (ctypes.c_int, [_fp, _fp, _fp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -255,7 +259,8 @@ _ops = None
 VALUE_FUNCS = {"ov_version", "ov_build_experiment", "ov_conv1d_pack_size", "ov_conv1d_pack_rows", "ov_wn_pack_size",
                "ov_conv1d_bf16_pack_size", "ov_resblock_pair_supported", "ov_wn_layer_supported", "ov_wn_layer_tile",
                "ov_resblock_pair_bf16_supported", "ov_resblock_pair2_bf16_supported", "ov_conv1d_split3_pack_size",
-               "ov_conv1d_split3_supported", "ov_conv1d_wino_supported", "ov_conv1d_wino_chunk", "ov_conv1d_wino_pack_size"}
+               "ov_conv1d_split3_supported", "ov_conv1d_wino_supported", "ov_conv1d_wino_chunk", "ov_conv1d_wino_pack_size",
+               "ov_wn_layer_wino_tile", "ov_wn_wino_pack_size"}
 
 
 def binding():

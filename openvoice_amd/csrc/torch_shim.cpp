@@ -262,11 +262,13 @@ void resblock_pair_f32(const OptTensor& x, const OptTensor& w1, const OptTensor&
 }
 
 // ip = [B, H, T, ld, K, first, last, width, bstride, cond_bstride, mask_bstride, cond_off, row_split]
-void wn_layer_f32(const OptTensor& x, const OptTensor& out, const OptTensor& skip, const OptTensor& w_in,
-                  const OptTensor& b_in, const OptTensor& cond, const OptTensor& w_rs, const OptTensor& b_rs,
-                  const OptTensor& mask, const OptTensor& dbg, const OptTensor& acts, at::IntArrayRef ip) {
-  TORCH_CHECK(ip.size() == 13, "openvoice_amd::wn_layer_f32: 13 integer parameters");
-  Ctx c{"wn_layer_f32", false};
+template <int (*FN)(const ov_wn_layer_params*, ov_stream_t)>
+void wn_layer_any(const char* op, const char* entry, const OptTensor& x, const OptTensor& out, const OptTensor& skip,
+                  const OptTensor& w_in, const OptTensor& b_in, const OptTensor& cond, const OptTensor& w_rs,
+                  const OptTensor& b_rs, const OptTensor& mask, const OptTensor& dbg, const OptTensor& acts,
+                  at::IntArrayRef ip) {
+  TORCH_CHECK(ip.size() == 13, "openvoice_amd::", op, ": 13 integer parameters");
+  Ctx c{op, false};
   ov_wn_layer_params p{};
   p.x = sptr<float>(x, c, 0); p.out = sptr<float>(out, c, 1); p.skip = sptr<float>(skip, c, 2);
   p.w_in = sptr<float>(w_in, c, 3); p.b_in = sptr<float>(b_in, c, 4); p.cond = sptr<float>(cond, c, 5, ip[11]);
@@ -277,7 +279,19 @@ void wn_layer_f32(const OptTensor& x, const OptTensor& out, const OptTensor& ski
   p.first = (int32_t)ip[5]; p.last = (int32_t)ip[6]; p.width = (int32_t)ip[7];
   p.bstride = ip[8]; p.cond_bstride = ip[9]; p.mask_bstride = ip[10]; p.row_split = (int32_t)ip[12];
   DeviceScope scope(c);
-  finish(ov_wn_layer_f32(&p, c.stream()), "ov_wn_layer_f32");
+  finish(FN(&p, c.stream()), entry);
+}
+void wn_layer_f32(const OptTensor& x, const OptTensor& out, const OptTensor& skip, const OptTensor& w_in,
+                  const OptTensor& b_in, const OptTensor& cond, const OptTensor& w_rs, const OptTensor& b_rs,
+                  const OptTensor& mask, const OptTensor& dbg, const OptTensor& acts, at::IntArrayRef ip) {
+  wn_layer_any<&ov_wn_layer_f32>("wn_layer_f32", "ov_wn_layer_f32", x, out, skip, w_in, b_in, cond, w_rs, b_rs, mask, dbg, acts, ip);
+}
+// the Winograd-domain form of the same layer: same arguments (w_in = ov_wn_wino_pack_f32)
+void wn_layer_wino_f32(const OptTensor& x, const OptTensor& out, const OptTensor& skip, const OptTensor& w_in,
+                       const OptTensor& b_in, const OptTensor& cond, const OptTensor& w_rs, const OptTensor& b_rs,
+                       const OptTensor& mask, const OptTensor& dbg, const OptTensor& acts, at::IntArrayRef ip) {
+  wn_layer_any<&ov_wn_layer_wino_f32>("wn_layer_wino_f32", "ov_wn_layer_wino_f32", x, out, skip, w_in, b_in, cond, w_rs, b_rs, mask, dbg,
+                                      acts, ip);
 }
 
 // ip = [B, L, Cin, Cout, K, dil, phase_s, bias_bstride, layout];  fp = [in_slope, scale, out_slope]
@@ -382,6 +396,8 @@ TORCH_LIBRARY(openvoice_amd, m) {
         "Tensor(b!)? dbg, Tensor? col_limit, int[] ip, float[] fp) -> ()", &resblock_pair_f32);
   m.def("wn_layer_f32(Tensor? x, Tensor(a!)? out, Tensor(b!)? skip, Tensor? w_in, Tensor? b_in, Tensor? cond, Tensor? w_rs, "
         "Tensor? b_rs, Tensor? mask, Tensor(c!)? dbg, Tensor(d!)? acts, int[] ip) -> ()", &wn_layer_f32);
+  m.def("wn_layer_wino_f32(Tensor? x, Tensor(a!)? out, Tensor(b!)? skip, Tensor? w_in, Tensor? b_in, Tensor? cond, Tensor? w_rs, "
+        "Tensor? b_rs, Tensor? mask, Tensor(c!)? dbg, Tensor(d!)? acts, int[] ip) -> ()", &wn_layer_wino_f32);
   m.def("conv1d_bf16cl(Tensor? x, Tensor? w, Tensor? bias, Tensor(a!)? out, Tensor? res, Tensor? add, Tensor(b!)? dbg, "
         "int[] ip, float[] fp) -> ()", &conv1d_bf16cl);
   m.def("resblock_pair_bf16cl(Tensor? x, Tensor? w1, Tensor? b1, Tensor? w2, Tensor? b2, Tensor(a!)? out, Tensor? add, "
@@ -430,6 +446,9 @@ TORCH_LIBRARY(openvoice_amd, m) {
   // ---- host helpers: weight packers (CPU tensors), sizes, capability queries
   bind_host<&ov_conv1d_pack_f32>(m, "conv1d_pack_f32");
   bind_host<&ov_wn_pack_f32>(m, "wn_pack_f32");
+  bind_host<&ov_wn_wino_pack_f32>(m, "wn_wino_pack_f32");
+  bind_value<&ov_wn_wino_pack_size>(m, "wn_wino_pack_size");
+  bind_value<&ov_wn_layer_wino_tile>(m, "wn_layer_wino_tile");
   bind_host<&ov_conv1d_bf16_pack>(m, "conv1d_bf16_pack");
   bind_host<&ov_conv1d_bf16_pack16>(m, "conv1d_bf16_pack16");
   bind_host<&ov_conv1d_split3_pack>(m, "conv1d_split3_pack");

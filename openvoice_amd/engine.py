@@ -418,21 +418,58 @@ def wn_pack(w_dense, device):
     return packed.to(device)
 
 
+# The Winograd-domain layer (csrc/wn_layer_wino.hip) deals (utterance, 128-column tile) items to one workgroup per CU, in
+# rounds of one item per CU, and a round costs what a full one costs (168 us per layer on 256 CUs); the direct layer
+# (csrc/wn_layer.hip) chooses tiles of 16 .. 128 columns that fill the CUs whatever the batch and costs 0.9-1.0 us per 128
+# columns.  Measured per layer at 861 frames (profiles/r07_wn_wino_sweep.txt), direct / Winograd in us: batch 1 (7 items)
+# 22 / 169, 2 (14) 36 / 168, 4 (28) 40 / 167, 8 (56) 68 / 168, 16 (112) 119 / 169, 24 (168) 178 / 171, 32 (224) 200 / 172,
+# 48 (336 = 2 rounds) 334 / 322, 64 (448) 391 / 324.  So the Winograd layer runs where its rounds are at least this full:
+# 168 of 256 items per round, the smallest fill measured at which it is ahead (batch 24 and batch 48).
+WN_WINO_MIN_ITEMS = 168
+WN_WINO_ROUND = 256          # items of a full round: the compute units of the chip the threshold was measured on
+
+
+def wn_wino_items(B, T):
+    """Work items of one ov_wn_layer_wino_f32 launch: (utterance, tile of ov_wn_layer_wino_tile() = 128 columns)."""
+    return B * ((T + 127) // 128)
+
+
+def wn_wino_policy(B, T):
+    """True where a (B, T) launch runs the Winograd-domain WaveNet layer: every round of WN_WINO_ROUND items it needs is, on
+    average, at least WN_WINO_MIN_ITEMS full."""
+    items = wn_wino_items(B, T)
+    rounds = (items + WN_WINO_ROUND - 1) // WN_WINO_ROUND
+    return items >= WN_WINO_MIN_ITEMS * rounds
+
+
+def wn_wino_pack(w_dense, device):
+    """Dense gate-ordered [2H][H][5] -> the transform-domain fragment stream of ``ov_wn_wino_pack_f32`` (device tensor)."""
+    w_dense = w_dense.detach().to(torch.float32).cpu().contiguous()
+    rows, cin, k = w_dense.shape
+    n = _lib.call("ov_wn_wino_pack_size", rows, cin, k)
+    assert n > 0, (rows, cin, k)
+    packed = torch.empty(n, dtype=torch.float32)
+    _lib.call("ov_wn_wino_pack_f32", w_dense, rows, cin, k, packed)
+    return packed.to(device)
+
+
 def launch_wn_layer(layer, x, out, skip, mask, B, T, ld, cond=None, cond_off=0, cond_bs=0, first=False, last=False,
-                    width=0, mask_bs=0, dbg=None, acts=None, row_split=0):
+                    width=0, mask_bs=0, dbg=None, acts=None, row_split=0, winograd=False):
     """One fused WaveNet layer (``ov_wn_layer_f32``): out = (x + res) * mask, skip (+)= rs; ``layer`` is a dict of
     the packed tensors built by ``_WaveNet``; x / out / skip are [B][H][ld].  ``acts`` ([B][H][ld] scratch) lets the
     launcher run one or two utterances as the row-split launch pair (bit-identical results); ``row_split`` 1 / 3 force
-    the fused / the split form."""
+    the fused / the split form.  ``winograd``: the same layer with its gate conv in the Winograd domain
+    (``ov_wn_layer_wino_f32``, ``layer["w_in_wino"]``; one launch, 128-column tiles)."""
+    entry, w_in = ("wn_layer_wino_f32", layer["w_in_wino"]) if winograd else ("wn_layer_f32", layer["w_in"])
     if _lib.use_torch_binding():
         H = layer["hidden"]
-        _lib.torch_op("wn_layer_f32", x, out, skip, layer["w_in"], layer["b_in"], cond, layer["w_rs"], layer["b_rs"],
+        _lib.torch_op(entry, x, out, skip, w_in, layer["b_in"], cond, layer["w_rs"], layer["b_rs"],
                       mask, dbg, acts, [B, H, T, ld, layer["K"], int(first), int(last), width, H * ld, cond_bs, mask_bs,
                                         cond_off, row_split])
         return
     p = _lib.WnLayerParams()
     p.x, p.out, p.skip = _ptr(x), _ptr(out), _ptr(skip)
-    p.w_in, p.b_in, p.w_rs, p.b_rs = _ptr(layer["w_in"]), _ptr(layer["b_in"]), _ptr(layer["w_rs"]), _ptr(layer["b_rs"])
+    p.w_in, p.b_in, p.w_rs, p.b_rs = _ptr(w_in), _ptr(layer["b_in"]), _ptr(layer["w_rs"]), _ptr(layer["b_rs"])
     p.cond = _ptr(cond, cond_off) if cond is not None else None
     p.mask = _ptr(mask)
     H = layer["hidden"]
@@ -442,7 +479,7 @@ def launch_wn_layer(layer, x, out, skip, mask, B, T, ld, cond=None, cond_off=0, 
     p.dbg = ctypes.c_void_p(dbg.data_ptr()) if dbg is not None else None
     p.acts = _ptr(acts) if acts is not None else None
     stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    _lib.check(_lib.load().ov_wn_layer_f32(ctypes.byref(p), stream), "ov_wn_layer_f32")
+    _lib.check(getattr(_lib.load(), "ov_" + entry)(ctypes.byref(p), stream), "ov_" + entry)
 
 
 class _WaveNet:
@@ -469,6 +506,7 @@ class _WaveNet:
                     w_rs = torch.cat([torch.zeros_like(w_rs), w_rs])
                     b_rs = torch.cat([torch.zeros_like(b_rs), b_rs])
                 self.fused_layers.append(dict(hidden=hidden, K=w_in.shape[2], w_in=wn_pack(w_in[forder], device),
+                                              w_in_wino=wn_wino_pack(w_in[forder], device),
                                               b_in=b_in[forder].contiguous().to(device), w_rs=wn_pack(w_rs, device),
                                               b_rs=b_rs.contiguous().to(device)))
         # cond_layer rows re-ordered per layer so its output is directly the gate's per-batch bias
@@ -755,10 +793,12 @@ class ConverterEngine:
         if self.fuse_wn and wn.fused:
             # one launch per layer; h ping-pongs between two buffers (a tile reads its neighbours' halo columns)
             src, dst = ws["h"], ws["h2"]
+            # gate conv in the Winograd domain where the launch fills the chip in whole rounds of (utterance, tile) items
+            winograd = self.use_winograd and wn_wino_policy(B, T)
             for i in range(wn.n_layers):
                 layer = wn.fused_layers[i]
                 args = dict(cond=cond, cond_off=2 * H * i, cond_bs=cbs, first=i == 0, last=i == wn.n_layers - 1,
-                            mask_bs=Tp, acts=ws["acts"], row_split=self.wn_row_split)
+                            mask_bs=Tp, acts=ws["acts"], row_split=self.wn_row_split, winograd=winograd)
                 if self.profile is None:
                     launch_wn_layer(layer, src, dst, ws["skip"], mask, B, T, Tp, **args)
                 else:
