@@ -369,6 +369,24 @@ int ov_vad_compact_f32(const float* pool, int64_t pool_len, const int64_t* recor
                        const int32_t* mask, const int64_t* offsets, const int64_t* out_bases, float* out,
                        int64_t out_len, ov_stream_t stream);
 
+/* ---- the join between the base-speaker TTS and the converter (csrc/clone.hip, openvoice_amd/clone.py) ---------------
+ * The device form of audio_numpy_concat (reference openvoice/api.py:56-63: `audio_segments += segment_data.reshape(-1)
+ * .tolist()` then `audio_segments += [0] * int((sr * 0.05) / speed)` per sentence, `np.array(...).astype(np.float32)`),
+ * for any number of utterances in one launch.  records is a DEVICE int64 [R][4] of (src_off, n, dst_off, gap), in
+ * elements relative to src / dst:
+ *   dst[dst_off + j] = src[src_off + j],  j < n;      dst[dst_off + n + j] = 0,  j < gap.
+ * The sources are rows of the padded TTS output [B, 1, ld] (src_off = b * ld, n = frames_b * hop); what lies beyond n
+ * in a row is never read.  n = 0 and gap = 0 are legal.  Records must not overlap in dst (the host plan,
+ * clone.join_plan, guarantees it); nothing outside the records' spans is written.  The kernel checks every record: one
+ * with a negative field, or that would read outside [0, src_elems) or write outside [0, dst_elems), copies nothing.
+ * Grid (chunk, record): 16-byte stores on the destination's own 16-byte grid, whatever dst_off is (the kernel peels up
+ * to three samples), 16-byte loads at the source's alignment, scalars at the edges; 64-bit indices.  max_span = the
+ * largest n + gap of the launch sizes the grid (a record with a longer span is still joined whole).  Host checks: null
+ * pointers, R in [1, 65535], extents > 0, max_span >= 0 (OV_E_BADARG); src and dst 4-byte aligned (OV_E_ALIGN).
+ * Additive to ABI 2.12: found by name, like the vad kernels. */
+int ov_join_segments_f32(const float* src, int64_t src_elems, const int64_t* records, int R, float* dst,
+                         int64_t dst_elems, int64_t max_span, ov_stream_t stream);
+
 /* Rate conversion at the audio boundary, reference openvoice/api.py:123,144 (``librosa.load(path, sr=...)`` = resampy's
  * kaiser_best band-limited sinc interpolation): a polyphase FIR over a mono waveform,
  *   y[t] = sum_{j < 2 taps} h[t % P][j] * x[(t * Q) / P - taps + 1 + j]        (x = 0 outside [0, n_in))
@@ -721,7 +739,7 @@ int ov_conv1d_wino_pack_f32(const float* w, int Cout, int Cin, int K, float* dst
  * was `reserved`; the struct grew by one pointer at its end).  2.06: ov_polyphase_fir_f32.  2.07: ov_conv1d_wino_f32 (+ _supported, _chunk,
  * _pack_size, _pack_f32).  2.08: ov_conv1d_wino_f32 instances for Cout % 32 == 0 at K = 11 (one 32-row fragment per
  * workgroup; ov_conv1d_wino_chunk(11, 32) = 2 where 2.07 returned 0).  2.09: ov_conv1d_wino_params.out_slope (the field that
- * was `reserved0`: same size and offset, 0 = none).  2.10: ov_frame_hops_windows_f32, ov_stitch_window_cores_f32.  2.11: ov_frame_hops_multi_f32.  2.12: ov_carry_rows_f32 (and, added later within 2.12 without a version change, ov_polyphase_fir_rows_f32 and ov_vad_frame_energy_f32, ov_vad_segments_i32, ov_vad_compact_f32, ov_rows_f32_to_cl_bf16, ov_cl_bf16_to_rows_f32: additive symbols, which the Python binding looks up by name when it loads the library; likewise ov_wn_layer_wino_f32, ov_wn_layer_wino_tile, ov_wn_wino_pack_size and ov_wn_wino_pack_f32).  The Python binding
+ * was `reserved0`: same size and offset, 0 = none).  2.10: ov_frame_hops_windows_f32, ov_stitch_window_cores_f32.  2.11: ov_frame_hops_multi_f32.  2.12: ov_carry_rows_f32 (and, added later within 2.12 without a version change, ov_polyphase_fir_rows_f32 and ov_vad_frame_energy_f32, ov_vad_segments_i32, ov_vad_compact_f32, ov_rows_f32_to_cl_bf16, ov_cl_bf16_to_rows_f32: additive symbols, which the Python binding looks up by name when it loads the library; likewise ov_wn_layer_wino_f32, ov_wn_layer_wino_tile, ov_wn_wino_pack_size and ov_wn_wino_pack_f32, and ov_join_segments_f32).  The Python binding
  * refuses a library older than the entry points it calls (openvoice_amd/_lib.py MIN_VERSION). */
 int ov_version(void);
 /* The version THIS header describes.  Parameter structs grow at their END in minor versions (2.04, 2.05, 2.07 did): a

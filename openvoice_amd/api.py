@@ -103,40 +103,81 @@ class BaseSpeakerTTS(OpenVoiceBaseClass):
         print(" > ===========================")
         return texts
 
+    @staticmethod
+    def _batch_noise(noises, width=None):
+        """Per-sentence noise tensors ``[C, >= own length]`` -> one ``[B, C, W]`` batch, each cut / zero-padded to ``W``
+        columns (``width``, or the widest of them)."""
+        noises = [torch.as_tensor(z, dtype=torch.float32) for z in noises]
+        W = max(z.shape[-1] for z in noises) if width is None else int(width)
+        out = torch.zeros(len(noises), noises[0].shape[-2], W, dtype=torch.float32, device=noises[0].device)
+        for i, z in enumerate(noises):
+            w = min(W, z.shape[-1])
+            out[i, :, :w] = z.reshape(-1, z.shape[-1])[:, :w].to(out.device)
+        return out
+
     @torch.no_grad()
-    def tts_from_ids(self, id_sequences, speaker_id, speed=1.0, batched=False, noise_scale=0.667,
-                     noise_scale_w=0.6):
-        """Synthesize already-tokenised sentences (symbol ids, blanks interspersed by the caller if the
-        config asks for it).  ``batched=False`` runs one ``infer`` per sentence exactly as the reference loop
-        (api.py:78-94); ``batched=True`` pads them into one batch (one pass over the GPU; because the
-        generator is unmasked, the last ~13 frames of the shorter items then differ slightly from a
-        per-sentence run).  Returns a list of float32 numpy waveforms."""
+    def infer_padded(self, id_sequences, speaker_id, speed=1.0, noise_scale=0.667, noise_scale_w=0.6, noise_w=None,
+                     noise_z=None):
+        """One padded ``infer(..., skip_padding=True)`` over already-tokenised sentences, results left on the device:
+        ``(o [B, 1, ld], frames [B] int64)`` -- row b holds ``frames[b] * hop`` samples, what lies beyond them in the
+        row is padding.  ``noise_w`` / ``noise_z``: None or one ``[2, Tx_b]`` / ``[192, >= Ty_b]`` per sentence (the
+        explicit forms of ``infer``'s two draws; in the batch each is zero-padded to the widest).  This is the launch
+        sequence behind ``tts_from_ids(batched=True)`` and ``clone.VoiceCloner``."""
         device = self.device
         seqs = [torch.as_tensor(s, dtype=torch.long).reshape(-1) for s in id_sequences]
-        hop = self.hps.data.hop_length
-        if not batched:
-            out = []
-            for s in seqs:
-                o = self.model.infer(s[None].to(device), torch.LongTensor([s.numel()]).to(device),
-                                     sid=torch.LongTensor([speaker_id]).to(device), noise_scale=noise_scale,
-                                     noise_scale_w=noise_scale_w, length_scale=1.0 / speed)[0]
-                out.append(o[0, 0].data.cpu().float().numpy())
-            return out
+        for name, nz in (("noise_w", noise_w), ("noise_z", noise_z)):
+            if nz is not None and len(nz) != len(seqs):
+                raise ValueError(f"{name}: one tensor per sentence ({len(seqs)}), got {len(nz)}")
         lengths = torch.tensor([s.numel() for s in seqs], dtype=torch.long)
         x = torch.zeros(len(seqs), int(lengths.max()), dtype=torch.long)
         for i, s in enumerate(seqs):
             x[i, :s.numel()] = s
         sid = torch.full((len(seqs),), int(speaker_id), dtype=torch.long)
+        if noise_w is not None:
+            noise_w = self._batch_noise(noise_w, x.shape[1])
+        if noise_z is not None:
+            noise_z = self._batch_noise(noise_z)
         # padded batch: the generator computes length + margin (16-20) frames per sentence, not the longest one's (the
         # samples returned below are bit-identical either way)
         o, _, y_mask, _ = self.model.infer(x.to(device), lengths.to(device), sid=sid.to(device), noise_scale=noise_scale,
-                                           noise_scale_w=noise_scale_w, length_scale=1.0 / speed, skip_padding=True)
-        frames = y_mask[:, 0].sum(1).long().cpu().tolist()
-        o = o[:, 0].data.cpu().float().numpy()
-        return [o[i, :frames[i] * hop] for i in range(len(seqs))]
+                                           noise_scale_w=noise_scale_w, length_scale=1.0 / speed, noise_w=noise_w,
+                                           noise_z=noise_z, skip_padding=True)
+        return o, y_mask[:, 0].sum(1).long()
 
-    def tts(self, text, output_path, speaker, language="English", speed=1.0, batched=False):
-        """reference: openvoice/api.py:73-98."""
+    @torch.no_grad()
+    def tts_from_ids(self, id_sequences, speaker_id, speed=1.0, batched=False, noise_scale=0.667,
+                     noise_scale_w=0.6, noise_w=None, noise_z=None):
+        """Synthesize already-tokenised sentences (symbol ids, blanks interspersed by the caller if the
+        config asks for it).  ``batched=False`` runs one ``infer`` per sentence exactly as the reference loop
+        (api.py:78-94); ``batched=True`` pads them into one batch (one pass over the GPU; because the
+        generator is unmasked, the last ~13 frames of the shorter items then differ slightly from a
+        per-sentence run).  ``noise_w`` / ``noise_z``: None (drawn on the device) or lists with one ``[2, Tx]`` /
+        ``[192, >= Ty]`` tensor per sentence, passed on to ``infer``.  Returns a list of float32 numpy waveforms."""
+        device = self.device
+        hop = self.hps.data.hop_length
+        if not batched:
+            seqs = [torch.as_tensor(s, dtype=torch.long).reshape(-1) for s in id_sequences]
+            for name, nz in (("noise_w", noise_w), ("noise_z", noise_z)):
+                if nz is not None and len(nz) != len(seqs):
+                    raise ValueError(f"{name}: one tensor per sentence ({len(seqs)}), got {len(nz)}")
+            row = lambda nz, i: None if nz is None else torch.as_tensor(nz[i], dtype=torch.float32)[None]
+            out = []
+            for i, s in enumerate(seqs):
+                o = self.model.infer(s[None].to(device), torch.LongTensor([s.numel()]).to(device),
+                                     sid=torch.LongTensor([speaker_id]).to(device), noise_scale=noise_scale,
+                                     noise_scale_w=noise_scale_w, length_scale=1.0 / speed, noise_w=row(noise_w, i),
+                                     noise_z=row(noise_z, i))[0]
+                out.append(o[0, 0].data.cpu().float().numpy())
+            return out
+        o, frames = self.infer_padded(id_sequences, speaker_id, speed=speed, noise_scale=noise_scale,
+                                      noise_scale_w=noise_scale_w, noise_w=noise_w, noise_z=noise_z)
+        frames = frames.cpu().tolist()
+        o = o[:, 0].data.cpu().float().numpy()
+        return [o[i, :frames[i] * hop] for i in range(len(frames))]
+
+    def text_to_ids(self, text, language="English"):
+        """The text half of ``tts`` (reference: openvoice/api.py:73-82): sentence pieces, language marks, ``get_text``
+        -> one id tensor per sentence."""
         mark = self.language_marks.get(language.lower(), None)
         assert mark is not None, f"language {language} is not supported"
         texts = self.split_sentences_into_pieces(text, mark)
@@ -145,6 +186,11 @@ class BaseSpeakerTTS(OpenVoiceBaseClass):
             t = re.sub(r"([a-z])([A-Z])", r"\1 \2", t)
             t = f"[{mark}]{t}[{mark}]"
             ids.append(self.get_text(t, self.hps, False))
+        return ids
+
+    def tts(self, text, output_path, speaker, language="English", speed=1.0, batched=False):
+        """reference: openvoice/api.py:73-98."""
+        ids = self.text_to_ids(text, language)
         audio_list = self.tts_from_ids(ids, self.hps.speakers[speaker], speed=speed, batched=batched)
         audio = self.audio_numpy_concat(audio_list, sr=self.hps.data.sampling_rate, speed=speed)
         if output_path is None:
