@@ -1,6 +1,8 @@
 """Fused bf16 ResBlock1 pair (ov_resblock_pair_bf16cl, csrc/conv1d_bf16_pair.hip) against
   * the two ov_conv1d_bf16cl launches it replaces -- bit for bit (the intermediate is rounded to bf16 at the same point), and
   * fp32 PyTorch on the same bf16-rounded operands, intermediate rounded to bf16 like the kernels do (bound 1e-2 of scale),
+  * the float64 mirror of the same expression, element by element: half a bf16 ulp + S * absacc + the allowance for
+    intermediates that may round the other way (oracle/bf16_ref.py),
 for every (C, K, dilation), ragged lengths, utterance boundaries inside a run, runs starting mid-utterance, the MRF
 operands.  reference: openvoice/modules.py:296-306."""
 import pytest
@@ -11,6 +13,7 @@ pytestmark = pytest.mark.gpu
 
 from openvoice_amd import _lib  # noqa: E402
 from openvoice_amd.bf16 import PackedConvBf16, launch_conv_bf16, launch_pair_bf16, pair_bf16_supported  # noqa: E402
+from oracle import bf16_ref as R  # noqa: E402
 
 DEV = "cuda:0"
 
@@ -47,10 +50,13 @@ def _two_launches(c1, c2, x, add=None, scale=1.0):
     return out
 
 
-def _check(out, ref):
+def _check(out, ref, x, w1, b1, w2, b2, d, add=None, scale=1.0, what=""):
     assert torch.isfinite(out.float()).all(), "unwritten (NaN-poisoned) output elements"
     err = (out.float().cpu() - ref).abs().max().item()
     assert err <= 1e-2 * max(1.0, ref.abs().max().item()), err
+    ref64, absacc, inter = R.pair1(x, w1, b1, w2, b2, d, add=add, scale=scale)
+    R.assert_within(out, ref64, R.limit(ref64, absacc, R.flip(inter)),
+                    f"{what} C={x.shape[2]} k={w1.shape[2]} d={d} L={x.shape[1]}", "pair")
 
 
 @pytest.mark.parametrize("c", [32, 64])
@@ -64,7 +70,7 @@ def test_pair_bf16_matches_two_launch_path_and_reference(c, k, d):
     xd = x.to(DEV, torch.bfloat16)
     out = torch.full_like(xd, float("nan"))
     launch_pair_bf16(c1, c2, xd, out)
-    _check(out, _reference(x, w1, b1, w2, b2, k, d))
+    _check(out, _reference(x, w1, b1, w2, b2, k, d), x, w1, b1, w2, b2, d)
     assert torch.equal(out, _two_launches(c1, c2, xd))
 
 
@@ -77,7 +83,7 @@ def test_pair_bf16_lengths_around_the_step_height(c, k, d, L):
     xd = x.to(DEV, torch.bfloat16)
     out = torch.full_like(xd, float("nan"))
     launch_pair_bf16(c1, c2, xd, out)
-    _check(out, _reference(x, w1, b1, w2, b2, k, d))
+    _check(out, _reference(x, w1, b1, w2, b2, k, d), x, w1, b1, w2, b2, d)
     assert torch.equal(out, _two_launches(c1, c2, xd))
 
 
@@ -101,7 +107,8 @@ def test_pair_bf16_mrf_sum_and_scale_in_place_on_the_accumulator(c, k, d):
     xd, accd = x.to(DEV, torch.bfloat16), acc.to(DEV, torch.bfloat16)
     want = _two_launches(c1, c2, xd, add=accd, scale=1.0 / 3.0)
     launch_pair_bf16(c1, c2, xd, accd, add=accd, scale=1.0 / 3.0)
-    _check(accd, _reference(x, w1, b1, w2, b2, k, d, add=acc, scale=1.0 / 3.0))
+    _check(accd, _reference(x, w1, b1, w2, b2, k, d, add=acc, scale=1.0 / 3.0), x, w1, b1, w2, b2, d, add=acc,
+           scale=1.0 / 3.0, what="MRF")
     assert torch.equal(accd, want)
 
 
@@ -131,8 +138,15 @@ def test_activated_store_two_launch_path_agrees_with_the_fused_pair_within_bf16_
     launch_conv_bf16(c1, xd, t, in_slope=0.1, out_slope=0.1)          # the engine's sequence (bf16.py decode)
     launch_conv_bf16(c2, t, two, in_slope=1.0, res=xd)
     ref = _reference(x, w1, b1, w2, b2, k, d)
-    _check(two, ref)
-    _check(fused, ref)
+    _check(fused, ref, x, w1, b1, w2, b2, d, what="fused")
+    # the two-launch path rounds t once (bf16(lrelu(v))): against the fused form's reference it keeps the global bound
+    # and the documented cross-path bound below; element by element each of its launches is held to its own mirror
+    assert torch.isfinite(two.float()).all()
+    assert (two.float().cpu() - ref).abs().max().item() <= 1e-2 * max(1.0, ref.abs().max().item())
+    t64, abs1 = R.conv_single(x, w1, b1, dil=d, in_slope=0.1, out_slope=0.1)
+    R.assert_within(t, t64, R.limit(t64, abs1), f"activated t C={c} k={k} d={d}", "single conv")
+    o64, abs2 = R.conv_single(t.float().cpu(), w2, b2, res=x)
+    R.assert_within(two, o64, R.limit(o64, abs2), f"conv2 on the stored t C={c} k={k} d={d}", "single conv")
     scale = max(1.0, ref.abs().max().item())
     diff = (two.float() - fused.float()).abs().max().item()
     assert diff <= 2 ** -6 * scale, diff          # two bf16 ulps of the output scale

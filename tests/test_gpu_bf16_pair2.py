@@ -1,6 +1,8 @@
 """Second-generation fused bf16 ResBlock1 pair (ov_resblock_pair2_bf16cl, csrc/conv1d_bf16_pair2.hip: C = 32 / 64 / 128,
 activations stored ACTIVATED in HBM) against fp32 PyTorch on the same bf16-rounded operands with every rounding of the
-kernel mirrored (bound: 1e-2 of scale, i.e. output rounding): every (C, K, dilation), lengths around the step height,
+kernel mirrored (bound: 1e-2 of scale, i.e. output rounding) and, element by element, the float64 mirror of the same
+expression (oracle/bf16_ref.py: half a bf16 ulp + S * absacc + the allowance for intermediates that may round the other
+way): every (C, K, dilation), lengths around the step height,
 utterance boundaries inside a run, runs starting mid-utterance (forced workgroup counts), the MRF operands, the output
 activation.  reference: openvoice/modules.py:296-306, models.py:280-286."""
 import pytest
@@ -10,6 +12,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from openvoice_amd.bf16 import PackedConvBf16, launch_pair2_bf16, pair2_bf16_supported  # noqa: E402
+from oracle import bf16_ref as R  # noqa: E402
 
 DEV = "cuda:0"
 SLOPE = 0.1
@@ -43,10 +46,13 @@ def _reference(xa, w1, b1, w2, b2, k, d, add=None, scale=1.0, out_slope=1.0):
     return y.transpose(1, 2)
 
 
-def _check(out, ref):
+def _check(out, ref, xa, w1, b1, w2, b2, d, what="", **kw):
     assert torch.isfinite(out.float()).all(), "unwritten (NaN-poisoned) output elements"
     err = (out.float().cpu() - ref).abs().max().item()
     assert err <= 1e-2 * max(1.0, ref.abs().max().item()), err
+    ref64, absacc, inter = R.pair2(xa, w1, b1, w2, b2, d, slope=SLOPE, **kw)
+    R.assert_within(out, ref64, R.limit(ref64, absacc, R.flip(inter)),
+                    f"{what} C={xa.shape[2]} k={w1.shape[2]} d={d} L={xa.shape[1]}", "pair2")
 
 
 def _act_input(B, L, c, seed):
@@ -63,7 +69,7 @@ def test_pair2_matches_reference(c, k, d):
     xd = xa.to(DEV, torch.bfloat16)
     out = torch.full_like(xd, float("nan"))
     launch_pair2_bf16(c1, c2, xd, out)
-    _check(out, _reference(xa, w1, b1, w2, b2, k, d))
+    _check(out, _reference(xa, w1, b1, w2, b2, k, d), xa, w1, b1, w2, b2, d)
 
 
 @pytest.mark.parametrize("L", [1, 5, 127, 128, 129, 255, 256, 257, 383, 384, 511, 512, 513, 600, 1030])
@@ -75,7 +81,7 @@ def test_pair2_lengths_around_the_step_height(c, k, d, L):
     xd = xa.to(DEV, torch.bfloat16)
     out = torch.full_like(xd, float("nan"))
     launch_pair2_bf16(c1, c2, xd, out)
-    _check(out, _reference(xa, w1, b1, w2, b2, k, d))
+    _check(out, _reference(xa, w1, b1, w2, b2, k, d), xa, w1, b1, w2, b2, d)
 
 
 @pytest.mark.parametrize("nwg", [1, 2, 3, 5, 7, 16])
@@ -89,7 +95,7 @@ def test_pair2_runs_that_start_mid_utterance_and_span_utterances(c, k, d, nwg):
     xd = xa.to(DEV, torch.bfloat16)
     out = torch.full_like(xd, float("nan"))
     launch_pair2_bf16(c1, c2, xd, out, nwg=nwg)
-    _check(out, _reference(xa, w1, b1, w2, b2, k, d))
+    _check(out, _reference(xa, w1, b1, w2, b2, k, d), xa, w1, b1, w2, b2, d)
     ref = out.clone()
     out.fill_(float("nan"))
     launch_pair2_bf16(c1, c2, xd, out)                 # the default workgroup count: same rows, same arithmetic
@@ -105,7 +111,8 @@ def test_pair2_mrf_operands_and_output_activation(c, k, d):
     xd, addd = xa.to(DEV, torch.bfloat16), add.to(DEV, torch.bfloat16)
     out = torch.full_like(xd, float("nan"))
     launch_pair2_bf16(c1, c2, xd, out, add=addd, scale=1.0 / 3.0)
-    _check(out, _reference(xa, w1, b1, w2, b2, k, d, add=add, scale=1.0 / 3.0))
+    _check(out, _reference(xa, w1, b1, w2, b2, k, d, add=add, scale=1.0 / 3.0), xa, w1, b1, w2, b2, d, what="sum",
+           add=add, scale=1.0 / 3.0)
     # `add` may alias `out` (the running sum is updated in place by the last pair of a chain)
     acc = addd.clone()
     launch_pair2_bf16(c1, c2, xd, acc, add=acc, scale=1.0 / 3.0)
@@ -113,11 +120,13 @@ def test_pair2_mrf_operands_and_output_activation(c, k, d):
     # an intermediate pair stores its output activated for the next one
     out2 = torch.full_like(xd, float("nan"))
     launch_pair2_bf16(c1, c2, xd, out2, out_slope=SLOPE)
-    _check(out2, _reference(xa, w1, b1, w2, b2, k, d, out_slope=SLOPE))
+    _check(out2, _reference(xa, w1, b1, w2, b2, k, d, out_slope=SLOPE), xa, w1, b1, w2, b2, d, what="activated",
+           out_slope=SLOPE)
     # the MRF mean is stored activated for the next stage's ConvTranspose (openvoice/models.py:278-279)
     out3 = torch.full_like(xd, float("nan"))
     launch_pair2_bf16(c1, c2, xd, out3, add=addd, scale=1.0 / 3.0, out_slope=SLOPE)
-    _check(out3, _reference(xa, w1, b1, w2, b2, k, d, add=add, scale=1.0 / 3.0, out_slope=SLOPE))
+    _check(out3, _reference(xa, w1, b1, w2, b2, k, d, add=add, scale=1.0 / 3.0, out_slope=SLOPE), xa, w1, b1, w2, b2, d,
+           what="activated mean", add=add, scale=1.0 / 3.0, out_slope=SLOPE)
 
 
 def test_pair2_chain_of_three_pairs_matches_raw_residual_chain():
