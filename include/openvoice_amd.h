@@ -494,7 +494,7 @@ int ov_layernorm_ch_f32(const float* x, const float* res, const float* gamma, co
 /* Multi-head self-attention with windowed relative-position keys and values (attentions.py:264-329):
  * q, k, v, out are (B, n_heads*dk, T); emb_k / emb_v are the shared [2*window+1][dk] tables; scores of masked
  * (query, key) pairs are set to -1e4 before the softmax as in the reference.  q, k, v share the batch stride
- * qkv_bstride (they may be row blocks of one fused projection output).  dk must be 96; T <= 1199. */
+ * qkv_bstride (they may be row blocks of one fused projection output).  dk must be 96; T <= 1172. */
 int ov_rel_attention_f32(const float* q, const float* k, const float* v, const float* emb_k, const float* emb_v,
                          const float* mask, float* out, int64_t qkv_bstride, int64_t out_bstride, int B, int n_heads,
                          int dk, int T, int ld, int window, ov_stream_t stream);

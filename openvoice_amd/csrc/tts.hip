@@ -482,7 +482,7 @@ int ov_rel_attention_f32(const float* q, const float* k, const float* v, const f
   if (dk != 96) return OV_E_UNSUPPORTED;                   // hidden 192 / 2 heads (models.py:39-45)
   if (8 * (2 * window + 1) > 256) return OV_E_UNSUPPORTED;
   const size_t smem = (size_t)(8 * 96 + 96 * 65 + 8 * (size_t)T) * sizeof(float);
-  if (smem > 64 * 1024) return OV_E_UNSUPPORTED;           // T <= 1199 tokens per utterance
+  if (smem > 64 * 1024) return OV_E_UNSUPPORTED;           // T <= 1172 tokens per utterance
   dim3 grid((T + 7) / 8, n_heads, B);
   if (qkv_bstride < (int64_t)n_heads * dk * ld || out_bstride < (int64_t)n_heads * dk * ld) return OV_E_BADARG;
   hipLaunchKernelGGL(rel_attention_kernel<96>, grid, dim3(256), smem, static_cast<hipStream_t>(stream), q, k, v, emb_k,

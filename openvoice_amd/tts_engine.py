@@ -25,6 +25,16 @@ from .engine import ConverterEngine, PackedConv, on_own_device, padded_frames
 from .params import ATTN_WINDOW, SDP_DDS_LAYERS, SDP_FLOWS, SDP_KERNEL, SDP_NUM_BINS, SDP_TAIL_BOUND
 
 LN_EPS = 1e-5   # modules.LayerNorm / attentions.LayerNorm default
+# ov_rel_attention_f32 keeps 8 query rows of scores against all Tx keys in LDS next to its q and k / v tiles:
+# (8 * 96 + 96 * 65 + 8 * Tx) * 4 bytes <= 64 KiB (csrc/tts.hip), so Tx <= 1172 tokens per utterance.
+MAX_TOKENS = (64 * 1024 // 4 - 8 * 96 - 96 * 65) // 8
+
+
+def check_token_count(Tx):
+    """Refuse a token axis that the attention kernel cannot hold, in words instead of its OV_E_UNSUPPORTED."""
+    if Tx > MAX_TOKENS:
+        raise ValueError(f"infer: token axis of {Tx} tokens, but the text encoder's attention kernel holds at most "
+                         f"{MAX_TOKENS}; split the text into shorter pieces (BaseSpeakerTTS splits by sentence)")
 
 
 def _pad_rows(w, b, rows):
@@ -139,6 +149,7 @@ class TtsEngine:
         utterance of a padded batch
         (valid samples bit-identical, the padded tail of ``o`` zero; ``ConverterEngine.voice_conversion``)."""
         dev = self.device
+        check_token_count(tokens.shape[-1])
         tokens = tokens.to(dev, torch.int64).contiguous()
         lengths = lengths.to(dev, torch.int64).contiguous()
         sid = sid.to(dev, torch.int64).reshape(-1)

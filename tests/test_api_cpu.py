@@ -62,6 +62,19 @@ def test_v1_tts_model_owns_the_reference_schema(synth_tts_sd):
         conv.infer(torch.zeros(1, 3, dtype=torch.long), torch.tensor([3]))
 
 
+def test_tts_token_limit_is_the_attention_kernels_and_is_named():
+    """The check ``TtsEngine.infer`` makes before its first launch (the engine itself needs a device:
+    tests/test_gpu_tts_kernels.py runs ``infer`` into it).  The limit is the launcher's LDS arithmetic in csrc/tts.hip:
+    (8 * 96 + 96 * 65 + 8 * Tx) * 4 bytes <= 64 KiB."""
+    from openvoice_amd.tts_engine import MAX_TOKENS, check_token_count
+    lds = lambda Tx: (8 * 96 + 96 * 65 + 8 * Tx) * 4
+    assert MAX_TOKENS == 1172 and lds(MAX_TOKENS) <= 64 * 1024 < lds(MAX_TOKENS + 1)
+    check_token_count(1)
+    check_token_count(MAX_TOKENS)
+    with pytest.raises(ValueError, match="1173 tokens.*at most 1172"):
+        check_token_count(MAX_TOKENS + 1)
+
+
 def test_state_dict_round_trip_strict(synth_sd):
     from openvoice_amd.models import SynthesizerTrn
     model = SynthesizerTrn(0, 513, n_speakers=0, **utils.CONVERTER_MODEL_CONFIG)
