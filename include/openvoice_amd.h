@@ -387,6 +387,31 @@ int ov_vad_compact_f32(const float* pool, int64_t pool_len, const int64_t* recor
 int ov_join_segments_f32(const float* src, int64_t src_elems, const int64_t* records, int R, float* dst,
                          int64_t dst_elems, int64_t max_span, ov_stream_t stream);
 
+/* ---- counter-based Gaussian noise (csrc/noise.hip, openvoice_amd/noise.py) -------------------------------------------
+ * Stands in for the reference's torch.randn / randn_like draws (openvoice/models.py:220, :476, :486) where a caller
+ * asks for `seed=`: the value at (seed, stream, purpose, channel c, frame t) is a pure function of those five numbers,
+ * 0 <= seed < 2^63, 0 <= stream, purpose, c < 2^32, 0 <= t < 2^34:
+ *   (r0, r1, r2, r3) = Philox4x32-10(counter = (t / 4, c, stream, purpose), key = (seed & 0xffffffff, seed >> 32)),
+ *     the standard function: multipliers 0xD2511F53 (on word 0) and 0xCD9E8D57 (on word 2), key increments 0x9E3779B9
+ *     and 0xBB67AE85, one round (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)), ten rounds;
+ *   j = t % 4: pair j / 2 takes (ra, rb) = (r0, r1) or (r2, r3);  u1 = ((ra >> 8) + 0.5) 2^-24,  u2 = (rb >> 8) 2^-24;
+ *   n = sqrt(-2 ln u1) cos(2 pi u2) for even j, sqrt(-2 ln u1) sin(2 pi u2) for odd j;  |n| <= sqrt(50 ln 2) = 5.887.
+ * Purposes in use: 0 the converter's posterior noise, 1 the TTS noise_w (frames = token positions), 2 the TTS noise_z.
+ * records is a DEVICE int64 [R][7] of (seed, stream, purpose, f0, nf, dst_off, dst_ld), offsets in elements of dst:
+ *   dst[dst_off + c * dst_ld + i] = n(seed, stream, purpose, c, f0 + i),  c < C, i < nf;
+ * nothing else is written (pad columns and what lies between slabs keep their contents).  One thread owns one Philox
+ * block (four consecutive frames of one channel) and computes its four values before it knows how they are stored: a
+ * block wholly inside the slab at a 16-byte aligned destination is one vector store, everything else goes element by
+ * element, so a value does not depend on f0's phase, on alignment, on R or on its neighbours.  The logarithm of
+ * u1 >= 1/2 is taken as log1p(-(1 - u1)) (1 - u1 is exact in fp32 there, u1 is not) and the angle as sin / cos of 2 u2
+ * half turns (exact argument).  max_frames = the largest nf of the launch sizes the grid only.  Host checks: null
+ * pointers, R outside [1, 65535], C <= 0, dst_elems <= 0, max_frames < 0 (OV_E_BADARG); dst 4-byte aligned
+ * (OV_E_ALIGN).  The kernel checks every record: one with a negative field, stream or purpose >= 2^32, f0 + nf > 2^34,
+ * nf > dst_ld, or a slab that leaves [0, dst_elems) writes nothing.  Additive to ABI 2.12: found by name, like the vad
+ * and join kernels. */
+int ov_normal_philox_f32(const int64_t* records, int R, int C, float* dst, int64_t dst_elems, int64_t max_frames,
+                         ov_stream_t stream);
+
 /* Rate conversion at the audio boundary, reference openvoice/api.py:123,144 (``librosa.load(path, sr=...)`` = resampy's
  * kaiser_best band-limited sinc interpolation): a polyphase FIR over a mono waveform,
  *   y[t] = sum_{j < 2 taps} h[t % P][j] * x[(t * Q) / P - taps + 1 + j]        (x = 0 outside [0, n_in))

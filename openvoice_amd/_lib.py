@@ -188,6 +188,7 @@ SIGNATURES = {
                                            _fp]),
     "ov_vad_compact_f32": (ctypes.c_int, [_fp, _i64, _fp, _i, _i, _i, _fp, _fp, _fp, _fp, _i64, _fp]),
     "ov_join_segments_f32": (ctypes.c_int, [_fp, _i64, _fp, _i, _fp, _i64, _i64, _fp]),
+    "ov_normal_philox_f32": (ctypes.c_int, [_fp, _i, _i, _fp, _i64, _i64, _fp]),
     "ov_embed_f32": (ctypes.c_int, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, ctypes.c_float, _fp]),
     "ov_layernorm_ch_f32": (ctypes.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, ctypes.c_float, _i, _fp]),
     "ov_rel_attention_f32": (ctypes.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i64, _i64, _i, _i, _i, _i, _i, _i,

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import audio_io, longform, rates, utils
+from . import noise as noise_mod
 from .mel_processing import spectrogram_torch
 from .models import SynthesizerTrn
 
@@ -117,14 +118,19 @@ class BaseSpeakerTTS(OpenVoiceBaseClass):
 
     @torch.no_grad()
     def infer_padded(self, id_sequences, speaker_id, speed=1.0, noise_scale=0.667, noise_scale_w=0.6, noise_w=None,
-                     noise_z=None):
+                     noise_z=None, *, seed=None):
         """One padded ``infer(..., skip_padding=True)`` over already-tokenised sentences, results left on the device:
         ``(o [B, 1, ld], frames [B] int64)`` -- row b holds ``frames[b] * hop`` samples, what lies beyond them in the
         row is padding.  ``noise_w`` / ``noise_z``: None or one ``[2, Tx_b]`` / ``[192, >= Ty_b]`` per sentence (the
-        explicit forms of ``infer``'s two draws; in the batch each is zero-padded to the widest).  This is the launch
+        explicit forms of ``infer``'s two draws; in the batch each is zero-padded to the widest); ``seed`` (instead of
+        them): counter-based noise (``noise.py``), an int ``s`` giving sentence ``i`` the stream ``(s, i)``, or a list
+        with one seed / pair per sentence.  This is the launch
         sequence behind ``tts_from_ids(batched=True)`` and ``clone.VoiceCloner``."""
+        noise_mod.exclusive(seed, noise_w=noise_w, noise_z=noise_z)
         device = self.device
         seqs = [torch.as_tensor(s, dtype=torch.long).reshape(-1) for s in id_sequences]
+        if seed is not None:
+            seed = noise_mod.per_item(seed, len(seqs))
         for name, nz in (("noise_w", noise_w), ("noise_z", noise_z)):
             if nz is not None and len(nz) != len(seqs):
                 raise ValueError(f"{name}: one tensor per sentence ({len(seqs)}), got {len(nz)}")
@@ -141,22 +147,27 @@ class BaseSpeakerTTS(OpenVoiceBaseClass):
         # samples returned below are bit-identical either way)
         o, _, y_mask, _ = self.model.infer(x.to(device), lengths.to(device), sid=sid.to(device), noise_scale=noise_scale,
                                            noise_scale_w=noise_scale_w, length_scale=1.0 / speed, noise_w=noise_w,
-                                           noise_z=noise_z, skip_padding=True)
+                                           noise_z=noise_z, skip_padding=True, **noise_mod.kw(seed))
         return o, y_mask[:, 0].sum(1).long()
 
     @torch.no_grad()
     def tts_from_ids(self, id_sequences, speaker_id, speed=1.0, batched=False, noise_scale=0.667,
-                     noise_scale_w=0.6, noise_w=None, noise_z=None):
+                     noise_scale_w=0.6, noise_w=None, noise_z=None, *, seed=None):
         """Synthesize already-tokenised sentences (symbol ids, blanks interspersed by the caller if the
         config asks for it).  ``batched=False`` runs one ``infer`` per sentence exactly as the reference loop
         (api.py:78-94); ``batched=True`` pads them into one batch (one pass over the GPU; because the
         generator is unmasked, the last ~13 frames of the shorter items then differ slightly from a
         per-sentence run).  ``noise_w`` / ``noise_z``: None (drawn on the device) or lists with one ``[2, Tx]`` /
-        ``[192, >= Ty]`` tensor per sentence, passed on to ``infer``.  Returns a list of float32 numpy waveforms."""
+        ``[192, >= Ty]`` tensor per sentence, passed on to ``infer``.  ``seed`` (instead of them): counter-based noise,
+        an int ``s`` giving sentence ``i`` the stream ``(s, i)`` in the batched and in the per-sentence loop alike (so
+        both draw the same durations), or a list with one seed / pair per sentence; a seeded call is reproducible
+        without anyone guessing ``Ty``.  Returns a list of float32 numpy waveforms."""
+        noise_mod.exclusive(seed, noise_w=noise_w, noise_z=noise_z)
         device = self.device
         hop = self.hps.data.hop_length
         if not batched:
             seqs = [torch.as_tensor(s, dtype=torch.long).reshape(-1) for s in id_sequences]
+            seeds = [None] * len(seqs) if seed is None else noise_mod.per_item(seed, len(seqs))
             for name, nz in (("noise_w", noise_w), ("noise_z", noise_z)):
                 if nz is not None and len(nz) != len(seqs):
                     raise ValueError(f"{name}: one tensor per sentence ({len(seqs)}), got {len(nz)}")
@@ -166,11 +177,11 @@ class BaseSpeakerTTS(OpenVoiceBaseClass):
                 o = self.model.infer(s[None].to(device), torch.LongTensor([s.numel()]).to(device),
                                      sid=torch.LongTensor([speaker_id]).to(device), noise_scale=noise_scale,
                                      noise_scale_w=noise_scale_w, length_scale=1.0 / speed, noise_w=row(noise_w, i),
-                                     noise_z=row(noise_z, i))[0]
+                                     noise_z=row(noise_z, i), **noise_mod.kw(seeds[i]))[0]
                 out.append(o[0, 0].data.cpu().float().numpy())
             return out
         o, frames = self.infer_padded(id_sequences, speaker_id, speed=speed, noise_scale=noise_scale,
-                                      noise_scale_w=noise_scale_w, noise_w=noise_w, noise_z=noise_z)
+                                      noise_scale_w=noise_scale_w, noise_w=noise_w, noise_z=noise_z, **noise_mod.kw(seed))
         frames = frames.cpu().tolist()
         o = o[:, 0].data.cpu().float().numpy()
         return [o[i, :frames[i] * hop] for i in range(len(frames))]
@@ -188,10 +199,12 @@ class BaseSpeakerTTS(OpenVoiceBaseClass):
             ids.append(self.get_text(t, self.hps, False))
         return ids
 
-    def tts(self, text, output_path, speaker, language="English", speed=1.0, batched=False):
-        """reference: openvoice/api.py:73-98."""
+    def tts(self, text, output_path, speaker, language="English", speed=1.0, batched=False, *, seed=None):
+        """reference: openvoice/api.py:73-98.  ``seed``: as for ``tts_from_ids`` (sentence ``i`` on stream ``(seed,
+        i)``)."""
         ids = self.text_to_ids(text, language)
-        audio_list = self.tts_from_ids(ids, self.hps.speakers[speaker], speed=speed, batched=batched)
+        audio_list = self.tts_from_ids(ids, self.hps.speakers[speaker], speed=speed, batched=batched,
+                                       **noise_mod.kw(seed))
         audio = self.audio_numpy_concat(audio_list, sr=self.hps.data.sampling_rate, speed=speed)
         if output_path is None:
             return audio
@@ -301,7 +314,7 @@ class ToneColorConverter(OpenVoiceBaseClass):
         return torch.stack(embs).mean(0).reshape(1, -1, 1).detach()
 
     @torch.no_grad()
-    def convert_batch(self, waveforms, src_se, tgt_se, tau=0.3, noise=None):
+    def convert_batch(self, waveforms, src_se, tgt_se, tau=0.3, noise=None, *, seed=None):
         """Batched conversion, everything on the device.
 
         ``waveforms``: float32 tensor ``[B, N]`` (equal lengths), or a list of 1-D tensors/arrays of
@@ -310,7 +323,10 @@ class ToneColorConverter(OpenVoiceBaseClass):
         ``(o_hat [B, 1, hop*T_max] on the device, lengths_in_samples [B])``.  Note the reference
         decoder is unmasked, so for ragged batches samples within ~13 frames of an utterance's end
         differ from a per-utterance run (hard part 6); trim with the returned
-        lengths."""
+        lengths.  ``seed`` (instead of ``noise``): counter-based noise (``openvoice_amd.noise``) -- an int ``s`` gives
+        item ``b`` the stream ``(s, b)``, a list holds one seed or ``(seed, stream)`` pair per item; item ``b`` then
+        draws ``noise.normal((s, b), 192, 0, T)``, whatever the batch it is in."""
+        noise_mod.exclusive(seed, noise=noise)
         hop = self.hps.data.hop_length
         ragged = isinstance(waveforms, (list, tuple))
         if ragged:
@@ -325,15 +341,18 @@ class ToneColorConverter(OpenVoiceBaseClass):
             y = torch.as_tensor(waveforms, dtype=torch.float32).to(self.device)
             spec = self._spec(y)
             spec_lengths = torch.full((spec.shape[0],), spec.shape[2], dtype=torch.int64, device=self.device)
+        if seed is not None:
+            seed = noise_mod.per_item(seed, spec.shape[0])
         if self.use_graphs:
             # the graph's outputs are static buffers: hand the caller its own copy
             o_hat = self.model.voice_conversion(spec, spec_lengths, sid_src=src_se, sid_tgt=tgt_se, tau=tau,
-                                                noise=noise, graph=True, skip_padding=ragged)[0].clone()
+                                                noise=noise, graph=True, skip_padding=ragged,
+                                                **noise_mod.kw(seed))[0].clone()
         else:
             # ragged batch: the generator skips what lies beyond length + margin (16-20) frames of each utterance (the
             # samples within the returned lengths are bit-identical to the full computation; the padded tail is zero)
             o_hat = self.model.voice_conversion(spec, spec_lengths, sid_src=src_se, sid_tgt=tgt_se, tau=tau,
-                                                noise=noise, skip_padding=ragged)[0]
+                                                noise=noise, skip_padding=ragged, **noise_mod.kw(seed))[0]
         return o_hat, spec_lengths * hop
 
     @torch.no_grad()
@@ -376,16 +395,22 @@ class ToneColorConverter(OpenVoiceBaseClass):
             return out, torch.tensor(frames, dtype=torch.int64, device=self.device) * hop
         return out
 
-    def convert(self, audio_src_path, src_se, tgt_se, output_path=None, tau=0.3, message="default"):
+    def convert(self, audio_src_path, src_se, tgt_se, output_path=None, tau=0.3, message="default", *, seed=None):
         """reference: openvoice/api.py:141-160.  A file at or beyond the one-pass launch limit
         (``longform.one_pass_limit_frames``: 63 551 frames = 12.3 min for the released configuration), which one pass
-        cannot convert, goes through ``convert_long`` with its defaults; every shorter file is converted in one pass."""
+        cannot convert, goes through ``convert_long`` with its defaults; every shorter file is converted in one pass.
+        ``seed``: counter-based noise of stream ``(seed, 0)`` (or of a pair), the same whichever of the two paths
+        runs."""
+        if seed is not None:
+            seed = noise_mod.check_seed(seed)
         hps = self.hps
         y = audio_io.load_to_device(audio_src_path, hps.data.sampling_rate, self.device)
         d = hps.data
         if longform.frames_of(y.numel(), d.filter_length, d.hop_length) >= longform.one_pass_limit_frames(self.model.model_cfg):
-            return self.convert_long(y, src_se, tgt_se, output_path=output_path, tau=tau, message=message)
-        o_hat, _ = self.convert_batch(y.unsqueeze(0), src_se, tgt_se, tau=tau)
+            return self.convert_long(y, src_se, tgt_se, output_path=output_path, tau=tau, message=message,
+                                     **noise_mod.kw(seed))
+        o_hat, _ = self.convert_batch(y.unsqueeze(0), src_se, tgt_se, tau=tau,
+                                      **noise_mod.kw(None if seed is None else [seed]))
         audio = o_hat[0, 0].data.cpu().float().numpy()
         audio = self.add_watermark(audio, message)
         if output_path is None:
@@ -422,37 +447,45 @@ class ToneColorConverter(OpenVoiceBaseClass):
 
     def convert_long(self, audio_or_path, src_se, tgt_se, output_path=None, tau=0.3, message="default",
                      window_frames=longform.DEFAULT_WINDOW_FRAMES, windows_per_launch=longform.DEFAULT_WINDOWS_PER_LAUNCH,
-                     noise=None, sr=None, out_sr=None):
+                     noise=None, sr=None, out_sr=None, *, seed=None):
         """``convert`` for a recording of any length: overlapping windows of ``window_frames`` frames, up to
         ``windows_per_launch`` of them per launch (``longform.WindowedConverter``); device memory is bounded by the window,
         not by the file.  ``audio_or_path``: a file path, or a 1-D float32 waveform (host or device) at ``sr`` Hz (None:
         the model rate; otherwise resampled on the device first).  ``noise``: ``[1, 192, >= T]`` or None -- then
         ``torch.randn(1, 192, T)`` on the device, the draw of a seeded one-pass ``convert``; T counts frames at the model
-        rate.  ``out_sr``: the rate of the returned / written audio (None: the model rate).  Otherwise the same return
+        rate; or ``seed`` (an int: stream ``(seed, 0)``, or a pair): counter-based noise, each window generating its own
+        frames, the same values as a one-pass ``convert(seed=...)``, a ``stream`` or a ``live_stream`` with that seed
+        draws.  ``out_sr``: the rate of the returned / written audio (None: the model rate).  Otherwise the same return
         value / file output as ``convert``."""
+        noise_mod.exclusive(seed, noise=noise)
         sr, out_sr = rates.check_rate(sr, "sr"), rates.check_rate(out_sr, "out_sr")
         y = self._to_model_rate(audio_or_path, sr)
-        o = self._windowed(window_frames, windows_per_launch).convert(y, src_se, tgt_se, tau=tau, noise=noise)
+        o = self._windowed(window_frames, windows_per_launch).convert(y, src_se, tgt_se, tau=tau, noise=noise,
+                                                                      **noise_mod.kw(seed))
         audio = self._finish(o, message, out_sr)
         if output_path is None:
             return audio
         audio_io.write(output_path, audio, self.hps.data.sampling_rate if out_sr is None else out_sr)
 
     def stream(self, src_se, tgt_se, tau=0.3, window_frames=longform.DEFAULT_STREAM_WINDOW_FRAMES, noise=None, sr_in=None,
-               sr_out=None):
+               sr_out=None, *, seed=None):
         """A ``longform.ConversionStream``: ``push(samples)`` -> newly finished converted samples (device tensor, maybe
         empty), ``close()`` -> the rest, ``latency_samples`` = ``(window_frames - 1) * hop + n_fft - (n_fft - hop) / 2``
         at the model rate.  ``sr_in`` / ``sr_out``: the rate of the pushes / of the output (None: the model rate); the
         stream resamples inside, carrying the filter state across pushes, and ``latency_samples`` (output samples) /
-        ``latency_seconds`` then include the resamplers' waits.  ``noise`` ``[1, 192, >= T]`` makes it reproducible.  The
+        ``latency_seconds`` then include the resamplers' waits.  ``noise`` ``[1, 192, >= T]`` makes it reproducible,
+        and so does
+        ``seed`` (stream ``(seed, 0)``, or a pair), which needs no length and keeps no noise tensor.  The
         output equals ``convert_long(..., windows_per_launch=1)`` of the whole input, bit for bit -- with rates, of the
         input resampled to the model rate, and resampled to ``sr_out`` after (``audio_io.resample_on_device``)."""
-        return self._windowed(window_frames, 1).stream(src_se, tgt_se, tau=tau, noise=noise, sr_in=sr_in, sr_out=sr_out)
+        return self._windowed(window_frames, 1).stream(src_se, tgt_se, tau=tau, noise=noise, sr_in=sr_in, sr_out=sr_out,
+                                                       **noise_mod.kw(seed))
 
     # ---- many streams and recordings in shared launches -------------------------------------------------------------
     def stream_pool(self, tau=0.3, window_frames=longform.DEFAULT_STREAM_WINDOW_FRAMES,
                     max_windows_per_launch=longform.DEFAULT_POOL_WINDOWS_PER_LAUNCH):
-        """A ``longform.StreamPool``: many live streams (``open(src_se, tgt_se, noise=None, sr_in=None, sr_out=None)`` ->
+        """A ``longform.StreamPool``: many live streams (``open(src_se, tgt_se, noise=None, sr_in=None, sr_out=None,
+        seed=None)`` ->
         handle, ``push(h, samples)``, ``close(h)``), whose ready windows one ``step()`` converts together, up to
         ``max_windows_per_launch`` per launch -> ``{handle: newly finished samples}``; streams at rates of their own are
         resampled in one launch per direction and step.  Each stream's output equals a ``stream(...)`` fed the same
@@ -461,7 +494,7 @@ class ToneColorConverter(OpenVoiceBaseClass):
 
     # ---- low-latency live streams ------------------------------------------------------------------------------------
     def live_stream(self, src_se, tgt_se, tau=0.3, chunk_frames=15, noise=None, sr_in=None, sr_out=None,
-                    generator="fp32"):
+                    generator="fp32", *, seed=None):
         """A ``live.LiveStream``: the conversion as a cascade of units that carry their recent input as state.
         ``push(samples)`` -> newly finished samples, ``close()`` -> the rest, ``latency_samples`` =
         ``live.live_latency_samples`` (1.45 s at 15 frames).  ``chunk_frames``: a positive multiple of 15 (the Winograd
@@ -472,15 +505,18 @@ class ToneColorConverter(OpenVoiceBaseClass):
         output samples) and ``latency_seconds`` then include the resamplers' waits (``rates.stream_latency``).  With
         ``noise`` ``[1, 192, >= T]`` the output equals ``convert_long`` of the whole input (resampled to the model rate
         before and to ``sr_out`` after by ``audio_io.resample_on_device``), with ``generator="bf16"`` the one made with
-        ``use_bf16_generator``."""
+        ``use_bf16_generator``.  ``seed`` (an int: stream ``(seed, 0)``, or a pair) does the same without a length: the
+        noise of frames ``[f0, f0 + n)`` is generated when the chunk is fed, so the output does not depend on the push
+        sizes, equals ``convert_long(seed=...)``, and no noise tensor is held however long the call lasts."""
         from . import live
         d = self.hps.data
         return live.LiveStream(self.model, src_se, tgt_se, tau=tau, chunk_frames=chunk_frames, noise=noise,
                                n_fft=d.filter_length, hop=d.hop_length, sr_in=sr_in, sr_out=sr_out,
-                               model_sr=d.sampling_rate, generator=generator)
+                               model_sr=d.sampling_rate, generator=generator, **noise_mod.kw(seed))
 
     def live_pool(self, tau=0.3, chunk_frames=15, max_streams_per_launch=32, generator="fp32"):
-        """A ``live.LivePool``: many live streams (``open(src_se, tgt_se, noise=None, sr_in=None, sr_out=None)`` /
+        """A ``live.LivePool``: many live streams (``open(src_se, tgt_se, noise=None, sr_in=None, sr_out=None,
+        seed=None)`` /
         ``push`` / ``close``), every stream with a ready chunk converted by one ``step()`` in launches of up to
         ``max_streams_per_launch`` rows per unit; streams at rates of their own are resampled in one launch per direction
         and step.  Each stream equals its solo ``live_stream``.  One ``tau`` and one ``generator`` (``"fp32"`` or
@@ -492,20 +528,25 @@ class ToneColorConverter(OpenVoiceBaseClass):
 
     def convert_many(self, items, src_se, tgt_se, tau=0.3, window_frames=longform.DEFAULT_WINDOW_FRAMES,
                      windows_per_launch=longform.DEFAULT_MANY_WINDOWS_PER_LAUNCH, noise=None, output_paths=None,
-                     message="default", sr=None, out_sr=None):
+                     message="default", sr=None, out_sr=None, *, seed=None):
         """``convert_long`` of many recordings with their windows packed ACROSS recordings into launches of up to
         ``windows_per_launch`` (``longform.WindowedConverter.convert_many``).  ``items``: file paths (any rate, decoded
         and resampled like ``convert_long``) or 1-D waveforms at ``sr`` Hz (None: the model rate; one rate, or a list
         with one per item).  ``out_sr``: the rate of the results (None: the model rate; one, or one per item).  The
         array items are resampled to the model rate in ONE launch, and the results to ``out_sr`` in one more
         (``rates.resample_many``).  ``src_se`` / ``tgt_se``: one ``[1, 256, 1]`` for every item, or a list with one per
-        item.  ``noise``: None or a list of ``[1, 192, >= T_i]``.  Returns a list of numpy arrays (watermark hook applied
+        item.  ``noise``: None or a list of ``[1, 192, >= T_i]``; ``seed`` (instead): an int ``s``
+        gives item ``i`` the stream ``(s, i)``, or a list with one seed / pair per item.  Returns a list of numpy
+        arrays (watermark hook applied
         per item, at the model rate), or writes ``output_paths[i]`` (at its ``out_sr``) instead.  Each item equals
         ``convert_long`` of it with the same ``window_frames``, noise and rates."""
         hps = self.hps
         msr = hps.data.sampling_rate
         items = list(items)
         n = len(items)
+        noise_mod.exclusive(seed, noise=noise)
+        if seed is not None:
+            seed = noise_mod.per_item(seed, n)
         per_item = lambda se: list(se) if isinstance(se, (list, tuple)) else [se] * n
         srcs, tgts = per_item(src_se), per_item(tgt_se)
         srs = [rates.check_rate(r, "sr") for r in per_item(sr)]
@@ -518,7 +559,8 @@ class ToneColorConverter(OpenVoiceBaseClass):
                  else torch.as_tensor(x, dtype=torch.float32).reshape(-1).to(self.device) for x in items]
         paths = [isinstance(x, (str, os.PathLike)) for x in items]
         waves = rates.resample_many(waves, [(None, None) if p else (r, msr) for p, r in zip(paths, srs)], self.device)
-        outs = self._windowed(window_frames, windows_per_launch).convert_many(waves, srcs, tgts, tau=tau, noises=noise)
+        outs = self._windowed(window_frames, windows_per_launch).convert_many(waves, srcs, tgts, tau=tau, noises=noise,
+                                                                              **noise_mod.kw(seed, "seeds"))
         if self.watermark_model is None:
             outs = rates.resample_many(outs, [(msr, r) for r in out_srs], self.device)
             audios = [o.cpu().numpy() for o in outs]

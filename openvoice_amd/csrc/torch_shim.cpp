@@ -420,6 +420,7 @@ TORCH_LIBRARY(openvoice_amd, m) {
   bind_device<&ov_vad_segments_i32>(m, "vad_segments_i32");
   bind_device<&ov_vad_compact_f32>(m, "vad_compact_f32");
   bind_device<&ov_join_segments_f32>(m, "join_segments_f32");
+  bind_device<&ov_normal_philox_f32>(m, "normal_philox_f32");
   bind_device<&ov_stitch_window_cores_f32>(m, "stitch_window_cores_f32");
   bind_device<&ov_conv_post_tanh_f32>(m, "conv_post_tanh_f32");
   bind_device<&ov_conv_post_tanh_limited_f32>(m, "conv_post_tanh_limited_f32");

@@ -16,6 +16,7 @@ import os
 import torch
 
 from . import _lib
+from . import noise as noise_mod
 from ._lib import (ConvParams, EPI_CONVT, EPI_COUPLE, EPI_GATE, EPI_LINEAR, EPI_POSTERIOR, EPI_RESSKIP,
                    F_CONVT_GROUPED, F_MASK_V, F_OUT2_INIT)
 from .params import ENC_Q_LAYERS, FLOW_LAYERS, N_FLOWS, REF_ENC_FILTERS, REF_ENC_GRU, effective_weight
@@ -839,11 +840,15 @@ class ConverterEngine:
     # ---- the path ----------------------------------------------------------------------------------
     @torch.no_grad()
     @on_own_device
-    def voice_conversion(self, spec, spec_lengths, sid_src, sid_tgt, tau=1.0, noise=None, skip_padding=False):
+    def voice_conversion(self, spec, spec_lengths, sid_src, sid_tgt, tau=1.0, noise=None, skip_padding=False, *,
+                         seed=None):
         """Same contract as the reference seam (openvoice/models.py:492-499):
         ``(o_hat [B,1,256T], y_mask [B,1,T], (z, z_p, z_hat) [B,192,T])``.  ``noise`` [B,192,T]
         replaces the reference's ``torch.randn_like`` draw (models.py:220); when omitted it is drawn
-        from torch's generator on the device.  ``skip_padding``: the generator -- 98 % of the work, and unmasked in
+        from torch's generator on the device.  ``seed`` (instead of ``noise``): counter-based noise (``noise.py``,
+        purpose 0) generated straight into the workspace rows by one launch -- an int ``s`` gives row ``b`` the pair
+        ``(s, b)``, a list holds one seed, pair or ``(seed, stream, first frame)`` per row (``noise.rows``).
+        ``skip_padding``: the generator -- 98 % of the work, and unmasked in
         the reference, so a padded batch costs as if every utterance had the longest length -- computes only the
         first ``length + limit_margin(B, T)`` frames of each utterance (length-aware work lists,
         ``ov_conv1d_params.col_limit``); every sample of the first ``length`` frames is bit-identical to the full
@@ -859,9 +864,12 @@ class ConverterEngine:
         lengths = spec_lengths.to(dev, torch.int64).contiguous()
         g_src = sid_src.to(dev, torch.float32).reshape(sid_src.shape[0], -1).contiguous()
         g_tgt = sid_tgt.to(dev, torch.float32).reshape(sid_tgt.shape[0], -1).contiguous()
+        noise_mod.exclusive(seed, noise=noise)
         ws = self._workspace(B, T)
         Tp, mask = ws["Tp"], ws["mask"]
-        if noise is None:
+        if seed is not None:
+            self.seed_noise(ws["noise"], seed, B, T, Tp)
+        elif noise is None:
             # one launch, the RNG stream of a dense torch.randn(B, C, T) (the reference's randn_like, models.py:220):
             # the pad columns [T, Tp) are not drawn into, so a seeded conversion does not depend on the row padding
             ws["noise"][:, :, :T].normal_()
@@ -904,6 +912,14 @@ class ConverterEngine:
         y_mask = torch.empty(B, 1, T, dtype=torch.float32, device=dev)
         _lib.call("ov_unpad_rows_f32", mask, y_mask, B, T, Tp)
         return o_hat, y_mask, (dense[0], dense[1], dense[2])
+
+    def seed_noise(self, dst, seed, B, T, ld, purpose=noise_mod.PURPOSE_POSTERIOR):
+        """Counter-based noise of ``seed`` (``noise.rows``: one ``(seed, stream, first frame)`` per row) into the first
+        ``T`` columns of the ``[B, inter, ld]`` rows of ``dst``: one record per row, one launch, no dense temporary; the
+        pad columns ``[T, ld)`` keep their contents."""
+        C = self.inter
+        noise_mod.fill([(s, k, purpose, f0, T, b * C * ld, ld) for b, (s, k, f0) in enumerate(noise_mod.rows(seed, B))],
+                       C, dst)
 
     def _frames(self, ws, b0, b1, spec, conds, tau):
         """Posterior encoder and the two flow passes for the utterances [b0, b1) (views of the whole-batch workspace)."""
@@ -1455,14 +1471,17 @@ class GraphedConversion:
 
     @torch.no_grad()
     @on_own_device
-    def __call__(self, spec, spec_lengths, sid_src, sid_tgt, noise=None):
+    def __call__(self, spec, spec_lengths, sid_src, sid_tgt, noise=None, *, seed=None):
+        noise_mod.exclusive(seed, noise=noise)
         if tuple(spec.shape) != (self.B, self.engine.spec_channels, self.T):
             raise _lib.OvError(f"graph captured for spec {(self.B, self.engine.spec_channels, self.T)}, got {tuple(spec.shape)}")
         self.spec.copy_(spec)
         self.lengths.copy_(spec_lengths)
         self.g_src.copy_(sid_src.reshape(self.g_src.shape))
         self.g_tgt.copy_(sid_tgt.reshape(self.g_tgt.shape))
-        if noise is None:
+        if seed is not None:        # outside the captured region, like the copies: the graph reads the static buffer
+            self.engine.seed_noise(self.noise, seed, self.B, self.T, self.T)
+        elif noise is None:
             self.noise.normal_()
         else:
             self.noise.copy_(noise)

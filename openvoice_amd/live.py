@@ -43,6 +43,7 @@ import math
 import torch
 
 from . import _lib, rates
+from . import noise as noise_mod
 from .longform import launch_ladder, stream_end_frames, winograd_grid_frames
 from .params import ENC_Q_KERNEL, ENC_Q_LAYERS, FLOW_KERNEL, FLOW_LAYERS, N_FLOWS
 
@@ -203,8 +204,10 @@ class Cascade:
 class _Live:
     """One stream of a ``LivePool``: waveform buffer, noise, cascade bookkeeping and its arena slot."""
 
-    def __init__(self, pool, slot, src_se, tgt_se, noise):
+    def __init__(self, pool, slot, src_se, tgt_se, noise, seed=None):
+        noise_mod.exclusive(seed, noise=noise)
         self.pool, self.slot = pool, slot
+        self.seed = None if seed is None else noise_mod.check_seed(seed)      # (seed, stream): frames made on demand
         dev = pool.device
         self.cas = Cascade(pool.units, pool.chunk)
         self.buf = torch.empty(0, dtype=torch.float32, device=dev)
@@ -374,9 +377,13 @@ class LivePool:
     def active(self):
         return list(self._streams)
 
-    def open(self, src_se, tgt_se, noise=None, sr_in=None, sr_out=None):
+    def open(self, src_se, tgt_se, noise=None, sr_in=None, sr_out=None, *, seed=None):
         """A new stream -> its handle.  ``sr_in`` / ``sr_out``: the rate of its pushes / of its output (None or the
-        model rate: no resampler in that direction)."""
+        model rate: no resampler in that direction).  ``noise`` ``[1, inter, >= T]``, or ``seed`` (an int: stream
+        ``(seed, 0)``, or a pair): counter-based noise (``noise.py``) generated chunk by chunk into the staging rows --
+        the stream then equals ``convert_long(seed=...)`` of its whole input whatever the push sizes and whoever shares
+        the pool, and holds no noise tensor; neither: drawn from torch's generator per chunk."""
+        noise_mod.exclusive(seed, noise=noise)
         sr_in, sr_out = rates.check_rate(sr_in, "sr_in"), rates.check_rate(sr_out, "sr_out")
         if not self._free_slots:                 # the arena doubles: streams already open keep their slots
             grown = max(1, 2 * self._slots)
@@ -386,7 +393,7 @@ class LivePool:
         slot = self._free_slots.pop()
         h = self._next
         self._next += 1
-        st = _Live(self, slot, src_se, tgt_se, noise)
+        st = _Live(self, slot, src_se, tgt_se, noise, seed=seed)
         st.sr_in, st.sr_out = sr_in, sr_out
         st.rin = st.rout = None
         if sr_in is not None and sr_in != self.model_sr:
@@ -493,7 +500,18 @@ class LivePool:
             W = len(chunk)
             stage = self.mem[self.stage_off:self.stage_off + W * rows0 * sld].view(W, rows0, sld)
             stage[:, :bins, :nf].copy_(spec)
-            stage[:, bins:, :nf].copy_(torch.stack([st.noise_for(f0, nf) for st, _, f0 in chunk]))
+            if all(st.seed is None for st, _, _ in chunk):
+                stage[:, bins:, :nf].copy_(torch.stack([st.noise_for(f0, nf) for st, _, f0 in chunk]))
+            else:
+                # every seeded stream of the launch in ONE fill launch, straight into its staging rows; the others copy
+                fills = []
+                for w, (st, _, f0) in enumerate(chunk):
+                    if st.seed is None:
+                        stage[w, bins:, :nf].copy_(st.noise_for(f0, nf))
+                    else:
+                        fills.append(st.seed + (noise_mod.PURPOSE_POSTERIOR, f0, nf,
+                                                self.stage_off + (w * rows0 + bins) * sld, sld))
+                noise_mod.fill(fills, self.inter, self.mem)
             carry = []
             for w, (st, _, f0) in enumerate(chunk):
                 k = 0
@@ -649,10 +667,11 @@ class LiveStream:
     the model rate).  ``generator``: as for ``LivePool``."""
 
     def __init__(self, model, src_se, tgt_se, tau=0.3, chunk_frames=DEFAULT_CHUNK_FRAMES, noise=None, n_fft=1024,
-                 hop=256, sr_in=None, sr_out=None, model_sr=rates.MODEL_RATE, generator="fp32"):
+                 hop=256, sr_in=None, sr_out=None, model_sr=rates.MODEL_RATE, generator="fp32", seed=None):
+        noise_mod.exclusive(seed, noise=noise)
         self._pool = LivePool(model, tau=tau, chunk_frames=chunk_frames, max_streams_per_launch=1, n_fft=n_fft, hop=hop,
                               model_sr=model_sr, generator=generator)
-        self._h = self._pool.open(src_se, tgt_se, noise=noise, sr_in=sr_in, sr_out=sr_out)
+        self._h = self._pool.open(src_se, tgt_se, noise=noise, sr_in=sr_in, sr_out=sr_out, **noise_mod.kw(seed))
         self.latency_seconds, self.latency_samples = self._pool.latency_of(self._h)
         self._closed = False
 

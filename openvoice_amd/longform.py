@@ -24,6 +24,7 @@ import math
 import torch
 
 from . import _lib, rates
+from . import noise as noise_mod
 from .engine import GENERATOR_MARGIN, generator_margin_frames
 from .params import ENC_Q_KERNEL, ENC_Q_LAYERS, FLOW_KERNEL, FLOW_LAYERS, N_FLOWS
 
@@ -186,17 +187,18 @@ class WindowedConverter:
         from .mel_processing import native_spectrogram
         return native_spectrogram(self._device(), self.n_fft, self.hop)
 
-    def _launch(self, wave, n_samples, plan_dev, firsts_dev, Tw, src_se, tgt_se, tau, nz, out, out_frame0):
+    def _launch(self, wave, n_samples, plan_dev, firsts_dev, Tw, src_se, tgt_se, tau, nz, out, out_frame0, seed=None):
         """One launch of W = len(firsts_dev) windows: framing -> spectrogram -> voice_conversion -> their cores into
-        ``out`` (``plan_dev`` [W, 3] int64 records, ``nz`` [W, inter, Tw] noise)."""
+        ``out`` (``plan_dev`` [W, 3] int64 records, ``nz`` [W, inter, Tw] noise, or ``seed``: one ``(seed, stream, first
+        frame)`` per window, generated inside ``voice_conversion``)."""
         W = firsts_dev.shape[0]
         spec = self._spectrogram().windows(wave, n_samples, firsts_dev, Tw)
         lengths = torch.full((W,), Tw, dtype=torch.int64, device=wave.device)
         o_hat = self.model.voice_conversion(spec, lengths, sid_src=src_se, sid_tgt=tgt_se, tau=tau, noise=nz,
-                                            graph=self.graph)[0]
+                                            graph=self.graph, **noise_mod.kw(seed))[0]
         _lib.call("ov_stitch_window_cores_f32", o_hat, plan_dev, W, Tw, self.spf, out, out.numel(), out_frame0)
 
-    def _launch_multi(self, pool, records_dev, Tw, src_se, tgt_se, tau, nz, out, stitch_dev, n_out):
+    def _launch_multi(self, pool, records_dev, Tw, src_se, tgt_se, tau, nz, out, stitch_dev, n_out, seed=None):
         """One launch of W = len(records_dev) windows, each from its own span of ``pool`` (``records_dev`` [W, 3] int64
         (base, n_samples, first_frame)): framing -> spectrogram -> voice_conversion with per-window embedding rows ->
         the cores of the first ``n_out`` windows into the packed ``out`` (``stitch_dev`` [n_out, 3] virtual records,
@@ -205,13 +207,14 @@ class WindowedConverter:
         spec = self._spectrogram().windows_multi(pool, records_dev, Tw)
         lengths = torch.full((W,), Tw, dtype=torch.int64, device=pool.device)
         o_hat = self.model.voice_conversion(spec, lengths, sid_src=src_se, sid_tgt=tgt_se, tau=tau, noise=nz,
-                                            graph=self.graph)[0]
+                                            graph=self.graph, **noise_mod.kw(seed))[0]
         _lib.call("ov_stitch_window_cores_f32", o_hat, stitch_dev, n_out, Tw, self.spf, out, out.numel(), 0)
 
     def _run_jobs(self, sources, jobs, tau, out, max_windows, ladder=None):
         """Windows of many sources in shared launches.  ``sources``: 1-D device waveforms (spans); ``jobs``: window
         jobs ``(source, f0, lo, hi, Tw, noise [1, inter, Tw], src_se [1, gin, 1], tgt_se, dst)`` with frames relative to
-        the source span and ``dst`` the packed output frame of the core's first frame.  Jobs of equal ``Tw`` share
+        the source span (``noise``: a tensor, or the ``(seed, stream, first frame)`` of a seeded source's window) and
+        ``dst`` the packed output frame of the core's first frame.  Jobs of equal ``Tw`` share
         launches of up to ``max_windows`` in the given order; a partial launch is padded up to the next ``ladder`` size
         (None: launched as it is) with copies of its last window.  Returns the number of launches."""
         if not jobs:
@@ -234,15 +237,29 @@ class WindowedConverter:
                 recs = [(bases[j[0]], sources[j[0]].numel(), j[1]) for j in rows]
                 recs += [(j[8] - (j[2] - j[1]), j[8], j[8] + j[3] - j[2]) for j in chunk]
                 recs_dev = torch.tensor(recs, dtype=torch.int64).to(pool.device)      # one host -> device copy
-                nz = torch.cat([j[5] for j in rows])
+                seeded = [not torch.is_tensor(j[5]) for j in rows]
+                if all(seeded):                 # generated inside voice_conversion, straight into its rows
+                    nz, seed = None, [j[5] for j in rows]
+                elif not any(seeded):
+                    nz, seed = torch.cat([j[5] for j in rows]), None
+                else:                           # a launch that mixes both kinds: the seeded rows in one fill launch
+                    nz, seed = torch.empty(W, self.inter, Tw, dtype=torch.float32, device=pool.device), None
+                    for w, j in enumerate(rows):
+                        if not seeded[w]:
+                            nz[w].copy_(j[5][0])
+                    noise_mod.fill([(j[5][0], j[5][1], noise_mod.PURPOSE_POSTERIOR, j[5][2], Tw, w * self.inter * Tw, Tw)
+                                    for w, j in enumerate(rows) if seeded[w]], self.inter, nz)
                 g_src = torch.cat([j[6].reshape(1, -1, 1) for j in rows])
                 g_tgt = torch.cat([j[7].reshape(1, -1, 1) for j in rows])
-                self._launch_multi(pool, recs_dev[:W], Tw, g_src, g_tgt, tau, nz, out, recs_dev[W:], r)
+                self._launch_multi(pool, recs_dev[:W], Tw, g_src, g_tgt, tau, nz, out, recs_dev[W:], r,
+                                   **noise_mod.kw(seed))
                 launches += 1
         return launches
 
-    def _prepare(self, wave, noise, dev):
-        """(device waveform, T, noise [1, inter, >= T]) of one recording, checked like ``convert``."""
+    def _prepare(self, wave, noise, dev, seed=None):
+        """(device waveform, T, noise [1, inter, >= T]) of one recording, checked like ``convert``; with ``seed`` the
+        third item is the ``(seed, stream)`` pair instead and no tensor exists."""
+        noise_mod.exclusive(seed, noise=noise)
         wave = torch.as_tensor(wave, dtype=torch.float32).reshape(-1).to(dev).contiguous()
         N = wave.numel()
         if self.pad >= N:
@@ -250,7 +267,9 @@ class WindowedConverter:
         T = frames_of(N, self.n_fft, self.hop)
         if T < 1:
             raise ValueError("waveform shorter than one frame")
-        if noise is None:
+        if seed is not None:
+            noise = noise_mod.check_seed(seed)
+        elif noise is None:
             noise = torch.randn(1, self.inter, T, dtype=torch.float32, device=dev)
         else:
             noise = noise.to(dev, torch.float32)
@@ -259,11 +278,13 @@ class WindowedConverter:
         return wave, T, noise
 
     @torch.no_grad()
-    def convert_many(self, waves, src_ses, tgt_ses, tau=0.3, noises=None):
+    def convert_many(self, waves, src_ses, tgt_ses, tau=0.3, noises=None, *, seeds=None):
         """``convert`` of many recordings with their windows packed across recordings into launches of up to
         ``windows_per_launch`` (``ov_frame_hops_multi_f32``: each window framed from its own recording).  ``src_ses`` /
         ``tgt_ses``: one embedding per recording; ``noises``: None or one ``[1, inter, >= T_i]`` (or None) per
-        recording -- drawn in order like ``convert`` otherwise.  Every recording runs the windows of its own
+        recording -- drawn in order like ``convert`` otherwise; ``seeds`` (instead): an int ``s`` gives recording ``i``
+        the counter-based noise of ``(s, i)``, or a list with one seed / pair per recording.  Every recording runs the
+        windows of its own
         ``plan_windows``; recordings of ``T <= window_frames`` frames are one ``T``-frame window each and share launches
         with the recordings of equal ``T``.  Returns the converted waveforms (device tensors, views of one packed
         output), each equal to ``convert`` of that recording with the same noise (bit for bit with direct kernels)."""
@@ -271,13 +292,17 @@ class WindowedConverter:
         n = len(waves)
         if len(src_ses) != n or len(tgt_ses) != n or (noises is not None and len(noises) != n):
             raise ValueError("convert_many: one src / tgt embedding (and noise) per recording")
-        items = [self._prepare(w, None if noises is None else noises[i], dev) for i, w in enumerate(waves)]
+        noise_mod.exclusive(seeds, noises=noises)
+        seeds = [None] * n if seeds is None else noise_mod.per_item(seeds, n)
+        items = [self._prepare(w, None if noises is None else noises[i], dev, **noise_mod.kw(seeds[i]))
+                 for i, w in enumerate(waves)]
         jobs, offs, acc = [], [], 0
         for i, (wave, T, noise) in enumerate(items):
             offs.append(acc)
             Tw = min(T, self.window_frames)
             for f0, lo, hi in plan_windows(T, self.window_frames, self.context, self.grid):
-                jobs.append((i, f0, lo, hi, Tw, noise[:, :, f0:f0 + Tw], src_ses[i], tgt_ses[i], acc + lo))
+                nz = noise + (f0,) if seeds[i] is not None else noise[:, :, f0:f0 + Tw]
+                jobs.append((i, f0, lo, hi, Tw, nz, src_ses[i], tgt_ses[i], acc + lo))
             acc += T
         out = torch.empty(acc * self.spf, dtype=torch.float32, device=dev)
         # windows of full length first (one shape), then the short recordings grouped by length
@@ -286,12 +311,14 @@ class WindowedConverter:
         return [out[o * self.spf:(o + T) * self.spf] for o, (_, T, _) in zip(offs, items)]
 
     @torch.no_grad()
-    def convert(self, wave, src_se, tgt_se, tau=0.3, noise=None):
+    def convert(self, wave, src_se, tgt_se, tau=0.3, noise=None, *, seed=None):
         """``wave``: 1-D float32 waveform at the model rate (host or device).  ``noise``: ``[1, inter, >= T]`` or None
-        (then ``torch.randn(1, inter, T)`` on the device: the stream of a seeded one-pass ``convert``).  Returns the
-        converted waveform ``[spf * T]`` on the device (spf = the generator's samples per frame = hop), ``T`` = frames of ``spectrogram_torch``."""
+        (then ``torch.randn(1, inter, T)`` on the device: the stream of a seeded one-pass ``convert``); ``seed``
+        (instead of ``noise``): the counter-based noise of ``(seed, 0)`` (or of a pair), each window generating its own
+        frames -- no ``[1, inter, T]`` tensor exists.  Returns the converted waveform ``[spf * T]`` on the device (spf =
+        the generator's samples per frame = hop), ``T`` = frames of ``spectrogram_torch``."""
         dev = self._device()
-        wave, T, noise = self._prepare(wave, noise, dev)
+        wave, T, noise = self._prepare(wave, noise, dev, **noise_mod.kw(seed))
         N = wave.numel()
         plan = plan_windows(T, self.window_frames, self.context, self.grid)
         Tw = min(T, self.window_frames)
@@ -301,12 +328,17 @@ class WindowedConverter:
         for i0 in range(0, len(plan), self.windows_per_launch):
             i1 = min(len(plan), i0 + self.windows_per_launch)
             # each window's noise is a slice of the file's [1, inter, T] draw (voice_conversion copies it into its rows)
-            nz = torch.stack([noise[0, :, f0:f0 + Tw] for f0, _, _ in plan[i0:i1]])
-            self._launch(wave, N, plan_dev[i0:i1], firsts_dev[i0:i1], Tw, src_se, tgt_se, tau, nz, out, 0)
+            if seed is not None:
+                nz, rows = None, [noise + (f0,) for f0, _, _ in plan[i0:i1]]
+            else:
+                nz, rows = torch.stack([noise[0, :, f0:f0 + Tw] for f0, _, _ in plan[i0:i1]]), None
+            self._launch(wave, N, plan_dev[i0:i1], firsts_dev[i0:i1], Tw, src_se, tgt_se, tau, nz, out, 0,
+                         **noise_mod.kw(rows))
         return out
 
-    def stream(self, src_se, tgt_se, tau=0.3, noise=None, sr_in=None, sr_out=None):
-        return ConversionStream(self, src_se, tgt_se, tau=tau, noise=noise, sr_in=sr_in, sr_out=sr_out)
+    def stream(self, src_se, tgt_se, tau=0.3, noise=None, sr_in=None, sr_out=None, *, seed=None):
+        return ConversionStream(self, src_se, tgt_se, tau=tau, noise=noise, sr_in=sr_in, sr_out=sr_out,
+                                **noise_mod.kw(seed))
 
     def stream_pool(self, tau=0.3, max_windows_per_launch=DEFAULT_POOL_WINDOWS_PER_LAUNCH):
         return StreamPool(self, tau=tau, max_windows_per_launch=max_windows_per_launch)
@@ -318,8 +350,10 @@ class _StreamState:
     rule, the end-of-input plan, the noise, and the rates of the input / output (``sr_in`` / ``sr_out``, None: the
     model rate)."""
 
-    def __init__(self, conv, src_se, tgt_se, noise=None, sr_in=None, sr_out=None):
+    def __init__(self, conv, src_se, tgt_se, noise=None, sr_in=None, sr_out=None, seed=None):
+        noise_mod.exclusive(seed, noise=noise)
         self.conv, self.src_se, self.tgt_se = conv, src_se, tgt_se
+        self._seed = None if seed is None else noise_mod.check_seed(seed)     # (seed, stream): frames made on demand
         self.dev = conv._device()
         c = conv
         self._Tw, self._core, self._ctx = c.window_frames, c.core, c.context
@@ -335,7 +369,8 @@ class _StreamState:
         self._k = 0                 # next regular window
         self._emitted = 0           # frames of output handed out
         self._noise = noise.to(self.dev, torch.float32) if noise is not None else None
-        self._nz = torch.empty(1, c.inter, 0, dtype=torch.float32, device=self.dev)   # drawn noise, frames [_nz0, ..)
+        # drawn noise, frames [_nz0, ..); a seeded stream keeps none
+        self._nz = None if seed is not None else torch.empty(1, c.inter, 0, dtype=torch.float32, device=self.dev)
         self._nz0 = 0
         self._closed = False
         self._tail = None           # StreamPool: the end-of-input plan, taken by close()
@@ -353,7 +388,10 @@ class _StreamState:
         return max(interior, longer)
 
     def _noise_for(self, f0, Tw):
-        """[1, inter, Tw] noise of frames [f0, f0 + Tw): a slice of the caller's tensor, or drawn once per frame."""
+        """[1, inter, Tw] noise of frames [f0, f0 + Tw): a slice of the caller's tensor, or drawn once per frame; of a
+        seeded stream ``(seed, stream, f0)``: the launch generates the frames where it needs them."""
+        if self._seed is not None:
+            return self._seed + (f0,)
         if self._noise is not None:
             if self._noise.shape[2] < f0 + Tw:
                 raise ValueError(f"noise has {self._noise.shape[2]} frames, the stream needs {f0 + Tw}")
@@ -375,7 +413,7 @@ class _StreamState:
         if base > self._base:
             keep = self._buf[base - self._base:self._len].clone()
             self._buf, self._len, self._base = keep, keep.numel(), base
-        if self._noise is None and keep_from_frame > self._nz0:
+        if self._noise is None and self._seed is None and keep_from_frame > self._nz0:
             self._nz = self._nz[:, :, keep_from_frame - self._nz0:].clone()
             self._nz0 = keep_from_frame
 
@@ -427,8 +465,8 @@ class ConversionStream(_StreamState):
     ``rates.StreamResampler`` to the model rate and the output through another one, one launch each per push;
     ``latency_samples`` (in output samples) and ``latency_seconds`` include their waits (``rates.stream_latency``)."""
 
-    def __init__(self, conv, src_se, tgt_se, tau=0.3, noise=None, sr_in=None, sr_out=None):
-        super().__init__(conv, src_se, tgt_se, noise, sr_in=sr_in, sr_out=sr_out)
+    def __init__(self, conv, src_se, tgt_se, tau=0.3, noise=None, sr_in=None, sr_out=None, seed=None):
+        super().__init__(conv, src_se, tgt_se, noise, sr_in=sr_in, sr_out=sr_out, seed=seed)
         self.tau = tau
         if self.sr_in is not None and self.sr_in != conv.model_sr:
             self.rin = rates.StreamResampler(self.sr_in, conv.model_sr, self.dev)
@@ -446,8 +484,11 @@ class ConversionStream(_StreamState):
         plan_dev = torch.tensor([(rel, rel + lo - f0, rel + hi - f0)], dtype=torch.int64).to(self.dev)
         out = torch.empty((hi - lo) * c.spf, dtype=torch.float32, device=self.dev)
         nz = self._noise_for(f0, Tw)
+        seed = None
+        if self._seed is not None:
+            nz, seed = None, [nz]
         c._launch(self._buf[:self._len], self._len, plan_dev, plan_dev[:, 0].contiguous(), Tw, self.src_se, self.tgt_se,
-                  self.tau, nz, out, rel + lo - f0)
+                  self.tau, nz, out, rel + lo - f0, **noise_mod.kw(seed))
         self._emitted = hi
         return out
 
@@ -487,8 +528,9 @@ class StreamPool:
     window of every open stream in ``ceil(R / max_windows_per_launch)`` launches (fewer per stream than one launch per
     window, which is what the solo ``ConversionStream`` costs).
 
-    ``open(src_se, tgt_se, noise=None)`` -> a handle (per-stream embeddings; ``noise`` ``[1, inter, >= T]`` or None:
-    drawn lazily per stream); ``push(h, samples)`` only buffers (a host -> device copy); ``step()`` -> ``{handle: newly
+    ``open(src_se, tgt_se, noise=None, seed=None)`` -> a handle (per-stream embeddings; ``noise`` ``[1, inter, >= T]``,
+    or ``seed``: the counter-based noise of ``(seed, 0)`` / of a pair, or neither: drawn lazily per stream); ``push(h,
+    samples)`` only buffers (a host -> device copy); ``step()`` -> ``{handle: newly
     finished samples}`` (device tensors, views of one packed output) for the streams with output; ``close(h)`` marks the
     end of h's input -- its last window(s) run in the next ``step()``, which retires h.  A window becomes ready exactly
     when it would in ``ConversionStream`` (the same ``_need`` / ``_tail_plan``), so each stream's concatenated output
@@ -532,8 +574,8 @@ class StreamPool:
         c = self.conv
         return (c.window_frames - 1) * c.hop + c.n_fft - c.pad
 
-    def open(self, src_se, tgt_se, noise=None, sr_in=None, sr_out=None):
-        st = _StreamState(self.conv, src_se, tgt_se, noise, sr_in=sr_in, sr_out=sr_out)
+    def open(self, src_se, tgt_se, noise=None, sr_in=None, sr_out=None, *, seed=None):
+        st = _StreamState(self.conv, src_se, tgt_se, noise, sr_in=sr_in, sr_out=sr_out, seed=seed)
         msr = self.conv.model_sr
         if st.sr_in is not None and st.sr_in != msr:
             st.rin = self._rin.open(st.sr_in, msr)

@@ -12,6 +12,7 @@ import weakref
 import torch
 from torch import nn
 
+from . import noise as noise_mod
 from .engine import ConverterEngine, validate_config
 from .params import converter_param_spec, tts_full_param_spec
 
@@ -96,9 +97,12 @@ class SynthesizerTrn(nn.Module):
             self._engine_key = key
         return self._engine
 
-    def voice_conversion(self, y, y_lengths, sid_src, sid_tgt, tau=1.0, noise=None, graph=False, skip_padding=False):
+    def voice_conversion(self, y, y_lengths, sid_src, sid_tgt, tau=1.0, noise=None, graph=False, skip_padding=False, *,
+                         seed=None):
         """reference: openvoice/models.py:492-499; ``noise`` is the explicit form of the
-        reference's ``randn_like`` draw (optional).  ``graph=True`` replays the launch sequence of this
+        reference's ``randn_like`` draw (optional), ``seed`` the counter-based one (``noise.py``: an int ``s`` gives
+        row ``b`` the stream ``(s, b)``; or one seed / pair per row).  ``graph=True`` replays the launch sequence of
+        this
         (B, T, tau) shape from a captured HIP graph (``engine.GraphedConversion``); the returned tensors are
         then static buffers, valid until the next graphed call of the same shape.  ``skip_padding=True`` (ragged
         batches): the generator computes only ``length + limit_margin`` (16-20) frames per utterance -- valid samples
@@ -108,16 +112,19 @@ class SynthesizerTrn(nn.Module):
             eng = eng.core      # a TTS checkpoint also carries enc_q / flow / dec
         if graph:
             g = eng.graphed(y.shape[0], y.shape[2], tau, sid_src.shape[0], sid_tgt.shape[0], skip_padding=skip_padding)
-            return g(y, y_lengths, sid_src, sid_tgt, noise=noise)
-        return eng.voice_conversion(y, y_lengths, sid_src, sid_tgt, tau=tau, noise=noise, skip_padding=skip_padding)
+            return g(y, y_lengths, sid_src, sid_tgt, noise=noise, **noise_mod.kw(seed))
+        return eng.voice_conversion(y, y_lengths, sid_src, sid_tgt, tau=tau, noise=noise, skip_padding=skip_padding,
+                                    **noise_mod.kw(seed))
 
     def voice_conversion_windowed(self, y, sid_src, sid_tgt, tau=1.0, noise=None, window_frames=None,
-                                  windows_per_launch=None, n_fft=1024, hop_length=256, graph=False):
+                                  windows_per_launch=None, n_fft=1024, hop_length=256, graph=False, *, seed=None):
         """``voice_conversion`` of ONE recording of any length, from its waveform ``y`` ([N] or [1, N], float32 at the
         model rate): what ``spectrogram_torch`` + ``voice_conversion`` compute in one pass (reference:
         openvoice/api.py:145-147, models.py:492-499), as overlapping windows of ``window_frames`` frames
         (``longform.WindowedConverter``) so that device memory is bounded by the window and there is no length limit.
-        ``noise`` ``[1, 192, >= T]`` (None: drawn on the device like the one-pass path).  Returns ``o_hat [1, 1, 256 T]``."""
+        ``noise`` ``[1, 192, >= T]`` (None: drawn on the device like the one-pass path), or ``seed`` (an int: stream
+        ``(seed, 0)``, or a pair): then the result equals the one-pass ``voice_conversion(seed=...)``'s within the
+        windows' own contract, with no noise tensor held.  Returns ``o_hat [1, 1, 256 T]``."""
         from . import longform
         if self.n_speakers != 0:
             raise RuntimeError("voice_conversion_windowed() needs the converter model (n_speakers == 0)")
@@ -126,14 +133,16 @@ class SynthesizerTrn(nn.Module):
             window_frames=longform.DEFAULT_WINDOW_FRAMES if window_frames is None else window_frames,
             windows_per_launch=longform.DEFAULT_WINDOWS_PER_LAUNCH if windows_per_launch is None else windows_per_launch,
             graph=graph)
-        return conv.convert(y, sid_src, sid_tgt, tau=tau, noise=noise).view(1, 1, -1)
+        return conv.convert(y, sid_src, sid_tgt, tau=tau, noise=noise, **noise_mod.kw(seed)).view(1, 1, -1)
 
     def infer(self, x, x_lengths, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1., sdp_ratio=0.2,
-              max_len=None, noise_w=None, noise_z=None, skip_padding=False):
+              max_len=None, noise_w=None, noise_z=None, skip_padding=False, *, seed=None):
         """reference: openvoice/models.py:467-490; ``noise_w`` / ``noise_z`` are the explicit forms of the
-        reference's two RNG draws (optional).  Returns ``(o, attn, y_mask, (z, z_p, m_p, logs_p))``."""
+        reference's two RNG draws (optional); ``seed`` draws both counter-based (``noise.py``: row ``b`` of an int
+        ``s`` is stream ``(s, b)``, ``noise_w`` purpose 1 over the tokens, ``noise_z`` purpose 2 over the frames).
+        Returns ``(o, attn, y_mask, (z, z_p, m_p, logs_p))``."""
         if self.n_speakers == 0:
             raise RuntimeError("infer() needs the TTS model (n_speakers > 0); this is the converter variant")
         return self.engine().infer(x, x_lengths, sid, noise_scale=noise_scale, length_scale=length_scale,
                                    noise_scale_w=noise_scale_w, sdp_ratio=sdp_ratio, max_len=max_len,
-                                   noise_w=noise_w, noise_z=noise_z, skip_padding=skip_padding)
+                                   noise_w=noise_w, noise_z=noise_z, skip_padding=skip_padding, **noise_mod.kw(seed))

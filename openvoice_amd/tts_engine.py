@@ -20,6 +20,7 @@ import math
 import torch
 
 from . import _lib
+from . import noise as noise_mod
 from ._lib import F_MASK_V, LN_POST_GELU, LN_PRE_RELU
 from .engine import ConverterEngine, PackedConv, on_own_device, padded_frames
 from .params import ATTN_WINDOW, SDP_DDS_LAYERS, SDP_FLOWS, SDP_KERNEL, SDP_NUM_BINS, SDP_TAIL_BOUND
@@ -141,14 +142,19 @@ class TtsEngine:
     @torch.no_grad()
     @on_own_device
     def infer(self, tokens, lengths, sid, noise_scale=1.0, length_scale=1.0, noise_scale_w=1.0, sdp_ratio=0.2,
-              max_len=None, noise_w=None, noise_z=None, return_attn=True, skip_padding=False):
+              max_len=None, noise_w=None, noise_z=None, return_attn=True, skip_padding=False, *, seed=None):
         """Same contract as the reference (models.py:467-490): returns
         ``(o [B,1,256*Ty'], attn [B,1,Ty,Tx], y_mask [B,1,Ty], (z, z_p, m_p, logs_p) [B,192,Ty])``.
         ``noise_w`` [B,2,Tx] / ``noise_z`` [B,192,>=Ty] replace the reference's two RNG draws when given.
+        ``seed`` (instead of them): both draws counter-based (``noise.py``), row ``b`` of an int ``s`` on stream
+        ``(s, b)`` (or one seed / pair per row): ``noise_w`` is purpose 1 over the token positions ``[0, Tx)``,
+        ``noise_z`` purpose 2 over the frames ``[0, Ty)``, generated straight into the workspace rows once ``Ty`` is
+        known -- nobody has to guess a bound for it.
         ``skip_padding``: the generator computes only ``y_length + core.limit_margin(B, Ty)`` frames (16-20) of each
         utterance of a padded batch
         (valid samples bit-identical, the padded tail of ``o`` zero; ``ConverterEngine.voice_conversion``)."""
         dev = self.device
+        noise_mod.exclusive(seed, noise_w=noise_w, noise_z=noise_z)
         check_token_count(tokens.shape[-1])
         tokens = tokens.to(dev, torch.int64).contiguous()
         lengths = lengths.to(dev, torch.int64).contiguous()
@@ -198,7 +204,12 @@ class TtsEngine:
         self._dds(self.sdp_convs, xs, t1, t2, mask, B, Fs, Tx, Lx)
         self._conv(self.sdp_proj, xs, Fs, t1, Fs, B, Tx, Lx, flags=F_MASK_V, mask=mask, mask_bs=Lx)
         xs, t1 = t1, xs                                                         # xs = conditioning of the flows
-        if noise_w is None:
+        if seed is not None:
+            streams = noise_mod.rows(seed, B)
+            noise_w = torch.empty(B, 2, Tx, dtype=torch.float32, device=dev)
+            noise_mod.fill([(s, k, noise_mod.PURPOSE_TTS_W, f0, Tx, b * 2 * Tx, Tx)
+                            for b, (s, k, f0) in enumerate(streams)], 2, noise_w)
+        elif noise_w is None:
             noise_w = torch.randn(B, 2, Tx, dtype=torch.float32, device=dev)
         zw = f(B, 2, Lx)
         zw[:, :, :Tx].copy_(noise_w.to(dev, torch.float32) * float(noise_scale_w))
@@ -222,9 +233,12 @@ class TtsEngine:
         ws = core._workspace(B, Ty)
         Ly, mask_y = ws["Tp"], ws["mask"]
         _lib.call("ov_sequence_mask_f32", y_len, mask_y, B, Ty, Ly)
-        if noise_z is None:
-            noise_z = torch.randn(B, C, Ty, dtype=torch.float32, device=dev)
-        ws["noise"][:, :, :Ty].copy_(noise_z[:, :, :Ty].to(dev, torch.float32))
+        if seed is not None:
+            core.seed_noise(ws["noise"], streams, B, Ty, Ly, purpose=noise_mod.PURPOSE_TTS_Z)
+        else:
+            if noise_z is None:
+                noise_z = torch.randn(B, C, Ty, dtype=torch.float32, device=dev)
+            ws["noise"][:, :, :Ty].copy_(noise_z[:, :, :Ty].to(dev, torch.float32))
         m_p, logs_p = f(B, C, Ly), f(B, C, Ly)
         attn = f(B, Ty, Tx) if return_attn else None
         z_p, z = ws["z_p"], ws["z_hat"]
