@@ -496,6 +496,32 @@ int ov_conv2d_s2_relu_f32(const float* x, const float* w, const float* bias, flo
 int ov_gru_f32(const float* gi, const float* whh_t, const float* bhh, float* h_out, int N, int H, int T,
                ov_stream_t stream);
 
+/* ---- ReferenceEncoder over a RAGGED batch (csrc/ref_enc_ragged.hip), reference openvoice/models.py:339-359 --------
+ * The three kernels above for items of different lengths in one launch: rows are `ld` floats apart for the whole
+ * batch ([N][C][F][ld], ld >= the longest item) and lens (DEVICE int32 [N]) holds each item's own number of frames.
+ * Over an item's own columns each kernel performs its dense twin's operations in the twin's order, so item n gets bit
+ * for bit what the dense entry point gives for that item alone (T = lens[n]); the columns from the item's end up to the
+ * row stride are written as 0.  A length outside [0, ld] is clamped in the kernel.  Host checks as for the dense twins
+ * (OV_E_BADARG: null pointers -- lens included --, non-positive extents, N > 65535; OV_E_UNSUPPORTED as stated).
+ * Additive to ABI 2.12: found by name, like the vad, join and noise kernels. */
+
+/* ov_layernorm_freq_f32 for columns t < lens[n] of item n (nn.LayerNorm(F), reference models.py:344); columns
+ * lens[n] <= t < ld of y are written as 0 and not read from x. */
+int ov_layernorm_freq_ragged_f32(const float* x, const float* gamma, const float* beta, const int32_t* lens, float* y,
+                                 int N, int F, int ld, float eps, ov_stream_t stream);
+
+/* ov_conv2d_s2_relu_f32 with Ti = lens_in[n] per item (models.py:314-325, :346-349): the zero padding of the 3x3
+ * stride-2 conv sits at the ITEM's end.  x [N][Cin][Fi][ld_in] -> y [N][Cout][(Fi-1)/2+1][ld_out]; output columns
+ * to < (lens_in[n]-1)/2+1 are computed, the rest up to ld_out written as 0.  ld_out >= (ld_in-1)/2+1 (OV_E_BADARG
+ * otherwise); Cout must be a multiple of 16. */
+int ov_conv2d_s2_relu_ragged_f32(const float* x, const float* w, const float* bias, const int32_t* lens_in, float* y,
+                                 int N, int Cin, int Cout, int Fi, int ld_in, int ld_out, ov_stream_t stream);
+
+/* ov_gru_f32 over lens[n] steps of item n (nn.GRU batch_first, models.py:356-357): gi [N][3H][ld], h_out [N][H] the
+ * state after the item's last true step (h0 = 0 for lens[n] = 0).  H must be 128. */
+int ov_gru_ragged_f32(const float* gi, const float* whh_t, const float* bhh, const int32_t* lens, float* h_out, int N,
+                      int H, int ld, ov_stream_t stream);
+
 /* ---- V1 base-speaker TTS front end (SynthesizerTrn.infer, reference openvoice/models.py:467-490) ----
  * Token-rate tensors are (B, C, T) fp32 with rows `ld` floats apart (ld >= T), like the frame-rate
  * tensors of the converter.  The dense 1x1 / k3 convs of this path go through ov_conv1d_f32. */

@@ -1,1 +1,1 @@
-from openvoice_amd.se_extractor import get_se, hash_numpy_array  # noqa: F401
+from openvoice_amd.se_extractor import get_se, get_se_many, hash_numpy_array  # noqa: F401

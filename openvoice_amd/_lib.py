@@ -156,6 +156,9 @@ SIGNATURES = {
     "ov_conv2d_s2_relu_f32": (ctypes.c_int, [_fp, _fp, _fp, _fp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                              ctypes.c_int, ctypes.c_int, _fp]),
     "ov_gru_f32": (ctypes.c_int, [_fp, _fp, _fp, _fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp]),
+    "ov_layernorm_freq_ragged_f32": (ctypes.c_int, [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, ctypes.c_float, _fp]),
+    "ov_conv2d_s2_relu_ragged_f32": (ctypes.c_int, [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _fp]),
+    "ov_gru_ragged_f32": (ctypes.c_int, [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _fp]),
     "ov_conv1d_bf16_pack_size": (ctypes.c_size_t, [_i, _i, _i]),
     "ov_conv1d_bf16_pack": (ctypes.c_int, [_fp, _i, _i, _i, _fp]),
     "ov_conv1d_bf16_pack16": (ctypes.c_int, [_fp, _i, _i, _i, _fp]),

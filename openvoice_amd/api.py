@@ -233,6 +233,36 @@ def bits_to_string(bits_array):
     return "".join(chr(int(v)) for v in vals)
 
 
+def plan_enrol_chunks(n_pieces, max_pieces_per_launch):
+    """The launches of ``extract_se_many``: ``[(start, end), ...]`` covering pieces ``0 .. n_pieces`` in order, each
+    chunk at most ``max_pieces_per_launch`` pieces."""
+    cap = int(max_pieces_per_launch)
+    if cap < 1:
+        raise ValueError(f"max_pieces_per_launch must be >= 1, got {max_pieces_per_launch}")
+    return [(lo, min(lo + cap, int(n_pieces))) for lo in range(0, int(n_pieces), cap)]
+
+
+def _flatten_voices(voices):
+    """``voices`` (one list of 1-D waveforms per voice) -> ``(pieces per voice, all pieces in the caller's order)``;
+    an empty list, a voice without pieces and a piece that is not 1-D or holds no sample are ValueErrors."""
+    if isinstance(voices, (str, bytes)) or not hasattr(voices, "__len__") or len(voices) == 0:
+        raise ValueError("extract_se_many: voices must be a non-empty list with one list of waveforms per voice")
+    counts, flat = [], []
+    for v, pieces in enumerate(voices):
+        if isinstance(pieces, (torch.Tensor, np.ndarray)) and pieces.ndim == 1:
+            raise ValueError(f"extract_se_many: voice {v} is a waveform, expected a list of waveforms")
+        if len(pieces) == 0:
+            raise ValueError(f"extract_se_many: voice {v} has no pieces")
+        for i, a in enumerate(pieces):
+            shape = tuple(a.shape) if hasattr(a, "shape") else (len(a),)
+            if len(shape) != 1 or shape[0] == 0:
+                raise ValueError(f"extract_se_many: piece {i} of voice {v} must be a non-empty 1-D waveform, "
+                                 f"got shape {shape}")
+            flat.append(a)
+        counts.append(len(pieces))
+    return counts, flat
+
+
 class ToneColorConverter(OpenVoiceBaseClass):
     """reference: openvoice/api.py:101-201."""
 
@@ -312,6 +342,72 @@ class ToneColorConverter(OpenVoiceBaseClass):
             for row, i in enumerate(idx):
                 embs[i] = g[row]
         return torch.stack(embs).mean(0).reshape(1, -1, 1).detach()
+
+    def _spec_ragged(self, pieces):
+        """Spectrograms of 1-D device waveforms of DIFFERENT lengths in one launch pair: ``(spec [P, bins, Tw],
+        frames)`` with ``Tw`` the longest item's frame count and ``frames[p]`` item p's own.  The pieces go into one
+        pool and ``_NativeSpectrogram.windows_multi`` frames span p as its own waveform (reflect padding at its two
+        ends, record ``(base, n_samples, 0)``), so columns ``[0, frames[p])`` of row p are the item's own spectrogram;
+        the columns beyond hold the span's reflected end followed by zeros -- defined values that the ragged
+        ReferenceEncoder never reads."""
+        from .mel_processing import native_spectrogram
+        d = self.hps.data
+        eng = native_spectrogram(self.device, d.filter_length, d.hop_length)
+        pad = (d.filter_length - d.hop_length) // 2
+        lens = [int(p.numel()) for p in pieces]
+        if min(lens) <= pad:
+            raise ValueError("waveform shorter than the reflect padding")       # as spectrogram_torch raises
+        frames = [(n + 2 * pad - d.filter_length) // d.hop_length + 1 for n in lens]
+        bases = [0]
+        for n in lens[:-1]:
+            bases.append(bases[-1] + n)
+        # one launch; the framing kernel reads the pool with scalar loads, so the bases need no alignment
+        pool = torch.cat(pieces) if len(pieces) > 1 else pieces[0].contiguous()
+        records = torch.tensor([[b, n, 0] for b, n in zip(bases, lens)], dtype=torch.int64).to(self.device)
+        return eng.windows_multi(pool, records, max(frames)), frames
+
+    @torch.no_grad()
+    def extract_se_many(self, voices, vad=False, max_pieces_per_launch=64, return_pieces=False):
+        """Enrol many voices at once: ``voices`` is a list with one entry per voice, each a list of 1-D float32
+        waveforms (arrays / tensors at the model's sampling rate, of ANY lengths) -> ``[V, gin, 1]``, row v the mean
+        reference-encoder embedding over voice v's pieces, i.e. what ``extract_se_from_audio(voices[v])`` returns
+        (pieces: the same launch-for-launch arithmetic per item; means: a sequential fp32 sum in piece order divided
+        by the count, so they agree within summation order).  All pieces of all voices, in the caller's order, are cut
+        into chunks of at most ``max_pieces_per_launch``; a chunk is ONE ragged spectrogram launch pair and ONE
+        ``reference_encoder_ragged`` launch sequence, whatever the pieces' lengths.  The result does not depend on the
+        cap (64 bounds the first conv's output, about 14 MB per 10 s piece).  ``vad=True`` removes silence from every
+        piece first, all voices in one ``remove_silence_many`` call.  ``return_pieces=True`` also returns the
+        ``[P, gin]`` piece embeddings.  ``last_extract_se_batches`` holds the chunk sizes afterwards."""
+        counts, flat = _flatten_voices(voices)
+        plan = plan_enrol_chunks(len(flat), max_pieces_per_launch)
+        pieces = [torch.as_tensor(a, dtype=torch.float32).to(self.device).reshape(-1) for a in flat]
+        if vad:
+            from . import vad as vad_mod
+            d = self.hps.data
+            pieces, _ = vad_mod.remove_silence_many(pieces, d.sampling_rate, d.hop_length)
+            if any(len(a) == 0 for a in pieces):
+                raise ValueError("extract_se(vad=True): an input holds no frame above the detector's threshold")
+        engine = self.model.engine()
+        self.last_extract_se_batches = []
+        embs = []
+        for lo, hi in plan:
+            spec, frames = self._spec_ragged(pieces[lo:hi])                  # [n, 513, Tw], one launch pair
+            embs.append(engine.reference_encoder_ragged(spec, frames))       # [n, gin], one launch sequence
+            self.last_extract_se_batches.append(hi - lo)
+        g = torch.cat(embs) if len(embs) > 1 else embs[0]
+        # per-voice mean: row P of gz is zero, and a voice with fewer pieces than the longest adds it (x + 0 = x)
+        P, width = len(flat), max(counts)
+        gz = torch.cat([g, torch.zeros(1, g.shape[1], dtype=g.dtype, device=g.device)])
+        idx, first = [], 0
+        for n in counts:
+            idx.append(list(range(first, first + n)) + [P] * (width - n))
+            first += n
+        idx = torch.tensor(idx, dtype=torch.int64).to(g.device)              # [V, width], one copy
+        acc = gz[idx[:, 0]]
+        for j in range(1, width):
+            acc = acc + gz[idx[:, j]]
+        se = (acc / torch.tensor(counts, dtype=torch.float32).to(g.device)[:, None]).unsqueeze(-1).detach()
+        return (se, g.detach()) if return_pieces else se
 
     @torch.no_grad()
     def convert_batch(self, waveforms, src_se, tgt_se, tau=0.3, noise=None, *, seed=None):

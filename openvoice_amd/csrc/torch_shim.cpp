@@ -433,6 +433,9 @@ TORCH_LIBRARY(openvoice_amd, m) {
   bind_device<&ov_layernorm_freq_f32>(m, "layernorm_freq_f32");
   bind_device<&ov_conv2d_s2_relu_f32>(m, "conv2d_s2_relu_f32");
   bind_device<&ov_gru_f32>(m, "gru_f32");
+  bind_device<&ov_layernorm_freq_ragged_f32>(m, "layernorm_freq_ragged_f32");
+  bind_device<&ov_conv2d_s2_relu_ragged_f32>(m, "conv2d_s2_relu_ragged_f32");
+  bind_device<&ov_gru_ragged_f32>(m, "gru_ragged_f32");
   bind_device<&ov_embed_f32>(m, "embed_f32");
   bind_device<&ov_layernorm_ch_f32>(m, "layernorm_ch_f32");
   bind_device<&ov_rel_attention_f32>(m, "rel_attention_f32");

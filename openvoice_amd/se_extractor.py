@@ -92,3 +92,61 @@ def get_se(audio_path, vc_model, target_dir="processed", vad=True):
     if len(audio_segs) == 0:
         raise NotImplementedError("No audio segments found!")
     return vc_model.extract_se(audio_segs, se_save_path=se_path), audio_name
+
+
+def _write_pieces(audio, sr, audio_name, target_dir, split_seconds=10.0):
+    """The cut of ``split_audio_vad`` / ``split_audio_equal``: ``round(dur / 10)`` pieces between ``np.linspace``
+    bounds, written under ``target_dir/<audio_name>/wavs``.  Returns the folder."""
+    wavs_folder = os.path.join(target_dir, audio_name, "wavs")
+    os.makedirs(wavs_folder, exist_ok=True)
+    num_splits = int(np.round(len(audio) / float(sr) / split_seconds))
+    assert num_splits > 0, "input audio is too short"
+    bounds = np.linspace(0, len(audio), num_splits + 1).astype(np.int64)
+    for i in range(num_splits):
+        audio_io.write(os.path.join(wavs_folder, f"{audio_name}_seg{i}.wav"), audio[bounds[i]:bounds[i + 1]], sr)
+    return wavs_folder
+
+
+def get_se_many(audio_paths, vc_model, target_dir="processed", vad=True):
+    """``get_se`` for many recordings with shared launches: ``[(se [1,gin,1], audio_name), ...]`` in the order of
+    ``audio_paths``, each pair and the files under ``target_dir/<audio_name>`` (the pieces under ``wavs``, ``se.pth``)
+    what ``get_se(path, vc_model, target_dir, vad)`` produces for that path.  All recordings are decoded first; with
+    ``vad=True`` their silence is removed in ONE ``vad.remove_silence_many`` call; the pieces are cut and written as
+    ``split_audio_vad`` / ``split_audio_equal`` do and read back from the files (the WAV round trip is part of what
+    ``get_se`` computes); then ONE ``vc_model.extract_se_many`` call embeds every piece of every recording, whatever
+    their lengths, and averages per recording."""
+    import torch
+    if isinstance(audio_paths, (str, bytes)) or len(audio_paths) == 0:
+        raise ValueError("get_se_many: audio_paths must be a non-empty list of paths")
+    version = vc_model.version
+    print("OpenVoice version:", version)
+    data = vc_model.hps.data
+    sr = int(data.sampling_rate)
+    names = [f"{os.path.basename(p).rsplit('.', 1)[0]}_{version}_{hash_numpy_array(p)}" for p in audio_paths]
+    if vad:
+        from . import vad as vad_mod
+        audios = [audio_io.load_to_device(p, sr, vc_model.device) for p in audio_paths]
+        kept, segments = vad_mod.remove_silence_many(audios, sr, int(data.hop_length))
+        actives = []
+        for active, segs in zip(kept, segments):
+            print([(s / sr, e / sr) for s, e in segs])
+            actives.append(active.cpu().numpy())
+            print(f"after vad: dur = {len(actives[-1]) / float(sr)}")
+    else:
+        actives = [audio_io.load(p, sr=sr)[0] for p in audio_paths]
+    voices = []
+    for audio, name in zip(actives, names):
+        wavs_folder = _write_pieces(audio, sr, name, target_dir)
+        audio_segs = sorted(glob(f"{wavs_folder}/*.wav"))
+        if len(audio_segs) == 0:
+            raise NotImplementedError("No audio segments found!")
+        voices.append([audio_io.load_to_device(f, sr, vc_model.device) for f in audio_segs])
+    gs = vc_model.extract_se_many(voices)
+    out = []
+    for v, name in enumerate(names):
+        se = gs[v:v + 1].clone()
+        se_path = os.path.join(target_dir, name, "se.pth")
+        os.makedirs(os.path.dirname(se_path), exist_ok=True)
+        torch.save(se.cpu(), se_path)
+        out.append((se, name))
+    return out
