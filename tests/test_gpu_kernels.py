@@ -3,6 +3,9 @@ called through the C ABI.  Run on the MI355X box: ``pytest -m gpu``.
 
 Tolerances: fp32 MFMA is an exact fmaf chain, so the only difference from the CPU reference is
 summation order; bounds below are ~1e-5 relative to the output scale (stated per test).
+
+The frame-rate epilogues (GATE, RESSKIP, COUPLE, POSTERIOR, CONVT, MAGNITUDE, frame-rate LINEAR) are also held, instance by
+instance and element by element, to float64 mirrors in tests/test_gpu_frame_kernels.py (oracle/fp32_ref.py).
 """
 import ctypes
 

@@ -3,6 +3,9 @@
 
 Tolerance: 2e-5 of the output scale -- fp32 MFMA is an exact fmaf chain (summation order differs from the CPU's);
 the gate uses v_exp_f32 / v_rcp_f32 (1 ulp) instead of libm tanhf / expf.
+
+tests/test_gpu_frame_kernels.py holds the same launches to a float64 mirror on every element (oracle/fp32_ref.py), at
+saturated, overflowing and exactly-zero gate arguments too.
 """
 import pytest
 import torch
