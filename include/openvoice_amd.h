@@ -387,6 +387,33 @@ int ov_vad_compact_f32(const float* pool, int64_t pool_len, const int64_t* recor
 int ov_join_segments_f32(const float* src, int64_t src_elems, const int64_t* records, int R, float* dst,
                          int64_t dst_elems, int64_t max_span, ov_stream_t stream);
 
+/* ---- a ragged batch on the bf16 generator as dense length groups (csrc/ragged_bf16.hip, openvoice_amd/bf16.py) --------
+ * Stand in for the generator of reference openvoice/models.py:272-291 applied to a PADDED batch (models.py:488:
+ * `self.dec((z * y_mask)[:, :, :max_len], g=g)` computes every item at the longest item's length): GeneratorBf16.
+ * decode_groups sorts the items by length, cuts them into a few groups and runs each group as a dense [B_g][L_g][C]
+ * bf16 tensor of its own length.  These two record-driven launches are the hand-over between the fp32 channels-first
+ * rows the flow leaves (item b: [C][ld], cols_b valid columns) and the groups' dense tensors; one launch each way serves
+ * every item of every group.  Offsets are in elements relative to src / dst, 64-bit.
+ *   ov_pack_groups_cl_bf16: records is a DEVICE int64 [n][5] of (src_off, src_ld, dst_off, cols, L);
+ *       dst[dst_off + l * C + c] = bf16(src[src_off + c * src_ld + l]),  l < cols, c < C;      0,  cols <= l < L:
+ *     round to nearest even with NaN -> 0x7fc0, the bits of torch's `.to(torch.bfloat16)` and of
+ *     ov_rows_f32_to_cl_bf16.  The source columns >= cols are NOT read (in a workspace row they are stale, possibly
+ *     NaN).  Any cols >= 0 and L >= 1.  A transpose tiled through LDS: the fp32 side moves as 16-byte vectors when src
+ *     is 16-byte aligned and src_off and src_ld are multiples of 4 (a vector that would cross column `cols` moves as
+ *     scalars), the bf16 side as 16-byte vectors when dst is 16-byte aligned and dst_off a multiple of 8.
+ *   ov_unpack_groups_f32: records is a DEVICE int64 [n][4] of (src_off, dst_off, keep, row);
+ *       dst[dst_off + j] = src[src_off + j],  j < keep;      dst[dst_off + j] = 0,  keep <= j < row.
+ *     16-byte stores on the destination's own 16-byte grid, loads at the source's alignment, scalars at the edges.
+ * Records must not overlap in dst; nothing outside the records' spans is written.  Host checks (OV_E_BADARG): null
+ * pointers, n outside [0, 65535] (n = 0 launches nothing), src_len / dst_len <= 0, C not a positive multiple of 8;
+ * src / dst not aligned to their element size (OV_E_ALIGN).  The kernels check every record: one with a negative
+ * field, L < 1, cols > L or keep > row, or that would read outside [0, src_len) or write outside [0, dst_len), reads
+ * nothing and writes nothing.  Additive to ABI 2.12: found by name, like ov_join_segments_f32. */
+int ov_pack_groups_cl_bf16(const float* src, int64_t src_len, const int64_t* records, int n, int C, uint16_t* dst,
+                           int64_t dst_len, ov_stream_t stream);
+int ov_unpack_groups_f32(const float* src, int64_t src_len, const int64_t* records, int n, float* dst, int64_t dst_len,
+                         ov_stream_t stream);
+
 /* ---- counter-based Gaussian noise (csrc/noise.hip, openvoice_amd/noise.py) -------------------------------------------
  * Stands in for the reference's torch.randn / randn_like draws (openvoice/models.py:220, :476, :486) where a caller
  * asks for `seed=`: the value at (seed, stream, purpose, channel c, frame t) is a pure function of those five numbers,
@@ -790,7 +817,7 @@ int ov_conv1d_wino_pack_f32(const float* w, int Cout, int Cin, int K, float* dst
  * was `reserved`; the struct grew by one pointer at its end).  2.06: ov_polyphase_fir_f32.  2.07: ov_conv1d_wino_f32 (+ _supported, _chunk,
  * _pack_size, _pack_f32).  2.08: ov_conv1d_wino_f32 instances for Cout % 32 == 0 at K = 11 (one 32-row fragment per
  * workgroup; ov_conv1d_wino_chunk(11, 32) = 2 where 2.07 returned 0).  2.09: ov_conv1d_wino_params.out_slope (the field that
- * was `reserved0`: same size and offset, 0 = none).  2.10: ov_frame_hops_windows_f32, ov_stitch_window_cores_f32.  2.11: ov_frame_hops_multi_f32.  2.12: ov_carry_rows_f32 (and, added later within 2.12 without a version change, ov_polyphase_fir_rows_f32 and ov_vad_frame_energy_f32, ov_vad_segments_i32, ov_vad_compact_f32, ov_rows_f32_to_cl_bf16, ov_cl_bf16_to_rows_f32: additive symbols, which the Python binding looks up by name when it loads the library; likewise ov_wn_layer_wino_f32, ov_wn_layer_wino_tile, ov_wn_wino_pack_size and ov_wn_wino_pack_f32, and ov_join_segments_f32).  The Python binding
+ * was `reserved0`: same size and offset, 0 = none).  2.10: ov_frame_hops_windows_f32, ov_stitch_window_cores_f32.  2.11: ov_frame_hops_multi_f32.  2.12: ov_carry_rows_f32 (and, added later within 2.12 without a version change, ov_polyphase_fir_rows_f32 and ov_vad_frame_energy_f32, ov_vad_segments_i32, ov_vad_compact_f32, ov_rows_f32_to_cl_bf16, ov_cl_bf16_to_rows_f32: additive symbols, which the Python binding looks up by name when it loads the library; likewise ov_wn_layer_wino_f32, ov_wn_layer_wino_tile, ov_wn_wino_pack_size and ov_wn_wino_pack_f32, and ov_join_segments_f32, and ov_pack_groups_cl_bf16 and ov_unpack_groups_f32).  The Python binding
  * refuses a library older than the entry points it calls (openvoice_amd/_lib.py MIN_VERSION). */
 int ov_version(void);
 /* The version THIS header describes.  Parameter structs grow at their END in minor versions (2.04, 2.05, 2.07 did): a

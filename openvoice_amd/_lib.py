@@ -191,6 +191,8 @@ SIGNATURES = {
                                            _fp]),
     "ov_vad_compact_f32": (ctypes.c_int, [_fp, _i64, _fp, _i, _i, _i, _fp, _fp, _fp, _fp, _i64, _fp]),
     "ov_join_segments_f32": (ctypes.c_int, [_fp, _i64, _fp, _i, _fp, _i64, _i64, _fp]),
+    "ov_pack_groups_cl_bf16": (ctypes.c_int, [_fp, _i64, _fp, _i, _i, _fp, _i64, _fp]),
+    "ov_unpack_groups_f32": (ctypes.c_int, [_fp, _i64, _fp, _i, _fp, _i64, _fp]),
     "ov_normal_philox_f32": (ctypes.c_int, [_fp, _i, _i, _fp, _i64, _i64, _fp]),
     "ov_embed_f32": (ctypes.c_int, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, ctypes.c_float, _fp]),
     "ov_layernorm_ch_f32": (ctypes.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, ctypes.c_float, _i, _fp]),
@@ -212,6 +214,24 @@ _lib = None
 
 class OvError(RuntimeError):
     pass
+
+
+GENERATORS = ("fp32", "bf16")
+
+
+def check_generator(generator, optional=False):
+    """The ``generator=`` keyword of the TTS, cloning and conversion entry points: ``"fp32"`` or ``"bf16"`` (and None
+    where ``optional``: follow the engine's ``use_bf16_generator`` switch); anything else is an ``OvError``."""
+    if generator is None and optional:
+        return None
+    if not isinstance(generator, str) or generator not in GENERATORS:
+        raise OvError(f"generator must be 'fp32' or 'bf16'{' (or None)' if optional else ''}, got {generator!r}")
+    return generator
+
+
+def generator_kw(generator):
+    """``{"generator": g}`` for a callee that takes the keyword, nothing when the caller left it at None."""
+    return {} if generator is None else {"generator": generator}
 
 
 def load():

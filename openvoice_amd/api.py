@@ -22,7 +22,7 @@ import re
 import numpy as np
 import torch
 
-from . import audio_io, longform, rates, utils
+from . import _lib, audio_io, longform, rates, utils
 from . import noise as noise_mod
 from .mel_processing import spectrogram_torch
 from .models import SynthesizerTrn
@@ -118,14 +118,16 @@ class BaseSpeakerTTS(OpenVoiceBaseClass):
 
     @torch.no_grad()
     def infer_padded(self, id_sequences, speaker_id, speed=1.0, noise_scale=0.667, noise_scale_w=0.6, noise_w=None,
-                     noise_z=None, *, seed=None):
+                     noise_z=None, *, seed=None, generator="fp32"):
         """One padded ``infer(..., skip_padding=True)`` over already-tokenised sentences, results left on the device:
         ``(o [B, 1, ld], frames [B] int64)`` -- row b holds ``frames[b] * hop`` samples, what lies beyond them in the
         row is padding.  ``noise_w`` / ``noise_z``: None or one ``[2, Tx_b]`` / ``[192, >= Ty_b]`` per sentence (the
         explicit forms of ``infer``'s two draws; in the batch each is zero-padded to the widest); ``seed`` (instead of
         them): counter-based noise (``noise.py``), an int ``s`` giving sentence ``i`` the stream ``(s, i)``, or a list
-        with one seed / pair per sentence.  This is the launch
+        with one seed / pair per sentence.  ``generator``: ``"fp32"`` (default) or ``"bf16"`` -- the generator on the
+        bf16 kernels, the ragged batch as dense length groups (``TtsEngine.infer``).  This is the launch
         sequence behind ``tts_from_ids(batched=True)`` and ``clone.VoiceCloner``."""
+        _lib.check_generator(generator)
         noise_mod.exclusive(seed, noise_w=noise_w, noise_z=noise_z)
         device = self.device
         seqs = [torch.as_tensor(s, dtype=torch.long).reshape(-1) for s in id_sequences]
@@ -147,12 +149,18 @@ class BaseSpeakerTTS(OpenVoiceBaseClass):
         # samples returned below are bit-identical either way)
         o, _, y_mask, _ = self.model.infer(x.to(device), lengths.to(device), sid=sid.to(device), noise_scale=noise_scale,
                                            noise_scale_w=noise_scale_w, length_scale=1.0 / speed, noise_w=noise_w,
-                                           noise_z=noise_z, skip_padding=True, **noise_mod.kw(seed))
+                                           noise_z=noise_z, skip_padding=True, **noise_mod.kw(seed),
+                                           **self._generator_kw(generator))
         return o, y_mask[:, 0].sum(1).long()
+
+    @staticmethod
+    def _generator_kw(generator):
+        """The keyword for ``infer``, left out for the default so that the fp32 call is today's call."""
+        return {} if generator == "fp32" else {"generator": generator}
 
     @torch.no_grad()
     def tts_from_ids(self, id_sequences, speaker_id, speed=1.0, batched=False, noise_scale=0.667,
-                     noise_scale_w=0.6, noise_w=None, noise_z=None, *, seed=None):
+                     noise_scale_w=0.6, noise_w=None, noise_z=None, *, seed=None, generator="fp32"):
         """Synthesize already-tokenised sentences (symbol ids, blanks interspersed by the caller if the
         config asks for it).  ``batched=False`` runs one ``infer`` per sentence exactly as the reference loop
         (api.py:78-94); ``batched=True`` pads them into one batch (one pass over the GPU; because the
@@ -161,7 +169,9 @@ class BaseSpeakerTTS(OpenVoiceBaseClass):
         ``[192, >= Ty]`` tensor per sentence, passed on to ``infer``.  ``seed`` (instead of them): counter-based noise,
         an int ``s`` giving sentence ``i`` the stream ``(s, i)`` in the batched and in the per-sentence loop alike (so
         both draw the same durations), or a list with one seed / pair per sentence; a seeded call is reproducible
-        without anyone guessing ``Ty``.  Returns a list of float32 numpy waveforms."""
+        without anyone guessing ``Ty``.  ``generator``: ``"fp32"`` (default) or ``"bf16"``, the generator's kernels in
+        either loop (``TtsEngine.infer``).  Returns a list of float32 numpy waveforms."""
+        _lib.check_generator(generator)
         noise_mod.exclusive(seed, noise_w=noise_w, noise_z=noise_z)
         device = self.device
         hop = self.hps.data.hop_length
@@ -177,11 +187,13 @@ class BaseSpeakerTTS(OpenVoiceBaseClass):
                 o = self.model.infer(s[None].to(device), torch.LongTensor([s.numel()]).to(device),
                                      sid=torch.LongTensor([speaker_id]).to(device), noise_scale=noise_scale,
                                      noise_scale_w=noise_scale_w, length_scale=1.0 / speed, noise_w=row(noise_w, i),
-                                     noise_z=row(noise_z, i), **noise_mod.kw(seeds[i]))[0]
+                                     noise_z=row(noise_z, i), **noise_mod.kw(seeds[i]),
+                                     **self._generator_kw(generator))[0]
                 out.append(o[0, 0].data.cpu().float().numpy())
             return out
         o, frames = self.infer_padded(id_sequences, speaker_id, speed=speed, noise_scale=noise_scale,
-                                      noise_scale_w=noise_scale_w, noise_w=noise_w, noise_z=noise_z, **noise_mod.kw(seed))
+                                      noise_scale_w=noise_scale_w, noise_w=noise_w, noise_z=noise_z, **noise_mod.kw(seed),
+                                      **self._generator_kw(generator))
         frames = frames.cpu().tolist()
         o = o[:, 0].data.cpu().float().numpy()
         return [o[i, :frames[i] * hop] for i in range(len(frames))]
@@ -199,12 +211,14 @@ class BaseSpeakerTTS(OpenVoiceBaseClass):
             ids.append(self.get_text(t, self.hps, False))
         return ids
 
-    def tts(self, text, output_path, speaker, language="English", speed=1.0, batched=False, *, seed=None):
+    def tts(self, text, output_path, speaker, language="English", speed=1.0, batched=False, *, seed=None,
+            generator="fp32"):
         """reference: openvoice/api.py:73-98.  ``seed``: as for ``tts_from_ids`` (sentence ``i`` on stream ``(seed,
-        i)``)."""
+        i)``); ``generator``: ``"fp32"`` (default) or ``"bf16"``, as for ``tts_from_ids``."""
+        _lib.check_generator(generator)
         ids = self.text_to_ids(text, language)
         audio_list = self.tts_from_ids(ids, self.hps.speakers[speaker], speed=speed, batched=batched,
-                                       **noise_mod.kw(seed))
+                                       **noise_mod.kw(seed), **self._generator_kw(generator))
         audio = self.audio_numpy_concat(audio_list, sr=self.hps.data.sampling_rate, speed=speed)
         if output_path is None:
             return audio
@@ -624,7 +638,7 @@ class ToneColorConverter(OpenVoiceBaseClass):
 
     def convert_many(self, items, src_se, tgt_se, tau=0.3, window_frames=longform.DEFAULT_WINDOW_FRAMES,
                      windows_per_launch=longform.DEFAULT_MANY_WINDOWS_PER_LAUNCH, noise=None, output_paths=None,
-                     message="default", sr=None, out_sr=None, *, seed=None):
+                     message="default", sr=None, out_sr=None, *, seed=None, generator=None):
         """``convert_long`` of many recordings with their windows packed ACROSS recordings into launches of up to
         ``windows_per_launch`` (``longform.WindowedConverter.convert_many``).  ``items``: file paths (any rate, decoded
         and resampled like ``convert_long``) or 1-D waveforms at ``sr`` Hz (None: the model rate; one rate, or a list
@@ -635,7 +649,9 @@ class ToneColorConverter(OpenVoiceBaseClass):
         gives item ``i`` the stream ``(s, i)``, or a list with one seed / pair per item.  Returns a list of numpy
         arrays (watermark hook applied
         per item, at the model rate), or writes ``output_paths[i]`` (at its ``out_sr``) instead.  Each item equals
-        ``convert_long`` of it with the same ``window_frames``, noise and rates."""
+        ``convert_long`` of it with the same ``window_frames``, noise and rates.  ``generator`` (keyword only): None
+        follows ``use_bf16_generator``, ``"fp32"`` / ``"bf16"`` choose the generator's kernels for this call."""
+        _lib.check_generator(generator, optional=True)
         hps = self.hps
         msr = hps.data.sampling_rate
         items = list(items)
@@ -656,7 +672,8 @@ class ToneColorConverter(OpenVoiceBaseClass):
         paths = [isinstance(x, (str, os.PathLike)) for x in items]
         waves = rates.resample_many(waves, [(None, None) if p else (r, msr) for p, r in zip(paths, srs)], self.device)
         outs = self._windowed(window_frames, windows_per_launch).convert_many(waves, srcs, tgts, tau=tau, noises=noise,
-                                                                              **noise_mod.kw(seed, "seeds"))
+                                                                              **noise_mod.kw(seed, "seeds"),
+                                                                              **_lib.generator_kw(generator))
         if self.watermark_model is None:
             outs = rates.resample_many(outs, [(msr, r) for r in out_srs], self.device)
             audios = [o.cpu().numpy() for o in outs]

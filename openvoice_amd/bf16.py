@@ -154,6 +154,112 @@ def generator_alg_bytes(cfg, B, T, esize=2, z_channels=192, fused=True):
     return total + B * L * ch * esize + B * L * 4
 
 
+# ---- a ragged batch as dense length groups (csrc/ragged_bf16.hip) -------------------------------------------------------
+MAX_GROUPS_CAP = 8              # the launch count of decode_groups stays bounded: at most 8 passes over the generator
+# Defaults of GeneratorBf16.max_groups / .group_cost, measured on an MI355X (tools/bf16_groups_table.py, DESIGN section
+# 20): a B = 1, T = 1 decode -- one more pass over the ~80 launches, whatever its size -- takes 0.697 ms, an item-frame
+# of a B = 64, T = 861 decode 0.625 us: one more group costs what 1114 item-frames cost.  On the V1 TTS batch (16 x 100
+# symbols, 191 .. 328 frames, 5248 padded item-frames) no cut saves that much, the planner keeps one group and the
+# grouped run equals the padded one (8.56 against 8.54 ms): grouping is NOT faster there, so the default is one group.
+DEFAULT_MAX_GROUPS = 1
+DEFAULT_GROUP_COST = 1100       # item-frames one more pass over the launch sequence costs
+PACK_FIELDS, UNPACK_FIELDS = 5, 4      # (src_off, src_ld, dst_off, cols, L) / (src_off, dst_off, keep, row)
+
+
+def plan_groups(lengths, Td, margin, max_groups, group_cost):
+    """Cut a ragged batch into dense groups: pure host code, a function of its arguments alone.
+
+    ``lengths[b]``: item b's own frames (clamped to ``[0, Td]``); ``Td``: the frames of the padded run; ``margin``: the
+    frames an item must be computed beyond its own length so that its first ``length`` frames do not feel the group's
+    right edge (``GeneratorBf16.margin``); ``max_groups >= 1``; ``group_cost``: what one more group costs, in
+    item-frames (rounded to an integer).  The items are sorted by length (stable: ties stay in batch order); a dynamic
+    programme over the contiguous cuts of the sorted list minimises ``sum_g(B_g * L_g) + n_groups * group_cost`` with
+    ``L_g = min(Td, longest length of the group + margin)`` over at most ``max_groups`` groups; among equal costs the
+    fewest groups, then the earliest cuts.  Returns ``[(batch indices, L_g), ...]`` in ascending length order -- a
+    partition of ``range(len(lengths))``.  One group has ``L = min(Td, longest + margin)``: ``Td`` whenever ``Td`` is
+    the longest item's length, as it is in ``infer``."""
+    Td, margin, G, gc = int(Td), int(margin), int(max_groups), int(round(group_cost))
+    if Td < 1 or margin < 0 or G < 1 or gc < 0:
+        raise ValueError(f"plan_groups: Td = {Td}, margin = {margin}, max_groups = {max_groups}, group_cost = {group_cost}")
+    lens = [min(max(int(n), 0), Td) for n in lengths]
+    if not lens:
+        return []
+    order = sorted(range(len(lens)), key=lambda b: lens[b])
+    need = [max(1, min(Td, lens[b] + margin)) for b in order]
+    # a cut between two items of equal need never pays: the runs of equal need are the units of the programme
+    ends = [j + 1 for j in range(len(need)) if j + 1 == len(need) or need[j + 1] != need[j]]
+    R = len(ends)
+    starts = [0] + ends[:-1]
+    G = min(G, R)
+    INF = float("inf")
+    best = [[INF] * R for _ in range(G + 1)]          # best[k][r]: runs 0 .. r in exactly k groups
+    cut = [[0] * R for _ in range(G + 1)]             # the first run of the last group
+    for r in range(R):
+        best[1][r] = ends[r] * need[ends[r] - 1] + gc
+    for k in range(2, G + 1):
+        for r in range(k - 1, R):
+            L = need[ends[r] - 1]
+            for i in range(k - 1, r + 1):             # the last group is runs i .. r
+                c = best[k - 1][i - 1] + (ends[r] - starts[i]) * L + gc
+                if c < best[k][r]:
+                    best[k][r], cut[k][r] = c, i
+    k = min(range(1, G + 1), key=lambda k: (best[k][R - 1], k))
+    groups, r = [], R - 1
+    while k >= 1:
+        i = cut[k][r] if k > 1 else 0
+        groups.append((order[starts[i]:ends[r]], need[ends[r] - 1]))
+        r, k = i - 1, k - 1
+    return groups[::-1]
+
+
+def plan_cost(plan, group_cost):
+    """``sum_g(B_g * L_g) + n_groups * group_cost`` of a plan, the quantity ``plan_groups`` minimises."""
+    return sum(len(idx) * L for idx, L in plan) + len(plan) * int(round(group_cost))
+
+
+def group_records(plan, lengths, Td, C, ld, spf):
+    """The two record tables of a plan, as host lists.  Item b's source row is ``z_rows[b]`` ([C][ld] fp32, offset
+    ``b * C * ld``); group g's dense bf16 tensor [B_g][L_g][C] starts at ``x_off[g]`` of the packed input arena, its
+    fp32 waveform [B_g][L_g * spf] at ``o_off[g]`` of the packed output arena; item b's row of the padded result
+    [B][Td * spf] starts at ``b * Td * spf``.  Returns ``(pack [n][5], unpack [n][4], x_off, o_off, x_elems, o_elems)``."""
+    pack, unpack, x_off, o_off, xa, oa = [], [], [], [], 0, 0
+    for idx, L in plan:
+        x_off.append(xa)
+        o_off.append(oa)
+        for j, b in enumerate(idx):
+            n = min(max(int(lengths[b]), 0), Td, L)
+            pack.append((b * C * ld, ld, xa + j * L * C, n, L))
+            unpack.append((oa + j * L * spf, b * Td * spf, n * spf, Td * spf))
+        xa += len(idx) * L * C
+        oa += len(idx) * L * spf
+    return pack, unpack, x_off, o_off, xa, oa
+
+
+def pack_groups_host(src, records, C, dst):
+    """``ov_pack_groups_cl_bf16`` restated on host tensors (``src`` flat float32, ``dst`` flat bfloat16), record checks
+    included: the layout's definition, and what the kernel is compared against."""
+    for so, sld, do, cols, L in records:
+        if min(so, sld, do, cols) < 0 or L < 1 or cols > L or do + L * C > dst.numel():
+            continue
+        if cols > 0 and so + (C - 1) * sld + cols > src.numel():
+            continue
+        rows = torch.as_strided(src, (C, cols), (sld, 1), so)
+        blk = dst[do:do + L * C].view(L, C)
+        blk[:cols] = rows.t().to(torch.bfloat16)
+        blk[cols:] = 0
+    return dst
+
+
+def unpack_groups_host(src, records, dst):
+    """``ov_unpack_groups_f32`` restated on flat float32 host tensors, record checks included."""
+    for so, do, keep, row in records:
+        if min(so, do, keep) < 0 or row < keep or so + keep > src.numel() or do + row > dst.numel():
+            continue
+        dst[do:do + keep] = src[so:so + keep]
+        dst[do + keep:do + row] = 0
+    return dst
+
+
 class GeneratorBf16:
     """HiFi-GAN generator (reference: openvoice/models.py:272-291) with bf16 activations in HBM, channels-last,
     fp32 accumulation -- BASELINE.json configs[4].  Same load-time algebra as the fp32 engine (weight-norm folded,
@@ -206,6 +312,16 @@ class GeneratorBf16:
         # per-kernel profiles harder to read: off unless asked for
         self.chain_streams = 1
         self._streams = []
+        # decode_groups: the frames an item is computed beyond its own length.  The bf16 kernels read exactly their taps
+        # (no Winograd tiles, no work lists), so this is the direct kernels' margin, not limit_margin_frames
+        from .engine import GENERATOR_MARGIN, generator_margin_frames
+        self.margin = max(GENERATOR_MARGIN, generator_margin_frames(cfg))
+        self.samples_per_frame = 1
+        for u in cfg["upsample_rates"]:
+            self.samples_per_frame *= u
+        self.max_groups, self.group_cost = DEFAULT_MAX_GROUPS, DEFAULT_GROUP_COST
+        self._arena = None
+        self.last_plan = None               # plan_groups of the last decode_groups call, for tests / logs
 
     def _side_streams(self, n):
         while len(self._streams) < n:
@@ -366,6 +482,93 @@ class GeneratorBf16:
             free = [buf for buf in ws["dec"] if buf.data_ptr() != out.data_ptr()]
             cur_x = out
         return cur_x
+
+    def _group_arena(self, x_elems, o_elems, rows_frames):
+        """The buffers of ``decode_groups``, kept across calls and only ever grown (``_workspace`` would drop its cache at
+        every new (B, T)): the groups' packed bf16 inputs and fp32 outputs, and ONE set of stage scratch sized for the
+        plan's largest group (``rows_frames`` = its B_g * L_g)."""
+        ch, L, biggest = self.cfg["upsample_initial_channel"], 1, 0
+        for u in self.cfg["upsample_rates"]:
+            ch //= 2
+            L *= u
+            biggest = max(biggest, ch * L)
+        want = dict(x=x_elems, o=o_elems, pre=rows_frames * self.cfg["upsample_initial_channel"], dec=rows_frames * biggest)
+        a = self._arena
+        if a is None or any(a["size"][k] < n for k, n in want.items()):
+            size = want if a is None else {k: max(n, a["size"][k]) for k, n in want.items()}
+            self._arena = a = None              # free the old buffers before the new ones are taken
+            f = lambda n: torch.empty(max(n, 8), dtype=torch.bfloat16, device=self.device)
+            a = dict(size=size, x=f(size["x"]), pre=f(size["pre"]), dec=[f(size["dec"]) for _ in range(5)],
+                     o=torch.empty(max(size["o"], 4), dtype=torch.float32, device=self.device))
+            self._arena = a
+        return a
+
+    @torch.no_grad()
+    def decode_groups(self, z_rows, ld, cond, lengths_host, Td, max_groups=None):
+        """``decode`` of a ragged batch as a few dense groups.  ``z_rows``: fp32 [B, inter, ld] contiguous, as the flow
+        leaves it in the workspace -- item b valid (and zero beyond its own length, the flow's mask) on its first
+        ``lengths_host[b]`` columns; the columns beyond an item's length are never read.  ``cond``: the conv_pre bias
+        rows [B or 1, ch] fp32 (``cond_rows``); ``lengths_host``: a HOST sequence of B ints; ``Td``: the frames of the
+        padded run; ``max_groups``: None = ``self.max_groups``, at most ``MAX_GROUPS_CAP``.  Returns fp32
+        [B, 1, Td * samples_per_frame]: samples ``[0, length_b * spf)`` of row b are the bits ``decode`` of the padded
+        batch ``z_rows[:, :, :Td]`` gives, every sample beyond them is zero.
+
+        One ``ov_pack_groups_cl_bf16`` launch, per group (``plan_groups``) the loop over ``stage`` that ``decode`` runs,
+        at the group's own ``L_g``, one ``ov_unpack_groups_f32`` launch; the chains of a stage stay on one stream."""
+        dev = self.device
+        B, C = int(z_rows.shape[0]), int(z_rows.shape[1])
+        ld, Td = int(ld), int(Td)
+        if (z_rows.dtype != torch.float32 or z_rows.dim() != 3 or not z_rows.is_contiguous() or z_rows.shape[2] != ld
+                or z_rows.device != dev or C != self.conv_pre.cin):
+            raise _lib.OvError(f"decode_groups: z_rows must be a contiguous float32 [B, {self.conv_pre.cin}, ld] tensor on "
+                               f"{dev}, got {tuple(z_rows.shape)} {z_rows.dtype} on {z_rows.device}")
+        lens = [int(n) for n in lengths_host]
+        if len(lens) != B or not 1 <= Td <= ld:
+            raise _lib.OvError(f"decode_groups: {len(lens)} lengths for {B} rows, Td = {Td}, ld = {ld}")
+        G = self.max_groups if max_groups is None else int(max_groups)
+        if G < 1:
+            raise _lib.OvError(f"decode_groups: max_groups = {max_groups}")
+        plan = plan_groups(lens, Td, self.margin, min(G, MAX_GROUPS_CAP), self.group_cost)
+        self.last_plan = plan
+        spf = self.samples_per_frame
+        pack, unpack, x_off, o_off, x_elems, o_elems = group_records(plan, lens, Td, C, ld, spf)
+        arena = self._group_arena(x_elems, o_elems, max(len(idx) * L for idx, L in plan))
+        # one host -> device copy: both record tables and the batch order of the plan
+        order = [b for idx, _ in plan for b in idx]
+        table = torch.tensor([v for r in pack for v in r] + [v for r in unpack for v in r] + order,
+                             dtype=torch.int64).to(dev)
+        n_pack, n_unpack = B * PACK_FIELDS, B * UNPACK_FIELDS
+        _lib.call("ov_pack_groups_cl_bf16", z_rows, z_rows.numel(), table[:n_pack], B, C, arena["x"],
+                  arena["x"].numel())
+        cond = cond.to(dev, torch.float32)
+        if cond.shape[0] == 1:
+            cond_sorted = cond.reshape(1, -1).expand(B, -1).contiguous()
+        else:
+            cond_sorted = cond.reshape(B, -1).index_select(0, table[n_pack + n_unpack:])
+        at = 0
+        for (idx, L), xo, oo in zip(plan, x_off, o_off):
+            Bg = len(idx)
+            x = arena["x"][xo: xo + Bg * L * C].view(Bg, L, C)
+            out = arena["o"][oo: oo + Bg * L * spf].view(Bg, 1, L * spf)
+            self._decode_dense(x, cond_sorted[at:at + Bg], out, Bg, L, arena["dec"], arena["pre"])
+            at += Bg
+        o = torch.empty(B, 1, Td * spf, dtype=torch.float32, device=dev)
+        _lib.call("ov_unpack_groups_f32", arena["o"], arena["o"].numel(), table[n_pack:n_pack + n_unpack], B, o, o.numel())
+        return o
+
+    def _decode_dense(self, x, cond, out, B, L, dec, pre):
+        """The stage loop of ``decode`` on caller-given buffers: ``x`` bf16 [B, L, inter], ``cond`` [B, ch] (contiguous
+        rows), ``out`` fp32 [B, 1, L * spf], ``dec`` five flat bf16 scratch buffers, ``pre`` the conv_pre output."""
+        ch = self.cfg["upsample_initial_channel"]
+        cur_x, free = x, list(dec)
+        for i, up in enumerate(self.ups):
+            s = up["stride"]
+            ch //= 2
+            o = free.pop(-2)[: B * L * s * ch].view(B, L * s, ch) if i + 1 < len(self.ups) else out
+            self.stage(i, cur_x, o, B, L, cond=cond if i == 0 else None, bufs=free, pre=pre)
+            L *= s
+            free = [buf for buf in dec if buf.data_ptr() != o.data_ptr()]
+            cur_x = o
 
     def cond_rows(self, g):
         """``g`` [rows, gin(, 1)] -> the conv_pre bias rows [rows, ch] fp32 (dec.cond + both biases), as ``decode``

@@ -208,10 +208,11 @@ class VoiceCloner:
 
     # ---- the chain ---------------------------------------------------------------------------------------------------
     def synthesize_many(self, reqs, noise_w=None, noise_z=None, noise_scale=0.667, noise_scale_w=0.6,
-                        max_sentences_per_launch=DEFAULT_SENTENCES_PER_LAUNCH):
+                        max_sentences_per_launch=DEFAULT_SENTENCES_PER_LAUNCH, generator="fp32"):
         """Steps 1 and 2 for parsed requests: the joined base-speaker waveforms, one 1-D device tensor per request at
-        the TTS model's rate."""
+        the TTS model's rate.  ``generator``: ``"fp32"`` (default) or ``"bf16"``, handed to ``infer_padded``."""
         import torch
+        gen_kw = {} if _lib.check_generator(generator) == "fp32" else {"generator": generator}
         batches = sentence_batches([[s.shape[0] for s in r.ids] for r in reqs], [(r.speed, r.speaker) for r in reqs],
                                    max_sentences_per_launch)
         self.last_batches = batches
@@ -220,7 +221,7 @@ class VoiceCloner:
         for (speed, speaker), items in batches:
             o, frames = self.tts.infer_padded([reqs[r].ids[s] for r, s in items], speaker, speed=speed,
                                               noise_scale=noise_scale, noise_scale_w=noise_scale_w,
-                                              noise_w=pick(noise_w, items), noise_z=pick(noise_z, items))
+                                              noise_w=pick(noise_w, items), noise_z=pick(noise_z, items), **gen_kw)
             outs.append(o)
             counts.append(frames)
         # the one copy to the host: the frame counts size the requests' waveforms
@@ -247,7 +248,8 @@ class VoiceCloner:
     def speak_ids_many(self, requests, tau=0.3, noise_w=None, noise_z=None, noise=None, output_paths=None,
                        message="default", window_frames=longform.DEFAULT_WINDOW_FRAMES,
                        windows_per_launch=longform.DEFAULT_MANY_WINDOWS_PER_LAUNCH,
-                       max_sentences_per_launch=DEFAULT_SENTENCES_PER_LAUNCH, noise_scale=0.667, noise_scale_w=0.6):
+                       max_sentences_per_launch=DEFAULT_SENTENCES_PER_LAUNCH, noise_scale=0.667, noise_scale_w=0.6,
+                       generator="fp32"):
         """Many "say this in that voice" requests in shared launches.  ``requests[i]``: ``(id sequences, speaker, src_se,
         tgt_se[, speed[, out_sr]])`` (or a dict with those keys) -- the sentences as symbol ids (blanks interspersed by
         the caller if the config asks for it), the base speaker's name or id, the two ``[1, 256, 1]`` embeddings, the
@@ -255,19 +257,25 @@ class VoiceCloner:
         reproducible: ``noise_w[i][s]`` ``[2, Tx]`` and ``noise_z[i][s]`` ``[192, >= Ty]`` per sentence, ``noise[i]``
         ``[1, 192, >= T]`` per request for the converter; None: drawn on the device.  Returns one float32 numpy array
         per request (watermark hook applied at the converter's rate), and writes ``output_paths[i]`` when given.  The
-        result equals the chain of the public pieces (module docstring) and depends on the batch composition."""
+        result equals the chain of the public pieces (module docstring) and depends on the batch composition.
+        ``generator``: ``"fp32"`` (default) or ``"bf16"`` -- both halves of the chain run their generator on those
+        kernels (``tts_from_ids(generator=)``, ``convert_many(generator=)``; the contract above holds with the same
+        keyword on the public pieces)."""
         import torch
         from . import audio_io
+        _lib.check_generator(generator)
+        gen_kw = {} if generator == "fp32" else {"generator": generator}
         conv = self.converter
         reqs = self._parse(requests, noise_w, noise_z, noise, output_paths)
         if not reqs:
             return []
         with torch.no_grad():
-            waves = self.synthesize_many(reqs, noise_w, noise_z, noise_scale, noise_scale_w, max_sentences_per_launch)
+            waves = self.synthesize_many(reqs, noise_w, noise_z, noise_scale, noise_scale_w, max_sentences_per_launch,
+                                         **gen_kw)
             msr = int(conv.hps.data.sampling_rate)
             waves = rates.resample_many(waves, [(self.tts_sr, msr)] * len(waves), self.device)
             outs = conv._windowed(window_frames, windows_per_launch).convert_many(
-                waves, [r.src_se for r in reqs], [r.tgt_se for r in reqs], tau=tau, noises=noise)
+                waves, [r.src_se for r in reqs], [r.tgt_se for r in reqs], tau=tau, noises=noise, **gen_kw)
             out_srs = [r.out_sr for r in reqs]
             if conv.watermark_model is None:
                 outs = rates.resample_many(outs, [(msr, r) for r in out_srs], self.device)
@@ -280,17 +288,21 @@ class VoiceCloner:
         return audios
 
     def speak_ids(self, id_sequences, speaker, src_se, tgt_se, speed=1.0, out_sr=None, output_path=None, noise_w=None,
-                  noise_z=None, noise=None, **kwargs):
+                  noise_z=None, noise=None, generator="fp32", **kwargs):
         """``speak_ids_many`` of one request: its audio (and ``output_path`` written when given)."""
+        _lib.check_generator(generator)
         one = lambda x: None if x is None else [x]
         return self.speak_ids_many([(id_sequences, speaker, src_se, tgt_se, speed, out_sr)], noise_w=one(noise_w),
-                                   noise_z=one(noise_z), noise=one(noise), output_paths=one(output_path), **kwargs)[0]
+                                   noise_z=one(noise_z), noise=one(noise), output_paths=one(output_path),
+                                   generator=generator, **kwargs)[0]
 
-    def speak_many(self, texts, speaker, src_se, tgt_se, language="English", speed=1.0, out_sr=None, **kwargs):
+    def speak_many(self, texts, speaker, src_se, tgt_se, language="English", speed=1.0, out_sr=None, generator="fp32",
+                   **kwargs):
         """``speak_ids_many`` of texts, each through ``BaseSpeakerTTS.text_to_ids`` (sentence pieces, language marks,
         ``get_text``: exactly what ``tts`` does; the same RuntimeError when no text front end is registered).
         ``speaker`` / ``src_se`` / ``tgt_se`` / ``language`` / ``speed`` / ``out_sr``: one for all, or a list with one
-        per text."""
+        per text; ``generator``: as for ``speak_ids_many``."""
+        _lib.check_generator(generator)
         texts = list(texts)
         per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * len(texts)
         cols = [per(v) for v in (speaker, src_se, tgt_se, language, speed, out_sr)]
@@ -298,10 +310,12 @@ class VoiceCloner:
             raise ValueError("speak_many: one value, or one per text")
         requests = [(self.tts.text_to_ids(t, lang), spk, s, g, spd, r)
                     for t, spk, s, g, lang, spd, r in zip(texts, *cols)]
-        return self.speak_ids_many(requests, **kwargs)
+        return self.speak_ids_many(requests, generator=generator, **kwargs)
 
     def speak(self, text, speaker, src_se, tgt_se, language="English", speed=1.0, out_sr=None, output_path=None,
-              noise_w=None, noise_z=None, noise=None, **kwargs):
+              noise_w=None, noise_z=None, noise=None, generator="fp32", **kwargs):
         """``speak_many`` of one text."""
+        _lib.check_generator(generator)
         return self.speak_ids(self.tts.text_to_ids(text, language), speaker, src_se, tgt_se, speed=speed, out_sr=out_sr,
-                              output_path=output_path, noise_w=noise_w, noise_z=noise_z, noise=noise, **kwargs)
+                              output_path=output_path, noise_w=noise_w, noise_z=noise_z, noise=noise,
+                              generator=generator, **kwargs)

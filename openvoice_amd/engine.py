@@ -854,7 +854,7 @@ class ConverterEngine:
     @torch.no_grad()
     @on_own_device
     def voice_conversion(self, spec, spec_lengths, sid_src, sid_tgt, tau=1.0, noise=None, skip_padding=False, *,
-                         seed=None):
+                         seed=None, generator=None):
         """Same contract as the reference seam (openvoice/models.py:492-499):
         ``(o_hat [B,1,256T], y_mask [B,1,T], (z, z_p, z_hat) [B,192,T])``.  ``noise`` [B,192,T]
         replaces the reference's ``torch.randn_like`` draw (models.py:220); when omitted it is drawn
@@ -865,7 +865,13 @@ class ConverterEngine:
         the reference, so a padded batch costs as if every utterance had the longest length -- computes only the
         first ``length + limit_margin(B, T)`` frames of each utterance (length-aware work lists,
         ``ov_conv1d_params.col_limit``); every sample of the first ``length`` frames is bit-identical to the full
-        computation, and everything beyond them in ``o_hat`` is zero instead of the reference's bias-driven junk."""
+        computation, and everything beyond them in ``o_hat`` is zero instead of the reference's bias-driven junk.
+        ``generator``: None follows the ``use_bf16_generator`` switch; ``"fp32"`` / ``"bf16"`` choose the generator's
+        kernels for this call, whatever the switch says and without touching it (the bf16 generator is built on first
+        use, as for a bf16 live pool)."""
+        use_bf16 = getattr(self, "_bf16_on", False)
+        if _lib.check_generator(generator, optional=True) is not None:
+            use_bf16 = generator == "bf16"
         dev = self.device
         spec = spec.to(dev, torch.float32)
         B, F, T = spec.shape
@@ -903,11 +909,11 @@ class ConverterEngine:
         self._frames(ws, 0, B, spec, conds, tau)
         z, z_p, z_hat = ws["z"], ws["z_p"], ws["z_hat"]
         # ---- generator (models.py:272-291); z_hat * y_mask is the identity (z_hat already masked) --
-        if getattr(self, "_bf16_on", False):
+        if use_bf16:
             if self.profile is not None:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
-            o_hat = self.generator_bf16.decode(z_hat[:, :, :T], g_d.unsqueeze(-1))
+            o_hat = self._live_generator_bf16().decode(z_hat[:, :, :T], g_d.unsqueeze(-1))
             if self.profile is not None:
                 e1.record()
                 self.profile.append(("gen_bf16", 0.0, e0, e1))

@@ -198,7 +198,8 @@ class WindowedConverter:
                                             graph=self.graph, **noise_mod.kw(seed))[0]
         _lib.call("ov_stitch_window_cores_f32", o_hat, plan_dev, W, Tw, self.spf, out, out.numel(), out_frame0)
 
-    def _launch_multi(self, pool, records_dev, Tw, src_se, tgt_se, tau, nz, out, stitch_dev, n_out, seed=None):
+    def _launch_multi(self, pool, records_dev, Tw, src_se, tgt_se, tau, nz, out, stitch_dev, n_out, seed=None,
+                      generator=None):
         """One launch of W = len(records_dev) windows, each from its own span of ``pool`` (``records_dev`` [W, 3] int64
         (base, n_samples, first_frame)): framing -> spectrogram -> voice_conversion with per-window embedding rows ->
         the cores of the first ``n_out`` windows into the packed ``out`` (``stitch_dev`` [n_out, 3] virtual records,
@@ -207,16 +208,17 @@ class WindowedConverter:
         spec = self._spectrogram().windows_multi(pool, records_dev, Tw)
         lengths = torch.full((W,), Tw, dtype=torch.int64, device=pool.device)
         o_hat = self.model.voice_conversion(spec, lengths, sid_src=src_se, sid_tgt=tgt_se, tau=tau, noise=nz,
-                                            graph=self.graph, **noise_mod.kw(seed))[0]
+                                            graph=self.graph, **noise_mod.kw(seed), **_lib.generator_kw(generator))[0]
         _lib.call("ov_stitch_window_cores_f32", o_hat, stitch_dev, n_out, Tw, self.spf, out, out.numel(), 0)
 
-    def _run_jobs(self, sources, jobs, tau, out, max_windows, ladder=None):
+    def _run_jobs(self, sources, jobs, tau, out, max_windows, ladder=None, generator=None):
         """Windows of many sources in shared launches.  ``sources``: 1-D device waveforms (spans); ``jobs``: window
         jobs ``(source, f0, lo, hi, Tw, noise [1, inter, Tw], src_se [1, gin, 1], tgt_se, dst)`` with frames relative to
         the source span (``noise``: a tensor, or the ``(seed, stream, first frame)`` of a seeded source's window) and
         ``dst`` the packed output frame of the core's first frame.  Jobs of equal ``Tw`` share
         launches of up to ``max_windows`` in the given order; a partial launch is padded up to the next ``ladder`` size
-        (None: launched as it is) with copies of its last window.  Returns the number of launches."""
+        (None: launched as it is) with copies of its last window.  ``generator``: handed to ``voice_conversion`` when
+        not None.  Returns the number of launches."""
         if not jobs:
             return 0
         bases, acc = [], 0
@@ -252,7 +254,7 @@ class WindowedConverter:
                 g_src = torch.cat([j[6].reshape(1, -1, 1) for j in rows])
                 g_tgt = torch.cat([j[7].reshape(1, -1, 1) for j in rows])
                 self._launch_multi(pool, recs_dev[:W], Tw, g_src, g_tgt, tau, nz, out, recs_dev[W:], r,
-                                   **noise_mod.kw(seed))
+                                   **noise_mod.kw(seed), **_lib.generator_kw(generator))
                 launches += 1
         return launches
 
@@ -278,7 +280,7 @@ class WindowedConverter:
         return wave, T, noise
 
     @torch.no_grad()
-    def convert_many(self, waves, src_ses, tgt_ses, tau=0.3, noises=None, *, seeds=None):
+    def convert_many(self, waves, src_ses, tgt_ses, tau=0.3, noises=None, *, seeds=None, generator=None):
         """``convert`` of many recordings with their windows packed across recordings into launches of up to
         ``windows_per_launch`` (``ov_frame_hops_multi_f32``: each window framed from its own recording).  ``src_ses`` /
         ``tgt_ses``: one embedding per recording; ``noises``: None or one ``[1, inter, >= T_i]`` (or None) per
@@ -287,7 +289,11 @@ class WindowedConverter:
         windows of its own
         ``plan_windows``; recordings of ``T <= window_frames`` frames are one ``T``-frame window each and share launches
         with the recordings of equal ``T``.  Returns the converted waveforms (device tensors, views of one packed
-        output), each equal to ``convert`` of that recording with the same noise (bit for bit with direct kernels)."""
+        output), each equal to ``convert`` of that recording with the same noise (bit for bit with direct kernels).
+        ``generator`` (keyword only): None follows the engine's ``use_bf16_generator`` switch, ``"fp32"`` / ``"bf16"``
+        choose the generator's kernels for this call (``ConverterEngine.voice_conversion``); the windows of a launch
+        have one length, so the bf16 generator runs them as the dense batch they are."""
+        _lib.check_generator(generator, optional=True)
         dev = self._device()
         n = len(waves)
         if len(src_ses) != n or len(tgt_ses) != n or (noises is not None and len(noises) != n):
@@ -307,7 +313,7 @@ class WindowedConverter:
         out = torch.empty(acc * self.spf, dtype=torch.float32, device=dev)
         # windows of full length first (one shape), then the short recordings grouped by length
         jobs.sort(key=lambda j: j[4] != self.window_frames)
-        self._run_jobs([w for w, _, _ in items], jobs, tau, out, self.windows_per_launch)
+        self._run_jobs([w for w, _, _ in items], jobs, tau, out, self.windows_per_launch, generator=generator)
         return [out[o * self.spf:(o + T) * self.spf] for o, (_, T, _) in zip(offs, items)]
 
     @torch.no_grad()

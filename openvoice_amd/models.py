@@ -12,6 +12,7 @@ import weakref
 import torch
 from torch import nn
 
+from . import _lib
 from . import noise as noise_mod
 from .engine import ConverterEngine, validate_config
 from .params import converter_param_spec, tts_full_param_spec
@@ -98,7 +99,7 @@ class SynthesizerTrn(nn.Module):
         return self._engine
 
     def voice_conversion(self, y, y_lengths, sid_src, sid_tgt, tau=1.0, noise=None, graph=False, skip_padding=False, *,
-                         seed=None):
+                         seed=None, generator=None):
         """reference: openvoice/models.py:492-499; ``noise`` is the explicit form of the
         reference's ``randn_like`` draw (optional), ``seed`` the counter-based one (``noise.py``: an int ``s`` gives
         row ``b`` the stream ``(s, b)``; or one seed / pair per row).  ``graph=True`` replays the launch sequence of
@@ -106,15 +107,21 @@ class SynthesizerTrn(nn.Module):
         (B, T, tau) shape from a captured HIP graph (``engine.GraphedConversion``); the returned tensors are
         then static buffers, valid until the next graphed call of the same shape.  ``skip_padding=True`` (ragged
         batches): the generator computes only ``length + limit_margin`` (16-20) frames per utterance -- valid samples
-        bit-identical, the padded tail of ``o_hat`` zero (``ConverterEngine.voice_conversion``)."""
+        bit-identical, the padded tail of ``o_hat`` zero (``ConverterEngine.voice_conversion``).  ``generator``: None
+        follows the engine's ``use_bf16_generator`` switch; ``"fp32"`` / ``"bf16"`` choose for this call (eager calls
+        only: a captured graph follows the switch)."""
+        _lib.check_generator(generator, optional=True)
         eng = self.engine()
         if self.n_speakers != 0:
             eng = eng.core      # a TTS checkpoint also carries enc_q / flow / dec
+        if graph and generator is not None:
+            raise _lib.OvError("voice_conversion: generator= chooses per eager call; a captured graph (graph=True) follows "
+                               "use_bf16_generator")
         if graph:
             g = eng.graphed(y.shape[0], y.shape[2], tau, sid_src.shape[0], sid_tgt.shape[0], skip_padding=skip_padding)
             return g(y, y_lengths, sid_src, sid_tgt, noise=noise, **noise_mod.kw(seed))
         return eng.voice_conversion(y, y_lengths, sid_src, sid_tgt, tau=tau, noise=noise, skip_padding=skip_padding,
-                                    **noise_mod.kw(seed))
+                                    **noise_mod.kw(seed), **_lib.generator_kw(generator))
 
     def voice_conversion_windowed(self, y, sid_src, sid_tgt, tau=1.0, noise=None, window_frames=None,
                                   windows_per_launch=None, n_fft=1024, hop_length=256, graph=False, *, seed=None):
@@ -136,13 +143,16 @@ class SynthesizerTrn(nn.Module):
         return conv.convert(y, sid_src, sid_tgt, tau=tau, noise=noise, **noise_mod.kw(seed)).view(1, 1, -1)
 
     def infer(self, x, x_lengths, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1., sdp_ratio=0.2,
-              max_len=None, noise_w=None, noise_z=None, skip_padding=False, *, seed=None):
+              max_len=None, noise_w=None, noise_z=None, skip_padding=False, *, seed=None, generator="fp32"):
         """reference: openvoice/models.py:467-490; ``noise_w`` / ``noise_z`` are the explicit forms of the
         reference's two RNG draws (optional); ``seed`` draws both counter-based (``noise.py``: row ``b`` of an int
         ``s`` is stream ``(s, b)``, ``noise_w`` purpose 1 over the tokens, ``noise_z`` purpose 2 over the frames).
+        ``generator``: ``"fp32"`` (default) or ``"bf16"``, the generator's kernels (``TtsEngine.infer``).
         Returns ``(o, attn, y_mask, (z, z_p, m_p, logs_p))``."""
+        _lib.check_generator(generator)
         if self.n_speakers == 0:
             raise RuntimeError("infer() needs the TTS model (n_speakers > 0); this is the converter variant")
         return self.engine().infer(x, x_lengths, sid, noise_scale=noise_scale, length_scale=length_scale,
                                    noise_scale_w=noise_scale_w, sdp_ratio=sdp_ratio, max_len=max_len,
-                                   noise_w=noise_w, noise_z=noise_z, skip_padding=skip_padding, **noise_mod.kw(seed))
+                                   noise_w=noise_w, noise_z=noise_z, skip_padding=skip_padding, **noise_mod.kw(seed),
+                                   **({} if generator == "fp32" else {"generator": generator}))

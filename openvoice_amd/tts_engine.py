@@ -142,7 +142,8 @@ class TtsEngine:
     @torch.no_grad()
     @on_own_device
     def infer(self, tokens, lengths, sid, noise_scale=1.0, length_scale=1.0, noise_scale_w=1.0, sdp_ratio=0.2,
-              max_len=None, noise_w=None, noise_z=None, return_attn=True, skip_padding=False, *, seed=None):
+              max_len=None, noise_w=None, noise_z=None, return_attn=True, skip_padding=False, *, seed=None,
+              generator="fp32"):
         """Same contract as the reference (models.py:467-490): returns
         ``(o [B,1,256*Ty'], attn [B,1,Ty,Tx], y_mask [B,1,Ty], (z, z_p, m_p, logs_p) [B,192,Ty])``.
         ``noise_w`` [B,2,Tx] / ``noise_z`` [B,192,>=Ty] replace the reference's two RNG draws when given.
@@ -152,7 +153,13 @@ class TtsEngine:
         known -- nobody has to guess a bound for it.
         ``skip_padding``: the generator computes only ``y_length + core.limit_margin(B, Ty)`` frames (16-20) of each
         utterance of a padded batch
-        (valid samples bit-identical, the padded tail of ``o`` zero; ``ConverterEngine.voice_conversion``)."""
+        (valid samples bit-identical, the padded tail of ``o`` zero; ``ConverterEngine.voice_conversion``).
+        ``generator``: ``"fp32"`` (default) or ``"bf16"`` -- the generator alone on the bf16 channels-last kernels
+        (``bf16.GeneratorBf16``, built on first use; ``use_bf16_generator`` is neither read nor set), everything before
+        it unchanged: ``attn``, ``y_mask`` and the four latents are the fp32 call's bits.  With ``skip_padding`` the
+        padded batch then runs as a few dense length groups (``GeneratorBf16.decode_groups``: valid samples the bits of
+        the padded bf16 run, the tail zero), without it as one padded ``GeneratorBf16.decode``."""
+        _lib.check_generator(generator)
         dev = self.device
         noise_mod.exclusive(seed, noise_w=noise_w, noise_z=noise_z)
         check_token_count(tokens.shape[-1])
@@ -227,7 +234,11 @@ class TtsEngine:
         y_len = torch.zeros(B, dtype=torch.int64, device=dev)
         _lib.call("ov_duration_f32", zw, 2 * Lx, self.ea_m, self.ea_logs, dp_out, 32 * Lx, mask, logw, cum, y_len,
                   B, Tx, Lx, float(sdp_ratio), float(length_scale))
-        Ty = int(y_len.max())                                                   # host sync, as in the reference
+        if generator == "bf16":       # the same one sync, carrying every length: decode_groups plans on the host
+            y_host = y_len.cpu().tolist()
+            Ty = max(y_host)
+        else:
+            Ty = int(y_len.max())                                               # host sync, as in the reference
         # ---- expansion + prior sample + flow (reverse) + generator ---------------------------------------
         core = self.core
         ws = core._workspace(B, Ty)
@@ -248,7 +259,14 @@ class TtsEngine:
         core._flow(z_p, z, ws, B, Ty, cond_flow, mask_y, reverse=True)      # z_p -> z, no copy
         cond_d = core._linear(g, core.dec_cond_w, core.dec_cond_b)
         Td = Ty if max_len is None else min(Ty, int(max_len))
-        o = core.decode(z, cond_d, ws, T=Td, limits=core.frame_limits(y_len, Td) if skip_padding else None)
+        if generator == "bf16":
+            gen = core._live_generator_bf16()
+            if skip_padding:
+                o = gen.decode_groups(z, Ly, gen.cond_rows(g), y_host, Td)
+            else:
+                o = gen.decode(z[:, :, :Td], g.unsqueeze(-1))
+        else:
+            o = core.decode(z, cond_d, ws, T=Td, limits=core.frame_limits(y_len, Td) if skip_padding else None)
         outs = tuple(t[:, :, :Ty].contiguous() for t in (z, z_p, m_p, logs_p))
         self.last_logw = logw[:, :Tx]
         return (o, attn.unsqueeze(1) if attn is not None else None, mask_y[:, :Ty].unsqueeze(1).contiguous(), outs)
