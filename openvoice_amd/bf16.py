@@ -6,6 +6,9 @@ import torch
 
 from . import _lib
 from ._lib import ConvBf16Params
+from .generator import (FINAL_LRELU_SLOPE, GENERATOR_MARGIN, LRELU_SLOPE, conv_transpose_as_conv, generator_margin_frames,
+                        generator_stages, resblock_convs, samples_per_frame, scratch_per_frame)
+from .params import effective_weight
 
 
 class PackedConvBf16:
@@ -138,13 +141,12 @@ def generator_alg_bytes(cfg, B, T, esize=2, z_channels=192, fused=True):
     """Algorithmic HBM bytes of one generator pass: every tensor pass of the launch sequence (conv_pre; per stage
     the ups read + write and the MRF -- per ResBlock pair 2 passes when it is one fused launch (read x, write out),
     5 as two launches (conv1 r + w, conv2 r + res + w) -- plus the 2 running-sum reads; conv_post)."""
-    ch, L = cfg["upsample_initial_channel"], T
-    total = B * T * (z_channels + ch) * esize
+    stages = generator_stages(cfg)
+    total = B * T * (z_channels + stages[0].cin) * esize
     kernels, dils = cfg["resblock_kernel_sizes"], cfg["resblock_dilation_sizes"]
-    for u in cfg["upsample_rates"]:
-        total += B * L * ch * esize
-        ch //= 2
-        L *= u
+    for _, cin, ch, _, rate_in, rate_out, _ in stages:
+        total += B * T * rate_in * cin * esize
+        L = T * rate_out
         tensor = B * L * ch * esize
         passes = 1                                                  # the ups write
         for j, (k, rd) in enumerate(zip(kernels, dils)):
@@ -267,8 +269,6 @@ class GeneratorBf16:
     running sum are added on the matrix pipe (identity rounds, csrc/conv1d_bf16.hip)."""
 
     def __init__(self, state_dict, model_cfg, device):
-        from .engine import conv_transpose_as_conv
-        from .params import effective_weight
         sd = {k: v.detach().float().cpu() for k, v in state_dict.items()}
         cfg = dict(model_cfg.items()) if hasattr(model_cfg, "items") else dict(model_cfg)
         self.cfg, self.device = cfg, torch.device(device)
@@ -276,23 +276,19 @@ class GeneratorBf16:
         self.conv_pre = PackedConvBf16(sd["dec.conv_pre.weight"], sd["dec.conv_pre.bias"], dev)
         self.cond_w = sd["dec.cond.weight"][:, :, 0].contiguous().to(dev)
         self.cond_b = (sd["dec.cond.bias"] + sd["dec.conv_pre.bias"]).contiguous().to(dev)   # conv_pre bias folded in
-        self.ups, self.resblocks = [], []
-        ch = cfg["upsample_initial_channel"]
-        for i, (u, k) in enumerate(zip(cfg["upsample_rates"], cfg["upsample_kernel_sizes"])):
+        self.stages = generator_stages(cfg)
+        self.ups = []
+        for i, cin, co, u, *_ in self.stages:
             wc = conv_transpose_as_conv(effective_weight(sd, f"dec.ups.{i}"), u)      # rows co*u + ph
-            co = ch // 2
-            wc = wc.reshape(co, u, ch, 3).transpose(0, 1).reshape(u * co, ch, 3)       # rows ph*co + c
+            wc = wc.reshape(co, u, cin, 3).transpose(0, 1).reshape(u * co, cin, 3)     # rows ph*co + c
             bias = sd[f"dec.ups.{i}.bias"].repeat(u)
             self.ups.append(dict(conv=PackedConvBf16(wc, bias, dev), stride=u))
-            ch = co
-            stage = []
-            for j, (rk, rd) in enumerate(zip(cfg["resblock_kernel_sizes"], cfg["resblock_dilation_sizes"])):
-                rb = f"dec.resblocks.{i * len(cfg['resblock_kernel_sizes']) + j}"
-                stage.append([(PackedConvBf16(effective_weight(sd, f"{rb}.convs1.{n}"), sd[f"{rb}.convs1.{n}.bias"], dev, dil=d),
-                               PackedConvBf16(effective_weight(sd, f"{rb}.convs2.{n}"), sd[f"{rb}.convs2.{n}.bias"], dev, dil=1))
-                              for n, d in enumerate(rd)])
-            self.resblocks.append(stage)
-        self.final_channels = ch
+        layer = lambda name, d: PackedConvBf16(effective_weight(sd, name), sd[name + ".bias"], dev, dil=d)
+        convs = list(resblock_convs(cfg))
+        self.resblocks = [[[(layer(f"{c.prefix}.convs1.{c.n}", c.dil), layer(f"{c.prefix}.convs2.{c.n}", 1))
+                            for c in convs if (c.stage, c.j) == (st.index, j)]
+                           for j in range(len(cfg["resblock_kernel_sizes"]))] for st in self.stages]
+        self.final_channels = self.stages[-1].ch
         self.post_w = sd["dec.conv_post.weight"][0].contiguous().to(dev)              # [C, 7] fp32
         self._ws = {}
         # ResBlock pairs of the HBM-bound stages as ONE launch each (csrc/conv1d_bf16_pair.hip): C = 32 every kernel
@@ -314,11 +310,8 @@ class GeneratorBf16:
         self._streams = []
         # decode_groups: the frames an item is computed beyond its own length.  The bf16 kernels read exactly their taps
         # (no Winograd tiles, no work lists), so this is the direct kernels' margin, not limit_margin_frames
-        from .engine import GENERATOR_MARGIN, generator_margin_frames
         self.margin = max(GENERATOR_MARGIN, generator_margin_frames(cfg))
-        self.samples_per_frame = 1
-        for u in cfg["upsample_rates"]:
-            self.samples_per_frame *= u
+        self.samples_per_frame = samples_per_frame(cfg)
         self.max_groups, self.group_cost = DEFAULT_MAX_GROUPS, DEFAULT_GROUP_COST
         self._arena = None
         self.last_plan = None               # plan_groups of the last decode_groups call, for tests / logs
@@ -332,23 +325,19 @@ class GeneratorBf16:
         key = (B, T, self.chain_streams > 1)
         if key not in self._ws:
             self._ws.clear()
-            ch, L, biggest = self.cfg["upsample_initial_channel"], T, 0
-            for u in self.cfg["upsample_rates"]:
-                ch //= 2
-                L *= u
-                biggest = max(biggest, ch * L)
             f = lambda n: torch.empty(n, dtype=torch.bfloat16, device=self.device)
             # stage input, ups output, running sum + (t1, ra) per concurrent chain: ONE pair for the default serial order
             # (chain_streams == 1: 5 buffers, 4.5 GB at batch 64), one per chain only when concurrency is on (9, 8.1 GB)
             nbuf = 3 + 2 * (max(1, len(self.cfg["resblock_kernel_sizes"])) if self.chain_streams > 1 else 1)
-            self._ws[key] = dict(pre=f(B * T * self.cfg["upsample_initial_channel"]), dec=[f(B * biggest) for _ in range(nbuf)])
+            self._ws[key] = dict(pre=f(B * T * self.stages[0].cin),
+                                 dec=[f(B * T * scratch_per_frame(self.cfg)) for _ in range(nbuf)])
         return self._ws[key]
 
     def _stage_flags(self, i):
         """``(act, fused, mean_act)`` of stage i, a function of the configuration and of ``fuse_pairs`` / ``act_hbm``:
         ``act`` -- the stage keeps its tensors activated in HBM (second-generation pairs); ``fused[j]`` -- ResBlock j
         runs first-generation fused pairs; ``mean_act`` -- the stage stores its output, the MRF mean, activated."""
-        ch = self.cfg["upsample_initial_channel"] >> (i + 1)
+        ch = self.stages[i].ch
         nk = len(self.cfg["resblock_kernel_sizes"])
         act = (self.act_hbm and self.fuse_pairs and
                all(pair2_bf16_supported(ch, c1.K, c1.dil) for pairs in self.resblocks[i] for c1, _ in pairs))
@@ -360,7 +349,7 @@ class GeneratorBf16:
 
     def stage_scratch_elems(self, i, B, L):
         """Elements of each of the scratch buffers ``stage(i, ...)`` takes for ``B`` rows of ``L`` input columns."""
-        return B * L * self.ups[i]["stride"] * (self.cfg["upsample_initial_channel"] >> (i + 1))
+        return B * L * self.stages[i].stride * self.stages[i].ch
 
     @torch.no_grad()
     def stage(self, i, x, out, B, L, cond=None, bufs=None, pre=None, side=None):
@@ -375,13 +364,8 @@ class GeneratorBf16:
         the last stage; 2 more per further chain with ``side``); ``pre`` (stage 0): flat bf16 of B * L * ch elements.
         ``side``: the HIP streams of ``chain_streams > 1`` (``decode`` passes them); a live unit leaves it None and its
         launches go to the current stream in the serial order, whatever ``chain_streams`` says."""
-        from .engine import FINAL_LRELU_SLOPE, LRELU_SLOPE
-        nstage = len(self.ups)
-        s = self.ups[i]["stride"]
-        cin = self.cfg["upsample_initial_channel"] >> i
-        ch = cin // 2
+        _, cin, ch, s, _, _, last_stage = self.stages[i]
         nk = len(self.cfg["resblock_kernel_sizes"])
-        last_stage = i == nstage - 1
         if i == 0:
             p = pre[: B * L * cin].view(B, L, cin)
             # every tensor a ConvTranspose reads is stored ACTIVATED by its producer (conv_pre here, the MRF mean below):
@@ -467,32 +451,16 @@ class GeneratorBf16:
         # the serial order.  Not under graph capture (the engine captures on one stream).
         concurrent = self.chain_streams > 1 and nk > 1 and not torch.cuda.is_current_stream_capturing()
         side = self._side_streams(nk) if concurrent else None
-        ch, L = self.cfg["upsample_initial_channel"], T
-        cur_x, free = x, list(ws["dec"])
-        for i, up in enumerate(self.ups):
-            s = up["stride"]
-            ch //= 2
-            if i + 1 < len(self.ups):
-                out = free.pop(-2)[: B * L * s * ch].view(B, L * s, ch)     # the ups output takes the last one
-            else:
-                out = torch.empty(B, 1, L * s, dtype=torch.float32, device=dev)
-            self.stage(i, cur_x, out, B, L, cond=cond if i == 0 else None, bufs=free, pre=ws["pre"], side=side)
-            L *= s
-            # every scratch buffer except the one holding this stage's output is free again
-            free = [buf for buf in ws["dec"] if buf.data_ptr() != out.data_ptr()]
-            cur_x = out
-        return cur_x
+        out = torch.empty(B, 1, T * self.samples_per_frame, dtype=torch.float32, device=dev)
+        self._decode_dense(x, cond, out, B, T, ws["dec"], ws["pre"], side)
+        return out
 
     def _group_arena(self, x_elems, o_elems, rows_frames):
         """The buffers of ``decode_groups``, kept across calls and only ever grown (``_workspace`` would drop its cache at
         every new (B, T)): the groups' packed bf16 inputs and fp32 outputs, and ONE set of stage scratch sized for the
         plan's largest group (``rows_frames`` = its B_g * L_g)."""
-        ch, L, biggest = self.cfg["upsample_initial_channel"], 1, 0
-        for u in self.cfg["upsample_rates"]:
-            ch //= 2
-            L *= u
-            biggest = max(biggest, ch * L)
-        want = dict(x=x_elems, o=o_elems, pre=rows_frames * self.cfg["upsample_initial_channel"], dec=rows_frames * biggest)
+        want = dict(x=x_elems, o=o_elems, pre=rows_frames * self.stages[0].cin,
+                    dec=rows_frames * scratch_per_frame(self.cfg))
         a = self._arena
         if a is None or any(a["size"][k] < n for k, n in want.items()):
             size = want if a is None else {k: max(n, a["size"][k]) for k, n in want.items()}
@@ -556,17 +524,16 @@ class GeneratorBf16:
         _lib.call("ov_unpack_groups_f32", arena["o"], arena["o"].numel(), table[n_pack:n_pack + n_unpack], B, o, o.numel())
         return o
 
-    def _decode_dense(self, x, cond, out, B, L, dec, pre):
-        """The stage loop of ``decode`` on caller-given buffers: ``x`` bf16 [B, L, inter], ``cond`` [B, ch] (contiguous
-        rows), ``out`` fp32 [B, 1, L * spf], ``dec`` five flat bf16 scratch buffers, ``pre`` the conv_pre output."""
-        ch = self.cfg["upsample_initial_channel"]
+    def _decode_dense(self, x, cond, out, B, T, dec, pre, side=None):
+        """The stage loop on caller-given buffers: ``x`` bf16 [B, T, inter], ``cond`` [B, ch] (contiguous rows), ``out``
+        fp32 [B, 1, T * spf], ``dec`` the flat bf16 scratch buffers (five; two more per further chain with ``side``, the
+        HIP streams of ``chain_streams > 1``), ``pre`` the conv_pre output."""
         cur_x, free = x, list(dec)
-        for i, up in enumerate(self.ups):
-            s = up["stride"]
-            ch //= 2
-            o = free.pop(-2)[: B * L * s * ch].view(B, L * s, ch) if i + 1 < len(self.ups) else out
-            self.stage(i, cur_x, o, B, L, cond=cond if i == 0 else None, bufs=free, pre=pre)
-            L *= s
+        for i, _, ch, _, rate_in, rate_out, last in self.stages:
+            # the ups output takes the last free buffer, the stage's output the one before it
+            o = out if last else free.pop(-2)[: B * T * rate_out * ch].view(B, T * rate_out, ch)
+            self.stage(i, cur_x, o, B, T * rate_in, cond=cond if i == 0 else None, bufs=free, pre=pre, side=side)
+            # every scratch buffer except the one holding this stage's output is free again
             free = [buf for buf in dec if buf.data_ptr() != o.data_ptr()]
             cur_x = o
 

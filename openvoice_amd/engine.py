@@ -19,17 +19,11 @@ from . import _lib
 from . import noise as noise_mod
 from ._lib import (ConvParams, EPI_CONVT, EPI_COUPLE, EPI_GATE, EPI_LINEAR, EPI_POSTERIOR, EPI_RESSKIP,
                    F_CONVT_GROUPED, F_MASK_V, F_OUT2_INIT)
+from .generator import (FINAL_LRELU_SLOPE, GENERATOR_MARGIN, LRELU_SLOPE, conv_transpose_as_conv,  # noqa: F401
+                        generator_margin_frames, generator_stages, resblock_convs, samples_per_frame, scratch_per_frame)
 from .params import ENC_Q_LAYERS, FLOW_LAYERS, N_FLOWS, REF_ENC_FILTERS, REF_ENC_GRU, effective_weight
 
-# Length-aware work lists (``skip_padding``): the generator's one-sided receptive field is 13.3 frames -- conv_pre 3,
-# the four transposed convs 1 + 1/8 + 1/64 + 1/128, the MRF 60 samples per stage (k = 11: dilations 1, 3, 5 + three
-# dilation-1 convs = 5 * (1 + 3 + 5 + 3)) at 8 / 64 / 128 / 256 samples per frame, conv_post 3 samples (reference:
-# openvoice/models.py:225-291, modules.py:221-309) -- so computing length + 16 frames leaves the first ``length``
-# frames bit-identical to the full computation.
-GENERATOR_MARGIN = 16   # the released configuration's; every engine computes its own (generator_margin_frames)
 LIMIT_MAX_BATCH = 256   # ovk::LIMIT_MAX_BATCH: utterances per launch the kernels' prefix table holds
-LRELU_SLOPE = 0.1       # reference: openvoice/modules.py:14
-FINAL_LRELU_SLOPE = 0.01  # F.leaky_relu default at openvoice/models.py:287
 
 
 # What the kernel library has instances for (csrc/conv1d_inst_*.hip; everything else returns OV_E_UNSUPPORTED at the
@@ -67,50 +61,22 @@ def validate_config(cfg):
     rates, uk = list(cfg["upsample_rates"]), list(cfg["upsample_kernel_sizes"])
     if len(rates) != len(uk) or not rates:
         bad("upsample_kernel_sizes", uk, f"one kernel size per entry of upsample_rates ({len(rates)}) is required")
-    ch = cfg["upsample_initial_channel"]
-    for i, (u, k) in enumerate(zip(rates, uk)):
+    for (i, cin, ch, u, *_), k in zip(generator_stages(cfg), uk):
         if k != 2 * u:
             bad("upsample_kernel_sizes", uk, f"stage {i}: the transposed conv is built as a 3-tap phase conv, which needs "
                 f"kernel == 2 * stride (got kernel {k}, stride {u})")
         if u <= 0 or 32 % u != 0:
             bad("upsample_rates", rates, f"stage {i}: stride {u} must divide 32 (phases are interleaved inside one "
                 f"32-row fragment)")
-        if ch % 2 != 0 or (ch // 2) % 32 != 0:
-            bad("upsample_initial_channel", cfg["upsample_initial_channel"], f"stage {i} would have {ch // 2} channels; "
+        if cin % 2 != 0 or ch % 32 != 0:
+            bad("upsample_initial_channel", cfg["upsample_initial_channel"], f"stage {i} would have {ch} channels; "
                 f"every stage needs a multiple of 32 (whole MFMA fragments)")
-        ch //= 2
     if cfg["hidden_channels"] % 32 != 0:
         bad("hidden_channels", cfg["hidden_channels"], "must be a multiple of 32 (the WaveNet gate rows are paired in "
             "32-row MFMA fragments)")
     if cfg["inter_channels"] % 64 != 0:
         bad("inter_channels", cfg["inter_channels"], "must be a multiple of 64 (the couplings split the channels in halves "
             "of whole 32-row fragments)")
-
-
-def generator_margin_frames(cfg, conv_pre_kernel=7, conv_post_kernel=7, chain_reach=None):
-    """Frames beyond an utterance's end that can still influence its last sample: an UPPER BOUND of the generator's
-    one-sided receptive field from the configuration (reference: openvoice/models.py:225-291 -- conv_pre, per stage a
-    ConvTranspose1d of kernel k_u and stride u followed by the MRF whose widest ResBlock1 reaches
-    (k - 1) / 2 * (sum(dilations) + len(dilations)) samples (modules.py:221-309: one dilated and one plain conv per
-    dilation), conv_post), rounded up plus one frame of slack.  The transposed-conv term charges (k_u - u + 1) / spf
-    frames per stage, more than the ceil((k_u - u) / 2 / u) + 1 inputs a stage really reaches back: the bound is loose
-    by design.  15 for the released V1 / V2 configurations (``ConverterEngine`` uses max(GENERATOR_MARGIN = 16, this):
-    tests/test_host_algebra_cpu.py::test_generator_margin_released_configs).  ``chain_reach(i, k, dilations)``, when
-    given, replaces the ResBlock term by the samples one chain of stage ``i`` really reaches forward with the kernels that
-    run it (``limit_margin_frames``)."""
-    import math
-    reach = (conv_pre_kernel - 1) / 2.0                      # frames
-    spf = 1                                                  # samples per frame after the stage
-    if chain_reach is None:
-        chain_reach = lambda i, k, d: (k - 1) // 2 * (sum(d) + len(d))
-    for i, (u, ku) in enumerate(zip(cfg["upsample_rates"], cfg["upsample_kernel_sizes"])):
-        spf *= u
-        reach += (ku - u + 1) / 2.0 / spf * 2                # a transposed conv reaches ceil((k_u - u) / 2) + 1 inputs back
-        widest = max(chain_reach(i, k, list(d)) for k, d in
-                     zip(cfg["resblock_kernel_sizes"], cfg["resblock_dilation_sizes"]))
-        reach += widest / spf
-    reach += (conv_post_kernel - 1) / 2.0 / spf
-    return int(math.ceil(reach)) + 1
 
 
 def on_own_device(method):
@@ -183,26 +149,6 @@ def gate_row_order(hidden):
     for q in range(hidden // 32):
         idx += list(range(32 * q, 32 * q + 32)) + list(range(hidden + 32 * q, hidden + 32 * q + 32))
     return torch.tensor(idx, dtype=torch.long)
-
-
-def conv_transpose_as_conv(w, stride):
-    """ConvTranspose1d(k = 2*stride, padding = stride/2) as a 3-tap stride-1 conv producing
-    ``stride`` output phases per input frame.  y[s*q + p] = sum_i x[i] * w[:, :, s*q + p + pad - s*i]
-    has exactly two non-zero taps per phase (i = q and i = q-1 or q+1); row = cout*stride + phase.
-    ``w`` is [Cin, Cout, k] (torch ConvTranspose1d layout, reference: openvoice/models.py:244-256)."""
-    cin, cout, k = w.shape
-    s = stride
-    pad = (k - s) // 2
-    assert k == 2 * s and (k - s) % 2 == 0
-    wc = torch.zeros(cout * s, cin, 3, dtype=w.dtype)
-    for p in range(s):
-        rows = torch.arange(cout) * s + p
-        wc[rows, :, 1] = w[:, :, p + pad].t()                 # x[q]
-        if p + pad < s:
-            wc[rows, :, 0] = w[:, :, p + pad + s].t()         # x[q-1]
-        else:
-            wc[rows, :, 2] = w[:, :, p + pad - s].t()         # x[q+1]
-    return wc
 
 
 def convt_row_order(cout, stride):
@@ -396,12 +342,10 @@ def limit_margin_frames(cfg, B, T, use_winograd=True, fuse_pairs=True):
     it (conv_reach of resblock_families), at least GENERATOR_MARGIN.  The columns beyond the computed ones hold stale
     scratch; a Winograd conv reads 2-3 dil columns further than its taps, so a direct-only launch keeps 16 while one with
     Winograd stages needs more (tests/test_host_algebra_cpu.py simulates every launch of decode() column by column)."""
-    ch0, rates = cfg["upsample_initial_channel"], cfg["upsample_rates"]
+    stages = generator_stages(cfg)
 
     def chain_reach(i, k, dils):
-        C, L = ch0 >> (i + 1), T
-        for u in rates[:i + 1]:
-            L *= u
+        C, L = stages[i].ch, T * stages[i].rate_out
         fams = resblock_families(C, k, dils, B, L, use_winograd, fuse_pairs)
         return sum(conv_reach(f1, k, d)[1] + conv_reach(f2, k, 1)[1] for (f1, f2), d in zip(fams, dils))
 
@@ -535,6 +479,29 @@ class _WaveNet:
             self.cond_b_fused = bc[full].contiguous().to(device)
 
 
+_DEC_BUFFERS = 5         # decoder scratch buffers of a workspace: the stage input, the ConvTranspose output, t1 / ra, the MRF sum
+
+
+def _workspace_elems(cfg, B, T):
+    """Float32 elements of a ``ConverterEngine._workspace(B, T)``: ``(frame-rate tensors together, each of the _DEC_BUFFERS
+    decoder scratch buffers)`` -- the one size computation behind ``_workspace`` and ``workspace_bytes``."""
+    H, C, Tp = cfg["hidden_channels"], cfg["inter_channels"], padded_frames(T)
+    # mask, h / h2 / acts / skip, noise, the three latents, the conv_pre output
+    frame_rate = Tp + 4 * H * Tp + C * Tp + 3 * C * Tp + generator_stages(cfg)[0].cin * Tp
+    return B * frame_rate, B * T * scratch_per_frame(cfg)
+
+
+def _resblock_tree(sd, cfg, make, keep=lambda stage: True):
+    """``[stage][ResBlock][(conv 1, conv 2) per dilation]`` of ``make(c, weight, bias, dilation)`` over
+    ``resblock_convs(cfg)`` (``c``: the pair's record); None in place of a stage that ``keep(stage index)`` refuses."""
+    convs = list(resblock_convs(cfg))
+    layer = lambda c, name, d: make(c, effective_weight(sd, name), sd[name + ".bias"], d)
+    return [[[(layer(c, f"{c.prefix}.convs1.{c.n}", c.dil), layer(c, f"{c.prefix}.convs2.{c.n}", 1))
+              for c in convs if (c.stage, c.j) == (i, j)]
+             for j in range(len(cfg["resblock_kernel_sizes"]))] if keep(i) else None
+            for i in range(len(cfg["upsample_rates"]))]
+
+
 class ConverterEngine:
     """Kernel-level implementation of the converter model for one device."""
 
@@ -578,54 +545,25 @@ class ConverterEngine:
         self.conv_pre = PackedConv(sd["dec.conv_pre.weight"], sd["dec.conv_pre.bias"], dev, K=7)
         self.dec_cond_w = sd["dec.cond.weight"][:, :, 0].contiguous().to(dev)
         self.dec_cond_b = sd["dec.cond.bias"].contiguous().to(dev)
-        self.ups, self.resblocks = [], []
-        ch = cfg["upsample_initial_channel"]
-        kernels, dils = cfg["resblock_kernel_sizes"], cfg["resblock_dilation_sizes"]
-        for i, (u, k) in enumerate(zip(cfg["upsample_rates"], cfg["upsample_kernel_sizes"])):
-            w = effective_weight(sd, f"dec.ups.{i}")
-            wc = conv_transpose_as_conv(w, u)
+        self.stages = generator_stages(cfg)
+        self.ups = []
+        for i, _, ch, u, *_ in self.stages:
+            wc = conv_transpose_as_conv(effective_weight(sd, f"dec.ups.{i}"), u)
             bias = sd[f"dec.ups.{i}.bias"].repeat_interleave(u)
-            order = convt_row_order(ch // 2, u)
+            order = convt_row_order(ch, u)
             if order is not None:
                 wc, bias = wc[order], bias[order]
-            self.ups.append(dict(conv=PackedConv(wc, bias, dev, K=3, cout=ch // 2), stride=u,
+            self.ups.append(dict(conv=PackedConv(wc, bias, dev, K=3, cout=ch), stride=u,
                                  flags=F_CONVT_GROUPED if order is not None else 0))
-            ch //= 2
-            stage = []
-            for j, (rk, rd) in enumerate(zip(kernels, dils)):
-                rb = f"dec.resblocks.{i * len(kernels) + j}"
-                pairs = []
-                for n, d in enumerate(rd):
-                    c1 = PackedConv(effective_weight(sd, f"{rb}.convs1.{n}"), sd[f"{rb}.convs1.{n}.bias"], dev, K=rk, dil=d)
-                    c2 = PackedConv(effective_weight(sd, f"{rb}.convs2.{n}"), sd[f"{rb}.convs2.{n}.bias"], dev, K=rk, dil=1)
-                    pairs.append((c1, c2))
-                stage.append(pairs)
-            self.resblocks.append(stage)
+        self.resblocks = _resblock_tree(sd, cfg, lambda c, w, b, d: PackedConv(w, b, dev, K=c.K, dil=d))
         # Winograd-domain twins (csrc/conv1d_wino.h) of the ResBlock convs of the MFMA-bound stages: the same fp32 conv
         # with 1.6-2x fewer executed multiplies; per stage / ResBlock / pair (w1 | None, w2 | None)
-        self.wino_resblocks = []
         from . import wino as _wino
-        ch = cfg["upsample_initial_channel"]
-        for i in range(len(cfg["upsample_rates"])):
-            ch //= 2
-            stage = []
-            for j, (rk, rd) in enumerate(zip(kernels, dils)):
-                rb = f"dec.resblocks.{i * len(kernels) + j}"
-                pairs = []
-                for n, d in enumerate(rd):
-                    w1 = w2 = None
-                    if _wino.supported(ch, ch, rk, d) and wino_policy(ch, rk, d):
-                        w1 = _wino.PackedConvWino(effective_weight(sd, f"{rb}.convs1.{n}"), sd[f"{rb}.convs1.{n}.bias"], dev, dil=d)
-                    if _wino.supported(ch, ch, rk, 1) and wino_policy(ch, rk, 1):
-                        w2 = _wino.PackedConvWino(effective_weight(sd, f"{rb}.convs2.{n}"), sd[f"{rb}.convs2.{n}.bias"], dev, dil=1)
-                    pairs.append((w1, w2))
-                stage.append(pairs)
-            self.wino_resblocks.append(stage)
-        self.final_channels = ch
+        self.wino_resblocks = _resblock_tree(sd, cfg, lambda c, w, b, d: _wino.PackedConvWino(w, b, dev, dil=d)
+                                             if _wino.supported(c.ch, c.ch, c.K, d) and wino_policy(c.ch, c.K, d) else None)
+        self.final_channels = self.stages[-1].ch
         self.post_w = sd["dec.conv_post.weight"][0].contiguous().to(dev)   # [C, 7]
-        self.total_upsample = 1
-        for u in cfg["upsample_rates"]:
-            self.total_upsample *= u
+        self.total_upsample = samples_per_frame(cfg)
         # ---- reference encoder (extract_se): present in converter checkpoints only -------------------
         self.ref_enc = None
         if "ref_enc.gru.weight_ih_l0" in sd:
@@ -641,7 +579,8 @@ class ConverterEngine:
                 bhh=sd["ref_enc.gru.bias_hh_l0"].contiguous().to(dev),
                 proj_w=sd["ref_enc.proj.weight"].contiguous().to(dev),
                 proj_b=sd["ref_enc.proj.bias"].contiguous().to(dev))
-        self._ws = {}
+        self._ws, self._graphs, self._limit_margins = {}, {}, {}
+        self._live_ws, self._live_ws_bf16, self.live_ws_builds = {}, {}, 0    # live unit scratch, per (unit, rows)
         # (B, T) workspaces kept resident at once, least recently used evicted first.  1 (the default): a new shape
         # frees the previous one.  StreamPool raises it to its ladder of launch sizes so that a varying ready count
         # does not rebuild gigabytes of decoder scratch per step (workspace_bytes() prices a shape).
@@ -667,9 +606,10 @@ class ConverterEngine:
         # fp32 arithmetic, 6 G / (4 K) of the direct form's multiplies, ~4x its rounding error
         self.use_winograd = True
         # opt-in fast generator: bf16 activations, fp32 accumulation (waveform within
-        # ~1e-2 of the fp32 path instead of ~1e-5).  Built lazily by use_bf16_generator().
+        # ~1e-2 of the fp32 path instead of ~1e-5).  Built on first use by bf16_generator().
         self._state_dict_for_bf16 = sd
         self.generator_bf16 = None
+        self._bf16_on = False
         # opt-in split-precision MRF stages: fp32-level products on the bf16 matrix pipe
         self._split3_on = False
         self.split3_products = 6
@@ -679,19 +619,23 @@ class ConverterEngine:
     def _stream(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
-    def _conv(self, layer, x, x_off, x_bs, out, out_off, out_bs, B, L, tag="conv", alg_flops=None, **kwargs):
-        """Launch one conv; when ``self.profile`` is a list, bracket the launch with HIP events on
-        the launch stream and record (tag, algorithmic FLOPs, start, end) for bench.py's roofline."""
+    def _timed(self, tag, flops, fn, *extra):
+        """Run ``fn()``; when ``self.profile`` is a list, bracket it with HIP events on the launch stream and record
+        ``(tag, algorithmic FLOPs, start, end, *extra)`` for bench.py's roofline."""
         if self.profile is None:
-            launch_conv(layer, x, x_off, x_bs, out, out_off, out_bs, B, L, **kwargs)
-            return
+            return fn()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        launch_conv(layer, x, x_off, x_bs, out, out_off, out_bs, B, L, **kwargs)
+        out = fn()
         e1.record()
+        self.profile.append((tag, flops, e0, e1) + extra)
+        return out
+
+    def _conv(self, layer, x, x_off, x_bs, out, out_off, out_bs, B, L, tag="conv", alg_flops=None, **kwargs):
+        """Launch one conv, profiled under ``tag`` with its algorithmic FLOPs."""
         if alg_flops is None:
             alg_flops = 2.0 * layer.rows * (kwargs.get("cin") or layer.cin) * layer.K * L * B
-        self.profile.append((tag, alg_flops, e0, e1))
+        self._timed(tag, alg_flops, lambda: launch_conv(layer, x, x_off, x_bs, out, out_off, out_bs, B, L, **kwargs))
 
     def _wino(self, layer, x, out, bs, B, L, res=None, add=None, scale=1.0, in_slope=LRELU_SLOPE, out_slope=1.0, **lim):
         """One Winograd-domain ResBlock conv (leaky ReLU on the input, LINEAR epilogue); profiled under the MRF tag with its
@@ -699,27 +643,15 @@ class ConverterEngine:
         from . import wino
         kw = dict(in_slope=in_slope, out_slope=out_slope, scale=scale, res=res, res_bs=bs if res is not None else 0, add=add,
                   add_bs=bs if add is not None else 0, **lim)
-        if self.profile is None:
-            wino.launch_conv_wino(layer, x, bs, out, bs, B, L, **kw)
-            return
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        wino.launch_conv_wino(layer, x, bs, out, bs, B, L, **kw)
-        e1.record()
         alg = 2.0 * layer.cout * layer.cin * layer.K * L * B
-        self.profile.append(("mrf", alg, e0, e1, alg * wino.PRODUCTS_PER_TILE[layer.K] / (4.0 * layer.K)))
+        self._timed("mrf", alg, lambda: wino.launch_conv_wino(layer, x, bs, out, bs, B, L, **kw),
+                    alg * wino.PRODUCTS_PER_TILE[layer.K] / (4.0 * layer.K))
 
     def _pair(self, c1, c2, x, out, bs, B, L, add, scale, **lim):
         """One fused ResBlock1 iteration; profiled under the same tag as the two launches it replaces, with their
         algorithmic FLOPs (both convs)."""
-        if self.profile is None:
-            launch_pair(c1, c2, x, bs, out, bs, B, L, add=add, add_bs=bs, scale=scale, **lim)
-            return
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        launch_pair(c1, c2, x, bs, out, bs, B, L, add=add, add_bs=bs, scale=scale, **lim)
-        e1.record()
-        self.profile.append(("mrf", 2 * 2.0 * c1.rows * c1.cin * c1.K * L * B, e0, e1))
+        self._timed("mrf", 2 * 2.0 * c1.rows * c1.cin * c1.K * L * B,
+                    lambda: launch_pair(c1, c2, x, bs, out, bs, B, L, add=add, add_bs=bs, scale=scale, **lim))
 
     def _linear(self, x2d, w, b):
         Bg, Kd = x2d.shape
@@ -752,30 +684,17 @@ class ConverterEngine:
             lat = f(3, B, C, Tp)         # the three latents in ONE allocation: one ov_unpad_rows_f32 returns them dense
             ws = dict(Tp=Tp, mask=f(B, Tp), h=f(B, H, Tp), h2=f(B, H, Tp), acts=f(B, H, Tp), skip=f(B, H, Tp), noise=f(B, C, Tp),
                       lat=lat, z=lat[0], z_p=lat[1], z_hat=lat[2])
-            ch = self.cfg["upsample_initial_channel"]
-            ws["pre"] = f(B, ch, Tp)
-            f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
-            L, biggest = T, 0
-            for u in self.cfg["upsample_rates"]:
-                ch //= 2
-                L *= u
-                biggest = max(biggest, ch * L)
-            ws["dec"] = [f(B * biggest) for _ in range(5)]
+            ws["pre"] = f(B, self.stages[0].cin, Tp)
+            dec = _workspace_elems(self.cfg, B, T)[1]
+            ws["dec"] = [torch.empty(dec, dtype=torch.float32, device=dev) for _ in range(_DEC_BUFFERS)]
             self._ws[key] = ws
         return ws
 
     def workspace_bytes(self, B, T):
         """Device bytes of the ``_workspace(B, T)`` allocation (the frame-rate tensors and the decoder scratch; the
         opt-in paths' lazily added buffers not included)."""
-        H, C, Tp = self.hidden, self.inter, padded_frames(T)
-        ch = self.cfg["upsample_initial_channel"]
-        frame_rate = Tp + 4 * H * Tp + C * Tp + 3 * C * Tp + ch * Tp          # mask, h / h2 / acts / skip, noise, lat, pre
-        L, biggest = T, 0
-        for u in self.cfg["upsample_rates"]:
-            ch //= 2
-            L *= u
-            biggest = max(biggest, ch * L)
-        return 4 * B * (frame_rate + 5 * biggest)
+        frame_rate, dec = _workspace_elems(self.cfg, B, T)
+        return 4 * (frame_rate + _DEC_BUFFERS * dec)
 
     def _zeros_like_cached(self, t):
         """An all-zero tensor of ``t``'s shape (the ``zero_g`` conditioning, models.py:495,498) without a fill launch
@@ -813,15 +732,9 @@ class ConverterEngine:
                 layer = wn.fused_layers[i]
                 args = dict(cond=cond, cond_off=2 * H * i, cond_bs=cbs, first=i == 0, last=i == wn.n_layers - 1,
                             mask_bs=Tp, acts=ws["acts"], row_split=self.wn_row_split, winograd=winograd)
-                if self.profile is None:
-                    launch_wn_layer(layer, src, dst, ws["skip"], mask, B, T, Tp, **args)
-                else:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    launch_wn_layer(layer, src, dst, ws["skip"], mask, B, T, Tp, **args)
-                    e1.record()
-                    rs_rows = H if args["last"] else 2 * H
-                    self.profile.append(("wn_layer", 2.0 * (2 * H * H * layer["K"] + rs_rows * H) * T * B, e0, e1))
+                rs_rows = H if args["last"] else 2 * H
+                self._timed("wn_layer", 2.0 * (2 * H * H * layer["K"] + rs_rows * H) * T * B,
+                            lambda: launch_wn_layer(layer, src, dst, ws["skip"], mask, B, T, Tp, **args))
                 src, dst = dst, src
             return
         for i in range(wn.n_layers):
@@ -869,7 +782,7 @@ class ConverterEngine:
         ``generator``: None follows the ``use_bf16_generator`` switch; ``"fp32"`` / ``"bf16"`` choose the generator's
         kernels for this call, whatever the switch says and without touching it (the bf16 generator is built on first
         use, as for a bf16 live pool)."""
-        use_bf16 = getattr(self, "_bf16_on", False)
+        use_bf16 = self._bf16_on
         if _lib.check_generator(generator, optional=True) is not None:
             use_bf16 = generator == "bf16"
         dev = self.device
@@ -895,13 +808,7 @@ class ConverterEngine:
         else:
             ws["noise"][:, :, :T].copy_(noise.to(dev, torch.float32))     # into the padded-row layout
         _lib.call("ov_sequence_mask_f32", lengths, mask, B, T, Tp)
-        # conditioning GEMVs (T = 1): modules.py:189-190 for every WN, models.py:275 for the decoder
-        g_q = self._zeros_like_cached(g_src) if self.zero_g else g_src
-        g_d = self._zeros_like_cached(g_tgt) if self.zero_g else g_tgt
-        conds = dict(q=self._wn_cond(self.q_wn, g_q),
-                     src=[self._wn_cond(cp["wn"], g_src) for cp in self.couplings],
-                     tgt=[self._wn_cond(cp["wn"], g_tgt) for cp in self.couplings])
-        cond_d = self._linear(g_d, self.dec_cond_w, self.dec_cond_b)
+        conds = self._conds(g_src, g_tgt)
         # ---- posterior encoder + flows at frame rate ---------------------------------------------------
         # (measured and dropped: issuing this part -- ~100 launches of <= 1.3 tiles per workgroup slot -- as 2 / 4
         # independent sub-batch chains on separate HIP streams, so that one chain's tiles would fill the other's
@@ -910,13 +817,8 @@ class ConverterEngine:
         z, z_p, z_hat = ws["z"], ws["z_p"], ws["z_hat"]
         # ---- generator (models.py:272-291); z_hat * y_mask is the identity (z_hat already masked) --
         if use_bf16:
-            if self.profile is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            o_hat = self._live_generator_bf16().decode(z_hat[:, :, :T], g_d.unsqueeze(-1))
-            if self.profile is not None:
-                e1.record()
-                self.profile.append(("gen_bf16", 0.0, e0, e1))
+            g_d = self._zeros_like_cached(g_tgt) if self.zero_g else g_tgt
+            o_hat = self._timed("gen_bf16", 0.0, lambda: self.bf16_generator().decode(z_hat[:, :, :T], g_d.unsqueeze(-1)))
             if skip_padding:
                 # the bf16 generator has no length-aware work lists (it computes the padded batch); the contract of
                 # skip_padding -- every sample beyond an utterance's own length is zero -- is kept by masking
@@ -924,7 +826,7 @@ class ConverterEngine:
                 o_hat.masked_fill_(torch.arange(o_hat.shape[2], device=dev).view(1, 1, -1) >= keep_samples, 0.0)
         else:
             limits = self.frame_limits(lengths, T) if skip_padding else None
-            o_hat = self.decode(z_hat, cond_d, ws, T=T, limits=limits)
+            o_hat = self.decode(z_hat, conds["d"], ws, T=T, limits=limits)
         # fresh dense tensors for the caller (the workspace is reused by the next call): padded rows -> [.., T]
         dense = torch.empty(3, B, C, T, dtype=torch.float32, device=dev)
         _lib.call("ov_unpad_rows_f32", ws["lat"], dense, 3 * B * C, T, Tp)
@@ -962,9 +864,9 @@ class ConverterEngine:
     def graphed(self, B, T, tau, src_rows=1, tgt_rows=1, max_cached=4, skip_padding=False):
         """``voice_conversion`` for one fixed (B, T, tau) as a captured HIP graph (see ``GraphedConversion``);
         the most recent ``max_cached`` shapes stay resident."""
-        key = (int(B), int(T), float(tau), int(src_rows), int(tgt_rows), bool(getattr(self, "_bf16_on", False)),
+        key = (int(B), int(T), float(tau), int(src_rows), int(tgt_rows), self._bf16_on,
                bool(skip_padding), bool(self._split3_on), self.split3_products)
-        cache = self.__dict__.setdefault("_graphs", {})
+        cache = self._graphs
         g = cache.pop(key, None)
         if g is None:
             g = GraphedConversion(self, B, T, tau, src_rows, tgt_rows, skip_padding=skip_padding)
@@ -976,11 +878,19 @@ class ConverterEngine:
     def use_bf16_generator(self, enable=True):
         """Route ``voice_conversion``'s generator through the bf16 kernels (BASELINE.json configs[4]).  Off by
         default: the fp32 path is the one held to the 1e-3 parity bar."""
-        if enable and self.generator_bf16 is None:
-            from .bf16 import GeneratorBf16
-            self.generator_bf16 = GeneratorBf16(self._state_dict_for_bf16, self.cfg, self.device)
+        if enable:
+            self.bf16_generator()
         self._bf16_on = bool(enable)
         return self
+
+    def bf16_generator(self):
+        """The bf16 channels-last generator of this checkpoint (``bf16.GeneratorBf16``), built on first use.  Asking for
+        it neither reads nor sets the ``use_bf16_generator`` switch: a call's or a live pool's ``generator="bf16"`` and
+        the fp32 path share one engine."""
+        if self.generator_bf16 is None:
+            from .bf16 import GeneratorBf16
+            self.generator_bf16 = GeneratorBf16(self._state_dict_for_bf16, self.cfg, self.device)
+        return self.generator_bf16
 
     def use_split_bf16x3(self, enable=True, products=6):
         """Run the MRF ResBlocks of the generator stages with C >= 128 (``SPLIT_MIN_CHANNELS``; stages 0-1 of the released
@@ -996,88 +906,52 @@ class ConverterEngine:
             raise _lib.OvError(f"use_split_bf16x3: products must be 6 or 3, got {products!r}")
         if enable and self.split_resblocks is None:
             from . import split3
-            sd, cfg = self._state_dict_for_bf16, self.cfg
-            kernels, dils = cfg["resblock_kernel_sizes"], cfg["resblock_dilation_sizes"]
-            ch = cfg["upsample_initial_channel"]
-            stages = []
-            for i in range(len(cfg["upsample_rates"])):
-                ch //= 2
-                ok = all(split3.supported(ch, ch, rk, d) and split3.supported(ch, ch, rk, 1)
-                         for rk, rd in zip(kernels, dils) for d in rd)
-                # C = 64 (stage 2) stays on the fp32 Winograd launches: its split convs tie with them (20.9 vs 21.5 ms) and
-                # cost two layout passes over the stage's tensors (1.3 ms): 104.3 -> 102.8 ms (profiles/r06_s34_*)
-                if not ok or ch < SPLIT_MIN_CHANNELS:
-                    stages.append(None)
-                    continue
-                stage = []
-                for j, (rk, rd) in enumerate(zip(kernels, dils)):
-                    rb = f"dec.resblocks.{i * len(kernels) + j}"
-                    stage.append([(split3.PackedConvSplit3(effective_weight(sd, f"{rb}.convs1.{n}"), sd[f"{rb}.convs1.{n}.bias"],
-                                                           self.device, dil=d),
-                                   split3.PackedConvSplit3(effective_weight(sd, f"{rb}.convs2.{n}"), sd[f"{rb}.convs2.{n}.bias"],
-                                                           self.device, dil=1)) for n, d in enumerate(rd)])
-                stages.append(stage)
-            self.split_resblocks = stages
+            convs = list(resblock_convs(self.cfg))
+            # C = 64 (stage 2) stays on the fp32 Winograd launches: its split convs tie with them (20.9 vs 21.5 ms) and
+            # cost two layout passes over the stage's tensors (1.3 ms): 104.3 -> 102.8 ms (profiles/r06_s34_*)
+            keep = lambda i: all(c.ch >= SPLIT_MIN_CHANNELS and split3.supported(c.ch, c.ch, c.K, c.dil)
+                                 and split3.supported(c.ch, c.ch, c.K, 1) for c in convs if c.stage == i)
+            self.split_resblocks = _resblock_tree(self._state_dict_for_bf16, self.cfg, lambda c, w, b, d:
+                                                  split3.PackedConvSplit3(w, b, self.device, dil=d), keep)
         self._split3_on = bool(enable)
         self.split3_products = products
-        self.__dict__.pop("_graphs", None)        # captured graphs hold the other path's launches
+        self._graphs.clear()                      # captured graphs hold the other path's launches
         return self
 
-    def _split_buffers(self, ws, B, ch, L):
-        """Plane tensors (3, B, L, ch) bf16 of the split-precision stages: the activated stage input, the conv1 output,
+    def _split_buffers(self, ws, B, st, L):
+        """Plane tensors (3, B, L, ch) bf16 of split-precision stage ``st``: the activated stage input, the conv1 output,
         two ping-pong pair outputs and one result per ResBlock; allocated once per workspace at the largest stage."""
         nk = len(self.cfg["resblock_kernel_sizes"])
-        need = 3 * B * L * ch
+        need = 3 * B * L * st.ch
         bufs = ws.get("split3")
         if bufs is None:
             # sized ONCE per workspace, at the largest split stage of this (batch, frames) -- stage i has ch_i channels at
-            # frames x prod(rates[:i + 1]) columns -- and never from a capturing graph's private pool
+            # frames x rate_out_i columns -- and never from a capturing graph's private pool
             if torch.cuda.is_current_stream_capturing():
                 raise _lib.OvError("split-precision plane buffers must exist before graph capture: run one eager conversion "
                                    "of this (batch, frames) shape first")
-            cfg, frames = self.cfg, L // self._stage_rate(ch)
-            c, rate, largest = cfg["upsample_initial_channel"], 1, need
-            for i, u in enumerate(cfg["upsample_rates"]):
-                c, rate = c // 2, rate * u
-                if self.split_resblocks is not None and self.split_resblocks[i] is not None:
-                    largest = max(largest, 3 * B * frames * rate * c)
+            frames = L // st.rate_out
+            largest = max([need] + [3 * B * frames * o.rate_out * o.ch for o in self.stages
+                                    if self.split_resblocks[o.index] is not None])
             bufs = ws["split3"] = [torch.empty(largest, dtype=torch.bfloat16, device=self.device) for _ in range(4 + nk)]
         assert bufs[0].numel() >= need
-        return [b[:need].view(3, B, L, ch) for b in bufs]
+        return [b[:need].view(3, B, L, st.ch) for b in bufs]
 
-    def _stage_rate(self, ch):
-        """Columns per frame at the generator stage that has ``ch`` channels."""
-        c, rate = self.cfg["upsample_initial_channel"], 1
-        for u in self.cfg["upsample_rates"]:
-            c, rate = c // 2, rate * u
-            if c == ch:
-                return rate
-        raise _lib.OvError(f"no generator stage with {ch} channels")
-
-    def _mrf_split(self, stage, u, acc, ws, B, ch, L, limits=None, rate=1):
-        """One MRF stage on the split-precision kernels: u (B, ch, L) fp32 raw -> acc (B, ch, L) fp32 = mean of the
+    def _mrf_split(self, st, u, acc, ws, B, L, limits=None):
+        """The MRF of stage ``st`` on the split-precision kernels: u (B, ch, L) fp32 raw -> acc (B, ch, L) fp32 = mean of the
         ResBlock1 outputs.  Tensors between the launches are plane tensors stored ACTIVATED (the producer applies the
         next conv's leaky ReLU before it splits); conv2 reads its residual from the pair's activated input and inverts
         the activation in fp32; the last pair of a ResBlock stores raw; the sum / mean is the layout kernel back."""
         from . import split3
+        stage, ch = self.split_resblocks[st.index], st.ch
         nk = len(stage)
-        bufs = self._split_buffers(ws, B, ch, L)
+        bufs = self._split_buffers(ws, B, st, L)
         xa, t, ping, pong, results = bufs[0], bufs[1], bufs[2], bufs[3], bufs[4:]
         prod = self.split3_products
         # length-aware work lists (skip_padding): 128-column tiles beyond an utterance's limit are dropped from every
         # conv's (dense) work list; the two layout kernels stream whole tensors
-        lim = dict(col_limit=limits, col_limit_scale=rate) if limits is not None else {}
-
-        def timed(tag, flops, fn):
-            if self.profile is None:
-                fn()
-                return
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            self.profile.append((tag, flops, e0, e1))
-
+        lim = dict(col_limit=limits, col_limit_scale=st.rate_out) if limits is not None else {}
+        timed = self._timed
         uv = u[:B * ch * L].view(B, ch, L)
         timed("split_layout", 0.0, lambda: split3.to_planes(uv, LRELU_SLOPE, out=xa))
         for j, pairs in enumerate(stage):
@@ -1101,7 +975,7 @@ class ConverterEngine:
         """``limit_margin_frames`` of this engine's configuration for a (B, T) launch under the CURRENT
         ``use_winograd`` / ``fuse_pairs`` (they may be switched after construction); at least ``generator_margin``."""
         key = (int(B), int(T), bool(self.use_winograd), bool(self.fuse_pairs))
-        cache = self.__dict__.setdefault("_limit_margins", {})
+        cache = self._limit_margins
         if key not in cache:
             cache[key] = max(self.generator_margin, limit_margin_frames(self.cfg, *key))
         return cache[key]
@@ -1200,6 +1074,32 @@ class ConverterEngine:
             for j in range(nk):                     # every chain's scratch is free again before the next stage
                 main.wait_event(done[j])
 
+    def _stage(self, st, x, x_ld, x_bs, bufs, out, ws, B, L, cond_d=None, limits=None, keep=None):
+        """Generator stage ``st`` (models.py:274-291) on the fp32 kernels: [conv_pre + cond into ``ws["pre"]`` (stage 0)],
+        leaky_relu + ConvTranspose, the MRF, [leaky_relu(0.01) + conv_post + tanh into ``out`` (last stage)].  ``x``
+        [B rows of ``x_bs``][cin][``x_ld``] with ``L`` columns; ``bufs`` = (u, t1, ra, acc), dense [B, ch, L * stride]
+        each: the ConvTranspose output, the MRF's two scratch buffers -- None for a split-precision stage, which takes
+        its plane buffers from ``ws`` -- and the MRF mean.  ``limits`` / ``keep``: the two rows of ``frame_limits``."""
+        lim = lambda scale: dict(col_limit=limits, col_limit_scale=scale) if limits is not None else {}
+        if st.index == 0:
+            Tp = ws["Tp"]
+            self._conv(self.conv_pre, x, 0, x_bs, ws["pre"], 0, st.cin * Tp, B, L, bias_b=cond_d,
+                       bias_b_bs=0 if cond_d.shape[0] == 1 else cond_d.shape[1], x_ld=x_ld, out_ld=Tp, tag="conv_pre",
+                       **lim(1))
+            x, x_ld = ws["pre"], Tp
+        u, t1, ra, acc = bufs
+        self._upsample(st.index, x, x_ld, u, B, L, st.cin, st.ch, **lim(st.rate_in))
+        L *= st.stride
+        if t1 is None:
+            self._mrf_split(st, u, acc, ws, B, L, limits=limits)
+        else:
+            self._mrf(st.index, u, t1, ra, acc, ws, B, st.ch, L, limits, st.rate_out)
+        if st.last and keep is not None:
+            _lib.call("ov_conv_post_tanh_limited_f32", acc, self.post_w, out, B, st.ch, L, self.post_w.shape[1],
+                      FINAL_LRELU_SLOPE, keep, st.rate_out)
+        elif st.last:
+            _lib.call("ov_conv_post_tanh_f32", acc, self.post_w, out, B, st.ch, L, self.post_w.shape[1], FINAL_LRELU_SLOPE)
+
     def decode(self, z_hat, cond_d, ws=None, T=None, limits=None):
         """Generator (models.py:272-291).  ``z_hat`` is [B, C, ld] with ``T`` valid frames per row
         (``T`` defaults to the full row, i.e. a dense tensor).  ``limits`` (``frame_limits``): frames per utterance
@@ -1208,9 +1108,6 @@ class ConverterEngine:
         T = ld if T is None else T
         if ws is None:
             ws = self._workspace(B, T)
-        Tp = ws["Tp"]
-        cfg = self.cfg
-        ch = cfg["upsample_initial_channel"]
         keep = None
         if limits is not None:
             limits, keep = limits[0], limits[1]
@@ -1219,40 +1116,20 @@ class ConverterEngine:
                 # tensors, but conv_post (a per-utterance limit, no table) still keeps `length` frames and writes zeros
                 # beyond them -- the skip_padding contract ("the padded tail of o_hat is zero") holds at any batch size
                 limits = None
-        lim = lambda scale: dict(col_limit=limits, col_limit_scale=scale) if limits is not None else {}
-        self._conv(self.conv_pre, z_hat, 0, C * ld, ws["pre"], 0, ch * Tp, B, T, bias_b=cond_d,
-                   bias_b_bs=0 if cond_d.shape[0] == 1 else cond_d.shape[1], x_ld=ld, out_ld=Tp, tag="conv_pre",
-                   **lim(1))
-        x, L, x_ld = ws["pre"], T, Tp
+        o_hat = torch.empty(B, 1, T * self.total_upsample, dtype=torch.float32, device=self.device)
+        x, x_ld, x_bs = z_hat, ld, C * ld
         free = list(ws["dec"])
-        rate = 1                                  # columns per frame at the current stage
-        for i, up in enumerate(self.ups):
-            s = up["stride"]
-            cin, ch = ch, ch // 2
+        for st in self.stages:
             u = free.pop()
-            self._upsample(i, x, x_ld, u, B, L, cin, ch, **lim(rate))
-            rate *= s
-            if i > 0:
-                free.append(x)
-            L *= s
-            x_ld = L
-            if self._split3_on and self.split_resblocks[i] is not None:
-                # split-precision stage (opt-in); with limits its convs carry the same length-aware work lists
-                acc = free.pop()
-                self._mrf_split(self.split_resblocks[i], u, acc, ws, B, ch, L, limits=limits, rate=rate)
-                free.append(u)
-                x = acc
-                continue
-            t1, ra, acc = free.pop(), free.pop(), free.pop()
-            self._mrf(i, u, t1, ra, acc, ws, B, ch, L, limits, rate)
-            free += [u, t1, ra]
-            x = acc
-        o_hat = torch.empty(B, 1, L, dtype=torch.float32, device=self.device)
-        if keep is not None:
-            _lib.call("ov_conv_post_tanh_limited_f32", x, self.post_w, o_hat, B, ch, L, self.post_w.shape[1],
-                      FINAL_LRELU_SLOPE, keep, rate)
-        else:
-            _lib.call("ov_conv_post_tanh_f32", x, self.post_w, o_hat, B, ch, L, self.post_w.shape[1], FINAL_LRELU_SLOPE)
+            if st.index > 0:
+                free.append(x)            # the stage's input is free once its ConvTranspose has read it: it serves as t1
+            # a split-precision stage (opt-in) keeps its intermediates in plane buffers of its own
+            split = self._split3_on and self.split_resblocks[st.index] is not None
+            t1, ra = (None, None) if split else (free.pop(), free.pop())
+            acc = free.pop()
+            self._stage(st, x, x_ld, x_bs, (u, t1, ra, acc), o_hat, ws, B, T * st.rate_in, cond_d, limits, keep)
+            free += [u] if split else [u, t1, ra]
+            x, x_ld = acc, T * st.rate_out
         return o_hat
 
     # ---- live streams (openvoice_amd/live.py): one conversion unit on caller-given buffers -----------------------
@@ -1266,12 +1143,12 @@ class ConverterEngine:
         WaveNet tensors and the mask in the ``_workspace`` layout (ld = ``padded_frames(width)``).  Generator stage i:
         the conv_pre output (stage 0), the ConvTranspose output and the two MRF scratch buffers, and the MRF output of
         the last stage (conv_post reads it)."""
-        cache = self.__dict__.setdefault("_live_ws", {})
+        cache = self._live_ws
         ws = cache.get((key, B))
         if ws is not None:
             assert ws["width"] >= width, "live unit wider than its workspace"
             return ws
-        self.live_ws_builds = getattr(self, "live_ws_builds", 0) + 1
+        self.live_ws_builds += 1
         dev, H = self.device, self.hidden
         z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
         Tp = padded_frames(width)
@@ -1279,28 +1156,28 @@ class ConverterEngine:
             ws = dict(Tp=Tp, mask=z(B, Tp), mask_len=-1, h=z(B, H, Tp), h2=z(B, H, Tp), acts=z(B, H, Tp),
                       skip=z(B, H, Tp))
         else:
-            ch, rate_in = self.cfg["upsample_initial_channel"], 1
-            for u in self.cfg["upsample_rates"][:stage]:
-                ch, rate_in = ch // 2, rate_in * u
-            out_cols = width * self.cfg["upsample_rates"][stage]
-            n = B * (ch // 2) * out_cols
+            st = self.stages[stage]
+            n = B * st.ch * width * st.stride
             ws = dict(Tp=Tp, dec=[z(n) for _ in range(3)])
             if stage == 0:
-                ws["pre"] = z(B, ch, Tp)
-            if stage == len(self.cfg["upsample_rates"]) - 1:
+                ws["pre"] = z(B, st.cin, Tp)
+            if st.last:
                 ws["acc"] = z(n)
         ws["width"] = width
         cache[(key, B)] = ws
         return ws
 
-    def live_conds(self, g_src, g_tgt):
-        """Per-row conditioning of a live launch (``g_src`` / ``g_tgt`` [B, gin]): the WaveNet gate biases of the
-        posterior encoder and of every coupling in both directions, and the generator's cond bias."""
+    def _conds(self, g_src, g_tgt):
+        """Conditioning GEMVs (T = 1) of ``g_src`` / ``g_tgt`` [rows, gin]: the WaveNet gate biases (modules.py:189-190)
+        of the posterior encoder (``q``) and of every coupling in both directions (``src``, ``tgt``), and the generator's
+        cond bias (``d``, models.py:275)."""
         g_q = self._zeros_like_cached(g_src) if self.zero_g else g_src
         g_d = self._zeros_like_cached(g_tgt) if self.zero_g else g_tgt
         return dict(q=self._wn_cond(self.q_wn, g_q), src=[self._wn_cond(cp["wn"], g_src) for cp in self.couplings],
                     tgt=[self._wn_cond(cp["wn"], g_tgt) for cp in self.couplings],
                     d=self._linear(g_d, self.dec_cond_w, self.dec_cond_b))
+
+    live_conds = _conds      # per-row conditioning of a live launch
 
     def _live_mask(self, ws, B, L):
         if ws["mask_len"] != L:
@@ -1338,60 +1215,37 @@ class ConverterEngine:
         ``x_bs``][C_in][``x_ld``] with ``L`` columns -> ``out`` dense [B, C_out, L * stride] ([B, 1, L * stride] for the
         last stage).  ``decode``'s own launches (``_upsample``, ``_mrf``): bit-identical per column to a one-pass run
         whose columns line up with the same Winograd tiles."""
-        if getattr(self, "_bf16_on", False) or self._split3_on:
+        if self._bf16_on or self._split3_on:
             raise _lib.OvError("live streams run the fp32 generator only (use_bf16_generator / split_bf16x3 are off)")
-        cfg = self.cfg
-        ch = cfg["upsample_initial_channel"]
-        for _ in range(i):
-            ch //= 2
-        if i == 0:
-            Tp = ws["Tp"]
-            self._conv(self.conv_pre, x, 0, x_bs, ws["pre"], 0, ch * Tp, B, L, bias_b=cond_d,
-                       bias_b_bs=0 if cond_d.shape[0] == 1 else cond_d.shape[1], x_ld=x_ld, out_ld=Tp, tag="conv_pre")
-            x, x_ld, x_bs = ws["pre"], Tp, ch * Tp
-        s = self.ups[i]["stride"]
+        st = self.stages[i]
         u, t1, ra = ws["dec"]
-        self._upsample(i, x, x_ld, u, B, L, ch, ch // 2)
-        last = i == len(self.ups) - 1
-        acc = ws["acc"] if last else out
-        self._mrf(i, u, t1, ra, acc, ws, B, ch // 2, L * s, None, 1)
-        if last:
-            _lib.call("ov_conv_post_tanh_f32", acc, self.post_w, out, B, ch // 2, L * s, self.post_w.shape[1],
-                      FINAL_LRELU_SLOPE)
+        self._stage(st, x, x_ld, x_bs, (u, t1, ra, ws["acc"] if st.last else out), out, ws, B, L, cond_d)
 
     # The same unit on the bf16 channels-last generator (``LivePool(generator="bf16")``).  The precision belongs to the
     # pool that asks for it: nothing here reads or sets ``_bf16_on``, so fp32 and bf16 pools share one engine.
-    def _live_generator_bf16(self):
-        if self.generator_bf16 is None:
-            from .bf16 import GeneratorBf16
-            self.generator_bf16 = GeneratorBf16(self._state_dict_for_bf16, self.cfg, self.device)
-        return self.generator_bf16
-
     @torch.no_grad()
     @on_own_device
     def live_cond_bf16(self, g_tgt):
         """``g_tgt`` [rows, gin] -> the bf16 generator's conv_pre bias rows [rows, ch] (``GeneratorBf16.cond_rows``: the
         launch ``decode`` issues, conv_pre's bias folded in -- not ``live_conds``' ``d``)."""
         g_d = self._zeros_like_cached(g_tgt) if self.zero_g else g_tgt
-        return self._live_generator_bf16().cond_rows(g_d)
+        return self.bf16_generator().cond_rows(g_d)
 
     def live_workspace_bf16(self, key, B, width, stage):
         """Scratch of one bf16 generator unit launch of ``B`` rows, ``width`` input columns at most, cached per
         ``(key, B)`` like ``live_workspace`` (same counter, ``live_ws_builds``): the channels-last bf16 input and
         output of the stage, the stage's own scratch buffers, and the conv_pre output (stage 0)."""
-        cache = self.__dict__.setdefault("_live_ws_bf16", {})
+        cache = self._live_ws_bf16
         ws = cache.get((key, B))
         if ws is not None:
             assert ws["width"] >= width, "live unit wider than its workspace"
             return ws
-        self.live_ws_builds = getattr(self, "live_ws_builds", 0) + 1
-        gen = self._live_generator_bf16()
+        self.live_ws_builds += 1
         f = lambda n: torch.empty(n, dtype=torch.bfloat16, device=self.device)
-        ch = self.cfg["upsample_initial_channel"] >> stage
-        last = stage == len(self.cfg["upsample_rates"]) - 1
-        n = gen.stage_scratch_elems(stage, B, width)
-        ws = dict(width=width, xin=f(B * width * (self.inter if stage == 0 else ch)), out=None if last else f(n),
-                  bufs=[f(n) for _ in range(4 if last else 3)], pre=f(B * width * ch) if stage == 0 else None)
+        st = self.stages[stage]
+        n = self.bf16_generator().stage_scratch_elems(stage, B, width)
+        ws = dict(width=width, xin=f(B * width * (self.inter if stage == 0 else st.cin)), out=None if st.last else f(n),
+                  bufs=[f(n) for _ in range(4 if st.last else 3)], pre=f(B * width * st.cin) if stage == 0 else None)
         cache[(key, B)] = ws
         return ws
 
@@ -1404,21 +1258,19 @@ class ConverterEngine:
         itself); ``ws`` from ``live_workspace_bf16``, ``cond_d`` [B, ch] from ``live_cond_bf16`` (stage 0).  The tensor
         between two stages is what ``GeneratorBf16.decode`` keeps there, widened to fp32 and rounded back without
         loss.  Exactly ``L`` columns are launched: the bf16 launchers take any L >= 1."""
-        if getattr(self, "_bf16_on", False) or self._split3_on:
+        if self._bf16_on or self._split3_on:
             raise _lib.OvError("a live unit's generator is chosen by its pool (use_bf16_generator / split_bf16x3 are off)")
-        gen = self._live_generator_bf16()
-        ch = self.cfg["upsample_initial_channel"] >> i
-        cin = self.inter if i == 0 else ch
-        s = self.ups[i]["stride"]
+        gen, st = self.bf16_generator(), self.stages[i]
+        cin, s = self.inter if i == 0 else st.cin, st.stride
         xin = ws["xin"][: B * L * cin].view(B, L, cin)
         _lib.call("ov_rows_f32_to_cl_bf16", x, x_bs, x_ld, xin, B, cin, L)
         bufs = list(ws["bufs"])
-        if i == len(self.ups) - 1:
+        if st.last:
             gen.stage(i, xin, out[: B * L * s].view(B, 1, L * s), B, L, cond=cond_d, bufs=bufs, pre=ws["pre"])
             return
-        o = ws["out"][: B * L * s * (ch // 2)].view(B, L * s, ch // 2)
+        o = ws["out"][: B * L * s * st.ch].view(B, L * s, st.ch)
         gen.stage(i, xin, o, B, L, cond=cond_d, bufs=bufs, pre=ws["pre"])
-        _lib.call("ov_cl_bf16_to_rows_f32", o, out, (ch // 2) * L * s, L * s, B, ch // 2, L * s)
+        _lib.call("ov_cl_bf16_to_rows_f32", o, out, st.ch * L * s, L * s, B, st.ch, L * s)
 
     # ---- extract_se path -----------------------------------------------------------------------------
     @torch.no_grad()

@@ -41,24 +41,34 @@ def cpu_model():
     return "unknown"
 
 
-def kernel_source_digest():
-    """sha256 (16 hex digits) over the kernel sources, the C ABI header and the launch sequence -- what decides the
-    HBM traffic of a conversion.  Measurement records (profiles/pmc_traffic_latest.json) carry it, and bench.py only
-    reports a PMC traffic figure whose digest equals the running tree's."""
-    import glob
+_HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def _digest(paths):
+    """sha256 (16 hex digits) over the names and contents of ``paths`` (relative to the package), in sorted order."""
     import hashlib
-    here = os.path.dirname(os.path.abspath(__file__))
-    files = sorted(glob.glob(os.path.join(here, "csrc", "*.hip")) + glob.glob(os.path.join(here, "csrc", "*.h")) +
-                   glob.glob(os.path.join(here, "..", "include", "*.h")) + [os.path.join(here, "engine.py")])
-    # the opt-in paths' kernels (bf16 generator: conv1d_bf16*; split-precision MRF: conv1d_split3*) launch nothing on
-    # the fp32 path the record is about
-    files = [f for f in files if not os.path.basename(f).startswith(("conv1d_bf16", "conv1d_split3"))]
     h = hashlib.sha256()
-    for f in files:
+    for f in sorted(os.path.join(_HERE, p) for p in paths):
         h.update(os.path.basename(f).encode())
         with open(f, "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()[:16]
+
+
+def _glob(*patterns):
+    import glob
+    return [os.path.relpath(f, _HERE) for p in patterns for f in glob.glob(os.path.join(_HERE, p))]
+
+
+def kernel_source_digest():
+    """sha256 (16 hex digits) over the kernel sources, the C ABI header and the launch sequence (engine.py and the stage
+    geometry it reads from generator.py) -- what decides the HBM traffic of a conversion.  Measurement records
+    (profiles/pmc_traffic_latest.json) carry it, and bench.py only reports a PMC traffic figure whose digest equals the
+    running tree's."""
+    files = _glob("csrc/*.hip", "csrc/*.h", "../include/*.h") + ["engine.py", "generator.py"]
+    # the opt-in paths' kernels (bf16 generator: conv1d_bf16*; split-precision MRF: conv1d_split3*) launch nothing on
+    # the fp32 path the record is about
+    return _digest(f for f in files if not os.path.basename(f).startswith(("conv1d_bf16", "conv1d_split3")))
 
 
 def launch_config_digest(batch, frames, fuse_pairs, pair_policy, chain_streams=1):
@@ -73,30 +83,12 @@ def launch_config_digest(batch, frames, fuse_pairs, pair_policy, chain_streams=1
 
 
 def bf16_source_digest():
-    """sha256 (16 hex digits) over what decides the opt-in bf16 generator's launches: its kernels and bf16.py.  The
-    counter record profiles/bf16_counters_latest.json carries it (tools/bf16_counters.py)."""
-    import glob
-    import hashlib
-    here = os.path.dirname(os.path.abspath(__file__))
-    files = sorted(glob.glob(os.path.join(here, "csrc", "conv1d_bf16*")) + [os.path.join(here, "bf16.py")])
-    h = hashlib.sha256()
-    for f in files:
-        h.update(os.path.basename(f).encode())
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-    return h.hexdigest()[:16]
+    """sha256 (16 hex digits) over what decides the opt-in bf16 generator's launches: its kernels, bf16.py and the stage
+    geometry of generator.py.  The counter record profiles/bf16_counters_latest.json carries it (tools/bf16_counters.py)."""
+    return _digest(_glob("csrc/conv1d_bf16*") + ["bf16.py", "generator.py"])
 
 
 def split3_source_digest():
     """sha256 (16 hex digits) over the split-precision conv kernels and their host helpers.  The counter record
     profiles/split3_traffic_latest.json carries it (tools/pmc_traffic_split.py)."""
-    import glob
-    import hashlib
-    here = os.path.dirname(os.path.abspath(__file__))
-    files = sorted(glob.glob(os.path.join(here, "csrc", "conv1d_split3*")) + [os.path.join(here, "split3.py")])
-    h = hashlib.sha256()
-    for f in files:
-        h.update(os.path.basename(f).encode())
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-    return h.hexdigest()[:16]
+    return _digest(_glob("csrc/conv1d_split3*") + ["split3.py"])

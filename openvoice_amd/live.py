@@ -44,6 +44,7 @@ import torch
 
 from . import _lib, rates
 from . import noise as noise_mod
+from .generator import generator_stages, samples_per_frame
 from .longform import launch_ladder, stream_end_frames, winograd_grid_frames
 from .params import ENC_Q_KERNEL, ENC_Q_LAYERS, FLOW_KERNEL, FLOW_LAYERS, N_FLOWS
 
@@ -108,13 +109,6 @@ def live_units(cfg):
     for u in units:
         u["history"] = u["left"] + u["align"] - 1
     return units
-
-
-def samples_per_frame(cfg):
-    spf = 1
-    for s in cfg["upsample_rates"]:
-        spf *= s
-    return spf
 
 
 def live_right_samples(cfg):
@@ -314,18 +308,16 @@ class LivePool:
         pad4 = lambda n: (n + 3) // 4 * 4
         from .engine import padded_frames
         cas = Cascade(self.units, self.chunk)
-        ch = self.cfg["upsample_initial_channel"]
+        stages = generator_stages(self.cfg)
         self.rows, self.cap, self.width, self.ld_in, self.ld_out, self.cout = [], [], [], [], [], []
         for k, u in enumerate(self.units):
             W = cas.width(k)
             self.width.append(W)
             self.cap.append(pad4(cas.capacity(k)))
             if u["kind"] == "g":
-                cin = self.inter if u["stage"] == 0 else ch
-                ch //= 2
-                cout = ch
-                if u["stage"] == len(self.cfg["upsample_rates"]) - 1:
-                    cout = 1
+                st = stages[u["stage"]]
+                cin = self.inter if st.index == 0 else st.cin
+                cout = 1 if st.last else st.ch
                 self.ld_in.append(pad4(W))
                 self.ld_out.append(W * u["stride"])           # dense per launch: ld = L * stride
             else:

@@ -25,7 +25,7 @@ import torch
 
 from . import _lib, rates
 from . import noise as noise_mod
-from .engine import GENERATOR_MARGIN, generator_margin_frames
+from .generator import GENERATOR_MARGIN, generator_margin_frames, generator_stages, samples_per_frame
 from .params import ENC_Q_KERNEL, ENC_Q_LAYERS, FLOW_KERNEL, FLOW_LAYERS, N_FLOWS
 
 # Defaults, picked with tools/bench_long.py (profiles/r07_bench_long.jsonl, 20 min file): 8192-frame windows (95 s, 3 % of
@@ -50,10 +50,9 @@ def winograd_grid_frames(cfg):
     tile = 4
     for d in [1] + [v for dl in cfg["resblock_dilation_sizes"] for v in dl]:
         tile = tile * 4 * d // math.gcd(tile, 4 * d)
-    g, rate = 1, 1
-    for u in cfg["upsample_rates"]:
-        rate *= u
-        gi = tile // math.gcd(tile, rate)
+    g = 1
+    for st in generator_stages(cfg):
+        gi = tile // math.gcd(tile, st.rate_out)
         g = g * gi // math.gcd(g, gi)
     return g
 
@@ -116,11 +115,8 @@ def one_pass_limit_frames(cfg):
     (12.3 min at 22.05 kHz); the Winograd bound alone would be 262 144 frames (50.7 min)."""
     u32, s32 = (1 << 32) - 1, (1 << 31) - 1
     checks = []                                    # (elements per frame, largest accepted element count)
-    ch, rate = cfg["upsample_initial_channel"], 1
-    for u in cfg["upsample_rates"]:
-        cin, ch = ch, ch // 2
-        checks.append((cin * rate, u32))                         # ConvTranspose (phase conv) input rows
-        rate *= u
+    for _, cin, ch, u, rate_in, rate, _ in generator_stages(cfg):
+        checks.append((cin * rate_in, u32))                      # ConvTranspose (phase conv) input rows
         checks.append(((ch * u + 32) * rate, u32))               # ... its ch x u phase rows of L x u columns
         checks += [(ch * rate, u32), ((ch + 32) * rate, u32)]    # direct ResBlock convs
         checks.append((ch * rate, s32))                          # Winograd ResBlock convs
@@ -175,9 +171,7 @@ class WindowedConverter:
         self.grid = winograd_grid_frames(self.cfg)
         self.context = context_frames(self.cfg)
         self.core = window_core(self.window_frames, self.context, self.grid)
-        self.spf = 1
-        for u in self.cfg["upsample_rates"]:
-            self.spf *= u
+        self.spf = samples_per_frame(self.cfg)
         self.inter = self.cfg["inter_channels"]
 
     def _device(self):

@@ -260,7 +260,7 @@ class TtsEngine:
         cond_d = core._linear(g, core.dec_cond_w, core.dec_cond_b)
         Td = Ty if max_len is None else min(Ty, int(max_len))
         if generator == "bf16":
-            gen = core._live_generator_bf16()
+            gen = core.bf16_generator()
             if skip_padding:
                 o = gen.decode_groups(z, Ly, gen.cond_rows(g), y_host, Td)
             else:

@@ -276,7 +276,7 @@ def test_tts_on_the_bf16_generator(tts_model, noise):
     kw = dict(noise_scale=0.667, noise_scale_w=0.6, sdp_ratio=0.2)
     kw.update(dict(noise_w=noise_w, noise_z=noise_z) if noise == "explicit" else dict(seed=77))
     o32, attn32, ym32, lat32 = tts_model.infer(tokens, lengths, sid=sid, skip_padding=True, **kw)
-    gen = tts_model.engine().core._live_generator_bf16()
+    gen = tts_model.engine().core.bf16_generator()
     assert not getattr(tts_model.engine().core, "_bf16_on", False)
     lens = ym32[:, 0].sum(1).long()
     Ty = int(lens.max())

@@ -277,3 +277,60 @@ def test_limit_margin_prices_the_kernels_that_run():
     lost = np.flatnonzero(~_skip_padding_exact_samples(cfg, 4, 513, lengths, GENERATOR_MARGIN - 1)) + 1
     assert 113 in lost.tolist(), lost
     assert _skip_padding_exact_samples(cfg, 1, 513, lengths, GENERATOR_MARGIN - 1).all()
+
+
+def test_generator_stages_is_the_stage_table_of_the_configuration():
+    """``generator.generator_stages``: channels, stride and columns per frame of every upsampling stage (reference:
+    openvoice/models.py:244-256), for the released converter configuration and for one with other rates and width."""
+    from openvoice_amd.generator import generator_stages, samples_per_frame, scratch_per_frame
+    from openvoice_amd.utils import CONVERTER_MODEL_CONFIG
+    rows = [tuple(st) for st in generator_stages(CONVERTER_MODEL_CONFIG)]
+    #              index cin  ch  stride rate_in rate_out last
+    assert rows == [(0, 512, 256, 8, 1, 8, False), (1, 256, 128, 8, 8, 64, False), (2, 128, 64, 2, 64, 128, False),
+                    (3, 64, 32, 2, 128, 256, True)]
+    st = generator_stages(CONVERTER_MODEL_CONFIG)[1]
+    assert (st.index, st.cin, st.ch, st.stride, st.rate_in, st.rate_out, st.last) == rows[1]
+    assert samples_per_frame(CONVERTER_MODEL_CONFIG) == 256
+    assert scratch_per_frame(CONVERTER_MODEL_CONFIG) == 8192             # 128 x 64 = 64 x 128 = 32 x 256
+    other = dict(CONVERTER_MODEL_CONFIG, upsample_initial_channel=384, upsample_rates=[4, 2, 16])
+    assert [tuple(st) for st in generator_stages(other)] == [(0, 384, 192, 4, 1, 4, False), (1, 192, 96, 2, 4, 8, False),
+                                                             (2, 96, 48, 16, 8, 128, True)]
+    assert samples_per_frame(other) == 128 and scratch_per_frame(other) == 48 * 128
+
+
+def test_resblock_convs_walks_the_checkpoint_names_in_order():
+    """``generator.resblock_convs`` yields every ``dec.resblocks.R.convs1.n`` of the checkpoint exactly once, in
+    ascending (R, n) order, with the channels of its stage and the kernel size and dilation of its configuration entry;
+    ``convs2.n`` of the same pair has the same shape."""
+    import re
+    from openvoice_amd.generator import generator_stages, resblock_convs
+    from openvoice_amd.params import synthetic_state_dict
+    from openvoice_amd.utils import CONVERTER_MODEL_CONFIG
+    for cfg in (CONVERTER_MODEL_CONFIG,
+                dict(CONVERTER_MODEL_CONFIG, resblock_kernel_sizes=[7, 3], resblock_dilation_sizes=[[1, 5], [3, 1, 5]])):
+        sd = synthetic_state_dict(cfg, 513, seed=1)
+        pat = re.compile(r"dec\.resblocks\.(\d+)\.convs1\.(\d+)\.bias$")
+        in_sd = sorted((int(m.group(1)), int(m.group(2))) for m in map(pat.match, sd) if m)
+        convs = list(resblock_convs(cfg))
+        assert [(int(c.prefix.rsplit(".", 1)[1]), c.n) for c in convs] == in_sd
+        nk, stages = len(cfg["resblock_kernel_sizes"]), generator_stages(cfg)
+        for c in convs:
+            assert c.prefix == f"dec.resblocks.{c.stage * nk + c.j}" and tuple(c) == (c.stage, c.j, c.n, c.ch, c.K, c.dil,
+                                                                                       c.prefix)
+            assert c.ch == stages[c.stage].ch and c.K == cfg["resblock_kernel_sizes"][c.j]
+            assert c.dil == cfg["resblock_dilation_sizes"][c.j][c.n]
+            for name in (f"{c.prefix}.convs1.{c.n}", f"{c.prefix}.convs2.{c.n}"):
+                assert sd[name + ".bias"].shape == (c.ch,)
+                assert sd[name + ".weight_v" if name + ".weight_v" in sd else name + ".weight"].shape == (c.ch, c.ch, c.K)
+
+
+def test_workspace_bytes_keeps_its_formula():
+    """``_workspace`` and ``workspace_bytes`` share ``engine._workspace_elems``: 4 bytes x (the frame-rate tensors + five
+    decoder scratch buffers at the largest stage).  The constants are what ``workspace_bytes`` returned for the released
+    configuration before the sizes were shared (mask + 4 WaveNet tensors + noise + 3 latents + conv_pre output at
+    ``padded_frames(T)`` columns, 5 x 8192 elements per frame)."""
+    from openvoice_amd.engine import _DEC_BUFFERS, _workspace_elems
+    from openvoice_amd.utils import CONVERTER_MODEL_CONFIG
+    for (B, T), expected in (((1, 40), 6881440), ((3, 96), 49546368), ((32, 861), 4740722688)):
+        frame_rate, dec = _workspace_elems(CONVERTER_MODEL_CONFIG, B, T)
+        assert dec == B * T * 8192 and 4 * (frame_rate + _DEC_BUFFERS * dec) == expected

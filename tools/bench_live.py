@@ -110,8 +110,8 @@ def main():
                     emit(run_live(model, chunk, N, M, args.min_ticks, dev, wave, ses, generator=generator))
                 emit(run_live(model, chunk, N, M, args.min_ticks, dev, wave_in, ses, args.sr_in, args.sr_out, generator))
     if not args.no_windowed:
-        eng.__dict__.pop("_live_ws", None)         # the windowed rows' peak memory without the live workspaces
-        eng.__dict__.pop("_live_ws_bf16", None)
+        eng._live_ws.clear()                       # the windowed rows' peak memory without the live workspaces
+        eng._live_ws_bf16.clear()
         for N in args.streams:
             emit(run_windowed(model, eng, 255, N, "pool", M, args.min_ticks, dev, wave, ses))
         eng.resident_workspaces = 1

@@ -78,7 +78,7 @@ def measure_tts(group_cost):
                                     noise_w=noise_w, noise_z=noise_z, **kw)
     y_mask = call(skip_padding=True)[2]
     frames = y_mask[:, 0].sum(1).long().tolist()
-    g16 = model.engine().core._live_generator_bf16()
+    g16 = model.engine().core.bf16_generator()
     res = {"batch": B, "symbols": Tx, "frames": frames, "padded_frames": max(frames), "margin": g16.margin,
            "fp32_skip_padding": wall_ms(lambda: call(skip_padding=True)),
            "fp32_padded": wall_ms(lambda: call()),
