@@ -797,6 +797,16 @@ typedef struct ov_conv1d_wino_params {
                           * without res / add.  (2.09: this field was `reserved0`.) */
 } ov_conv1d_wino_params;
 int ov_conv1d_wino_f32(const ov_conv1d_wino_params* p, ov_stream_t stream);
+/* n = 1 .. 3 INDEPENDENT convs (no conv reads or writes a tensor another one writes) as ONE persistent launch: the three
+ * ResBlocks of an MRF step (K = 3, 7, 11 on the same shape).  Every workgroup walks its share of the K = 11 conv, then of
+ * the K = 7 conv, then of the K = 3 conv, with no device-wide synchronisation in between; the shares are cut by cost so
+ * that the launch ends with K = 3 items.  Every output element is computed by the instruction sequence of the single
+ * launch: the results are bit-identical to n calls of ov_conv1d_wino_f32, in any order of `convs`.  Each conv passes the
+ * checks of ov_conv1d_wino_f32; beyond them the convs must agree on B, L, Cin, Cout, dil, col_limit, col_limit_scale
+ * (OV_E_BADARG) and have pairwise different K, Cout % 64 == 0, frags 0 or 2, dbg NULL (OV_E_UNSUPPORTED); nothing is launched
+ * when a check fails.  nwg is read from convs[0]; n = 1 is ov_conv1d_wino_f32(convs).  (Added within 2.12: an additive
+ * symbol.) */
+int ov_conv1d_wino_multi_f32(const ov_conv1d_wino_params* convs, int n, ov_stream_t stream);
 /* 1 when (Cin, Cout, K, dil) has an instance, else 0 (callers then use ov_conv1d_f32). */
 int ov_conv1d_wino_supported(int Cin, int Cout, int K, int dil);
 /* Input channels per LDS fill of the instance for K taps and Cout rows (Cout % 128 == 0: four 32-row fragments per

@@ -152,49 +152,41 @@ __host__ __device__ inline size_t wino_pack_floats(int Cout, int Cin, int K, int
 // K = 11): ONE 32-row fragment x FOUR column sub-blocks (1 024 columns per workgroup), all four waves on the same A stream.
 // The helpers' work per MFMA doubles with every halving of the rows (the transform of a tile is shared by fewer row
 // fragments); what keeps them off the critical path is their instruction count -- see the helper section.
-template <int K, int DIL, int CI, int NF, int MW, bool DBG>
-__global__ __launch_bounds__(64 * (4 + 2 * NF), NF == 1 ? 3 : 2) void conv1d_wino_kernel(const ov_conv1d_wino_params p) {
-  using Ge = Geo<K>;
-  using Gd = GeoD<K, DIL == 1 ? 3 : DIL, NF>;   // (only read when DIL > 1)
-  constexpr int G = Ge::G, KR = CI * G, NSTEP = KR / 2, NPAIR = NSTEP / 2;
-  constexpr int NB = 4 / MW;           // column sub-blocks per workgroup
-  constexpr int NTS = 32 * NF;         // Winograd tiles per sub-block (what one matrix wave owns)
-  constexpr int NT = NTS * NB;         // Winograd tiles per N-block
-  constexpr int NCOLS = DIL == 1 ? 4 * NTS : Gd::NCOL;   // output columns per sub-block
-  constexpr int NCOL = NCOLS * NB;     // output columns per N-block
-  constexpr int RW = (DIL == 1 ? NCOLS + 16 : Gd::RW) + (NB - 1) * NCOLS;   // floats per raw LDS row: column t0 - ORG + c at index c
-  static_assert(MW == 4 || ((MW == 2 || MW == 1) && NF == 2), "two- and one-row-fragment workgroups run two fragments per wave");
-  constexpr int ORG = DIL == 1 ? 8 : Gd::PADA;
-  constexpr int RW4 = RW / 4;
-  constexpr int NHELP = 2 * NF;        // helper waves
-  static_assert(DIL == 1 || NF == 2, "dilated instances run two fragments per wave");
-  static_assert(KR % 4 == 0 && CI % 2 == 0, "k-rows in whole k-step pairs");
-  constexpr int NPR = CI / 2;            // input-channel pairs per chunk (a pair = one k-step of each group)
-  constexpr int NITEM = NPR * RW4;       // staging items per chunk: (channel pair, 4 columns) = two 16-byte vectors
-  constexpr int RAWBUF = CI * RW;        // floats per raw buffer: raw[pair][raw index][channel of the pair]
-  constexpr int VBUF = KR * NT * 6;      // floats per V buffer: V[k-row = g * CI + channel][tile][6]
-  __shared__ __attribute__((aligned(16))) float raw[2 * RAWBUF];
-  __shared__ __attribute__((aligned(16))) float Vs[2 * VBUF];
-  __shared__ __attribute__((aligned(16))) float bias_s[MAX_COUT];   // read back 16 bytes at a time at every item start
-  // DIL > 1: a lane's four outputs are DIL columns apart; they leave through an 8-row x 256-column tile per matrix wave
-  // (written 4 bytes at a time, read back as whole rows) so that the global stores are 16 bytes per lane as at DIL = 1
-  constexpr int OST = 256;
-  __shared__ __attribute__((aligned(16))) float ostage[DIL == 1 ? 4 : 4 * 8 * OST];
+// Input channels per LDS fill: by kernel size and by the rows a workgroup covers (128: four row fragments; 64: two row
+// fragments x two column sub-blocks, i.e. twice the V tile per channel; 32: one row fragment x four sub-blocks, K = 11
+// only -- at K = 7 a chunk of two channels would be an odd number of k-steps) -- the packed weight stream is ordered by it.
+constexpr int wino_ci(int K, int mw = 4) {
+  return mw == 1 ? (K == 11 ? 2 : 0) : K == 3 ? (mw == 4 ? 16 : 8) : (K == 7 || K == 11) ? (mw == 4 ? 8 : 4) : 0;
+}
+constexpr int wino_mw(int Cout) { return Cout % 128 == 0 ? 4 : (Cout % 64 == 0 ? 2 : (Cout % 32 == 0 ? 1 : 0)); }
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+// Shape of one instance: what the kernels below size their LDS regions and work lists by (wino_body derives the same
+// figures for itself and asserts that they agree).
+template <int K, int DIL, int CI, int NF, int MW>
+struct WinoShape {
+  using Gd = GeoD<K, DIL == 1 ? 3 : DIL, NF>;   // (only read when DIL > 1)
+  static constexpr int G = (K + 2) / 3, KR = CI * G;
+  static constexpr int NB = 4 / MW, NTS = 32 * NF, NT = NTS * NB;
+  static constexpr int NCOLS = DIL == 1 ? 4 * NTS : Gd::NCOL, NCOL = NCOLS * NB;
+  static constexpr int RW = (DIL == 1 ? NCOLS + 16 : Gd::RW) + (NB - 1) * NCOLS;
+  static constexpr int RAW_FLOATS = 2 * CI * RW;          // two raw buffers
+  static constexpr int V_FLOATS = 2 * KR * NT * 6;        // two V buffers
+  static constexpr int OST_FLOATS = DIL == 1 ? 4 : 4 * 8 * 256;   // the dilated instances' output stage
+};
+
+// Items of a launch: (utterance, N-block, M-block).  Under a length-aware work list (ov_conv1d_wino_params.col_limit, as
+// ov_conv1d_params.col_limit) utterance b contributes only the N-blocks that start before its column limit; lim_pref[b] =
+// blocks of the utterances before b, so the list stays dense and is dealt evenly whatever the lengths are.  One wave
+// computes the prefix sums once per workgroup; every wave of the workgroup must call this (it holds a barrier).
+template <int NCOL, int MW>
+__device__ __forceinline__ int wino_total(const ov_conv1d_wino_params& p, int* lim_pref) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int L = p.L;
-  const int nchunks = p.Cin / CI;
   const int ntiles = (L + NCOL - 1) / NCOL;
   const int mblocks = p.Cout / (32 * MW);
   int total = ntiles * mblocks * p.B;
-  // Length-aware work list (ov_conv1d_wino_params.col_limit, as ov_conv1d_params.col_limit): utterance b contributes only
-  // the N-blocks that start before its column limit; lim_pref[b] = blocks of the utterances before b, so the list stays
-  // dense and is dealt evenly whatever the lengths are.  One wave computes the prefix sums once per workgroup.
-  __shared__ int lim_pref[ovk::LIMIT_MAX_BATCH + 1];
-  const bool limited = p.col_limit != nullptr;
-  if (limited) {
+  if (p.col_limit != nullptr) {
     if (wave == 0) {
       int carry = 0;
       for (int base = 0; base < p.B; base += 64) {
@@ -219,6 +211,51 @@ __global__ __launch_bounds__(64 * (4 + 2 * NF), NF == 1 ? 3 : 2) void conv1d_win
     __syncthreads();
     total = __builtin_amdgcn_readfirstlane(lim_pref[p.B]) * mblocks;
   }
+  return total;
+}
+
+// One conv's share of a workgroup: items wid0, wid0 + wstride, ... < wend of p's work list (lim_pref: wino_total's table,
+// read under a column limit only).  raw / Vs / bias_s / ostage: the workgroup's LDS regions of WinoShape's sizes (ostage is
+// read and written by the dilated instances only).  Every wave of the workgroup takes wid0 >= wend together (the range is
+// uniform), and all of them execute the same number of barriers: (A), (B) and one per chunk walked -- so a caller may run
+// several bodies one after the other with one workgroup barrier in between (conv1d_wino_multi_kernel).
+template <int K, int DIL, int CI, int NF, int MW, bool DBG>
+__device__ __forceinline__ void wino_body(const ov_conv1d_wino_params& p, const int wid0, const int wend, const int wstride,
+                                          float* raw, float* Vs, float* bias_s, float* ostage, const int* lim_pref) {
+  using Ge = Geo<K>;
+  using Gd = GeoD<K, DIL == 1 ? 3 : DIL, NF>;   // (only read when DIL > 1)
+  constexpr int G = Ge::G, KR = CI * G, NSTEP = KR / 2, NPAIR = NSTEP / 2;
+  constexpr int NB = 4 / MW;           // column sub-blocks per workgroup
+  constexpr int NTS = 32 * NF;         // Winograd tiles per sub-block (what one matrix wave owns)
+  constexpr int NT = NTS * NB;         // Winograd tiles per N-block
+  constexpr int NCOLS = DIL == 1 ? 4 * NTS : Gd::NCOL;   // output columns per sub-block
+  constexpr int NCOL = NCOLS * NB;     // output columns per N-block
+  constexpr int RW = (DIL == 1 ? NCOLS + 16 : Gd::RW) + (NB - 1) * NCOLS;   // floats per raw LDS row: column t0 - ORG + c at index c
+  static_assert(MW == 4 || ((MW == 2 || MW == 1) && NF == 2), "two- and one-row-fragment workgroups run two fragments per wave");
+  constexpr int ORG = DIL == 1 ? 8 : Gd::PADA;
+  constexpr int RW4 = RW / 4;
+  constexpr int NHELP = 2 * NF;        // helper waves
+  static_assert(DIL == 1 || NF == 2, "dilated instances run two fragments per wave");
+  static_assert(KR % 4 == 0 && CI % 2 == 0, "k-rows in whole k-step pairs");
+  constexpr int NPR = CI / 2;            // input-channel pairs per chunk (a pair = one k-step of each group)
+  constexpr int NITEM = NPR * RW4;       // staging items per chunk: (channel pair, 4 columns) = two 16-byte vectors
+  constexpr int RAWBUF = CI * RW;        // floats per raw buffer: raw[pair][raw index][channel of the pair]
+  constexpr int VBUF = KR * NT * 6;      // floats per V buffer: V[k-row = g * CI + channel][tile][6]
+  // DIL > 1: a lane's four outputs are DIL columns apart; they leave through an 8-row x 256-column tile per matrix wave
+  // (written 4 bytes at a time, read back as whole rows) so that the global stores are 16 bytes per lane as at DIL = 1
+  constexpr int OST = 256;
+  using Sh = WinoShape<K, DIL, CI, NF, MW>;
+  static_assert(Sh::RAW_FLOATS == 2 * RAWBUF && Sh::V_FLOATS == 2 * VBUF && Sh::NCOL == NCOL &&
+                    Sh::OST_FLOATS == (DIL == 1 ? 4 : 4 * 8 * OST), "WinoShape restates this geometry");
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int L = p.L;
+  const int nchunks = p.Cin / CI;
+  const int ntiles = (L + NCOL - 1) / NCOL;
+  const int mblocks = p.Cout / (32 * MW);
+  const bool limited = p.col_limit != nullptr;
   auto decode = [&](int w, int& ub, int& utile, int& umblk) {
     const int g = w / mblocks;
     umblk = w - g * mblocks;
@@ -235,15 +272,6 @@ __global__ __launch_bounds__(64 * (4 + 2 * NF), NF == 1 ? 3 : 2) void conv1d_win
     ub = lo;
     utile = g - __builtin_amdgcn_readfirstlane(lim_pref[lo]);
   };
-  // XCD-contiguous order (see conv1d_mfma.h): XCD x = blockIdx.x % 8 owns a contiguous eighth of the list
-  int wid0 = blockIdx.x, wend = total, wstride = gridDim.x;
-  if ((gridDim.x & 7u) == 0) {
-    const int xcd = blockIdx.x & 7;
-    const int lo = (int)(((long long)xcd * total) >> 3);
-    wend = (int)(((long long)(xcd + 1) * total) >> 3);
-    wid0 = lo + (int)(blockIdx.x >> 3);
-    wstride = gridDim.x >> 3;
-  }
   if (wid0 >= wend) return;
   const int nitems = (wend - wid0 + wstride - 1) / wstride;
   const int nstream = nitems * nchunks;      // chunks this workgroup walks, across its items
@@ -757,6 +785,141 @@ __global__ __launch_bounds__(64 * (4 + 2 * NF), NF == 1 ? 3 : 2) void conv1d_win
   }
 }
 
+// XCD-contiguous order (see conv1d_mfma.h): XCD x = blockIdx.x % 8 owns a contiguous eighth [lo, hi) of a list of `total`
+// items, which its gridDim.x / 8 workgroups walk with that stride; grids that are no multiple of 8 deal the whole list.
+__device__ __forceinline__ bool wino_xcd_eighth(int total, int& lo, int& hi) {
+  if ((gridDim.x & 7u) != 0) return false;
+  const int xcd = blockIdx.x & 7;
+  lo = (int)(((long long)xcd * total) >> 3);
+  hi = (int)(((long long)(xcd + 1) * total) >> 3);
+  return true;
+}
+
+template <int K, int DIL, int CI, int NF, int MW, bool DBG>
+__global__ __launch_bounds__(64 * (4 + 2 * NF), NF == 1 ? 3 : 2) void conv1d_wino_kernel(const ov_conv1d_wino_params p) {
+  using Sh = WinoShape<K, DIL, CI, NF, MW>;
+  __shared__ __attribute__((aligned(16))) float raw[Sh::RAW_FLOATS];
+  __shared__ __attribute__((aligned(16))) float Vs[Sh::V_FLOATS];
+  __shared__ __attribute__((aligned(16))) float bias_s[MAX_COUT];   // read back 16 bytes at a time at every item start
+  __shared__ __attribute__((aligned(16))) float ostage[Sh::OST_FLOATS];
+  __shared__ int lim_pref[ovk::LIMIT_MAX_BATCH + 1];
+  const int total = wino_total<Sh::NCOL, MW>(p, lim_pref);
+  int wid0 = blockIdx.x, wend = total, wstride = gridDim.x;
+  int lo, hi;
+  if (wino_xcd_eighth(total, lo, hi)) {
+    wend = hi;
+    wid0 = lo + (int)(blockIdx.x >> 3);
+    wstride = gridDim.x >> 3;
+  }
+  wino_body<K, DIL, CI, NF, MW, DBG>(p, wid0, wend, wstride, raw, Vs, bias_s, ostage, lim_pref);
+}
+
+// Up to three convs of one launch: slot 0 holds the K = 11 conv, slot 1 the K = 7 conv, slot 2 the K = 3 conv (heaviest
+// first); bit s of `present` says that slot s is filled.  The convs agree on B, L, Cin, Cout, dilation and column limit, so
+// they share one work list geometry (an N-block's columns do not depend on K) and one `total`.
+struct wino_multi_args {
+  ov_conv1d_wino_params seg[3];
+  long long cost[3];   // what one item of slot s costs, in any unit (launcher: executed products x Cin + a fixed part)
+  int present;
+  int balance;         // 0: every slot dealt as its single launch deals it
+};
+
+// Cost-balanced split of the slots' lists over the m workgroups of an XCD (each list: n items, workgroup j = 0 .. m - 1).
+// All slots but the last are dealt with stride m as a single launch deals them -- q = n / m items each, one more for r = n % m
+// workgroups: the FIRST r of the first slot, the LAST r of the second -- and the last slot (the cheapest items) is cut
+// into contiguous ranges that level what the others left: workgroup j starts at floor((j W - m S(j)) / (m c_last)), W = the
+// XCD's whole cost, S(j) = cost dealt to workgroups 0 .. j - 1 by the other slots.  Integer arithmetic in closed form: every
+// workgroup computes its own three ranges, and the ranges of a slot tile its list exactly (the same floor ends one range and
+// starts the next; j = m gives n).  Falls back to the even deal where it cannot level (r = 0: nothing to level; a
+// workgroup's share of the other slots already exceeds the mean: short lists).
+struct wino_range { int wid0, wend, wstride; };
+__device__ __forceinline__ void wino_multi_ranges(const wino_multi_args& a, int total, wino_range (&rg)[3]) {
+#pragma unroll
+  for (int s = 0; s < 3; ++s) rg[s] = wino_range{(int)blockIdx.x, total, (int)gridDim.x};
+  int lo, hi;
+  if (!wino_xcd_eighth(total, lo, hi)) return;
+  const int m = gridDim.x >> 3, j = blockIdx.x >> 3, n = hi - lo;
+#pragma unroll
+  for (int s = 0; s < 3; ++s) rg[s] = wino_range{lo + j, hi, m};
+  const int pr = a.present & 7, nseg = __builtin_popcount(pr);
+  const int q = n / m, r = n - q * m;
+  if (!a.balance || nseg < 2 || r == 0) return;
+  // (no indexing by a run-time slot number below: a register array indexed that way would live in scratch memory)
+  const int last = (pr & 4) ? 2 : 1;                         // two or three slots: the last one filled is 2, or 1 (slots 0, 1)
+  const int head = (pr & 1) ? 0 : 1;                         // the first one filled
+  const long long c0 = head == 0 ? a.cost[0] : a.cost[1];
+  const long long c1 = nseg == 3 ? a.cost[1] : 0;            // (three slots: the middle one is slot 1)
+  const long long cl = last == 2 ? a.cost[2] : a.cost[1];
+  const long long W = (long long)n * (c0 + c1 + cl);
+  if (cl <= 0 || W < (long long)m * (q + 1) * (c0 + c1)) return;
+  auto start = [&](int jj) {
+    const int over = jj - (m - r);
+    const long long S = (long long)jj * q * (c0 + c1) + c0 * (jj < r ? jj : r) + c1 * (over > 0 ? over : 0);
+    return (int)(((long long)jj * W - (long long)m * S) / ((long long)m * cl));
+  };
+  const wino_range cut = wino_range{lo + start(j), lo + start(j + 1), 1};
+  if (nseg == 3) {
+    const int pos = j + r < m ? j + r : j + r - m;      // workgroups m - r .. m - 1 come first: they take the extra items
+    rg[1] = wino_range{lo + pos, hi, m};
+  }
+  if (last == 2) rg[2] = cut; else rg[1] = cut;
+}
+
+// The convs of `a` one after the other in ONE persistent launch: a workgroup walks its range of slot 0, then of slot 1, then
+// of slot 2.  The convs are independent tensors, so nothing is synchronised across workgroups; inside a workgroup the LDS
+// of a body is dead once all its waves have passed the body's last chunk barrier (after it the helpers touch no LDS and a
+// matrix wave only its own output stage), so ONE workgroup barrier separates two bodies -- every wave reaches it: a wave
+// leaves wino_body by return (no items; a helper at the end of its stream), never the kernel.  One LDS region sized for the
+// largest body, carved per body; the column-limit table is computed once (the slots share the geometry).
+template <int DIL, int NF, int MW>
+__global__ __launch_bounds__(64 * (4 + 2 * NF), 2) void conv1d_wino_multi_kernel(const wino_multi_args a) {
+  using S11 = WinoShape<11, DIL, wino_ci(11, MW), NF, MW>;
+  using S7 = WinoShape<7, DIL, wino_ci(7, MW), NF, MW>;
+  using S3 = WinoShape<3, DIL, wino_ci(3, MW), NF, MW>;
+  constexpr int F11 = S11::RAW_FLOATS + S11::V_FLOATS + S11::OST_FLOATS, F7 = S7::RAW_FLOATS + S7::V_FLOATS + S7::OST_FLOATS,
+                F3 = S3::RAW_FLOATS + S3::V_FLOATS + S3::OST_FLOATS;
+  constexpr int FMAX = F11 > F7 ? (F11 > F3 ? F11 : F3) : (F7 > F3 ? F7 : F3);
+  static_assert(S11::NCOL == S7::NCOL && S11::NCOL == S3::NCOL, "one work list geometry for all kernel sizes");
+  static_assert(S11::RAW_FLOATS % 4 == 0 && S7::RAW_FLOATS % 4 == 0 && S3::RAW_FLOATS % 4 == 0 && S11::V_FLOATS % 4 == 0 &&
+                    S7::V_FLOATS % 4 == 0 && S3::V_FLOATS % 4 == 0, "16-byte aligned regions");
+  __shared__ __attribute__((aligned(16))) float lds[FMAX];
+  __shared__ __attribute__((aligned(16))) float bias_s[MAX_COUT];
+  __shared__ int lim_pref[ovk::LIMIT_MAX_BATCH + 1];
+  const int first = (a.present & 1) ? 0 : ((a.present & 2) ? 1 : 2);
+  const int total = wino_total<S11::NCOL, MW>(a.seg[first], lim_pref);
+  wino_range rg[3];
+  wino_multi_ranges(a, total, rg);
+  if (a.present & 1)
+    wino_body<11, DIL, wino_ci(11, MW), NF, MW, false>(a.seg[0], rg[0].wid0, rg[0].wend, rg[0].wstride, lds, lds + S11::RAW_FLOATS,
+                                                        bias_s, lds + S11::RAW_FLOATS + S11::V_FLOATS, lim_pref);
+  __syncthreads();
+  if (a.present & 2)
+    wino_body<7, DIL, wino_ci(7, MW), NF, MW, false>(a.seg[1], rg[1].wid0, rg[1].wend, rg[1].wstride, lds, lds + S7::RAW_FLOATS,
+                                                      bias_s, lds + S7::RAW_FLOATS + S7::V_FLOATS, lim_pref);
+  __syncthreads();
+  if (a.present & 4)
+    wino_body<3, DIL, wino_ci(3, MW), NF, MW, false>(a.seg[2], rg[2].wid0, rg[2].wend, rg[2].wstride, lds, lds + S3::RAW_FLOATS,
+                                                      bias_s, lds + S3::RAW_FLOATS + S3::V_FLOATS, lim_pref);
+}
+
+template <int DIL, int NF, int MW>
+int wino_multi_launch(const wino_multi_args* a, int nwg_forced, hipStream_t stream) {
+  constexpr int NCOL = WinoShape<11, DIL, wino_ci(11, MW), NF, MW>::NCOL, NHELP = 2 * NF;
+  const ov_conv1d_wino_params* p = &a->seg[(a->present & 1) ? 0 : ((a->present & 2) ? 1 : 2)];
+  const int ntiles = (p->L + NCOL - 1) / NCOL;
+  const long total = (long)ntiles * (p->Cout / (32 * MW)) * p->B;   // items of EACH slot (an upper bound under a column limit)
+  auto kernel = conv1d_wino_multi_kernel<DIL, NF, MW>;
+  static std::atomic<int> slot_cache[ovk::OV_MAX_DEVICES];
+  const int slots = ovk::resident_workgroups(reinterpret_cast<const void*>(kernel), 64 * (4 + NHELP), slot_cache);
+  long nwg = nwg_forced > 0 ? nwg_forced : slots;
+  if (nwg > total) nwg = total;
+  if (nwg >= 8) nwg = (nwg + 7) / 8 * 8;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)nwg), dim3(64 * (4 + NHELP)), 0, stream, *a);
+  return hipGetLastError() == hipSuccess ? OV_OK : OV_E_LAUNCH;
+}
+// (instances: conv1d_wino_multi.hip)
+int wino_multi_dispatch(const wino_multi_args* a, int nwg, hipStream_t stream);
+
 template <int K, int DIL, int CI, int NF, int MW, bool DBG>
 int wino_launch(const ov_conv1d_wino_params* p, hipStream_t stream) {
   constexpr int NCOL = (DIL == 1 ? 128 * NF : GeoD<K, DIL == 1 ? 3 : DIL, NF>::NCOL) * (4 / MW), NHELP = 2 * NF;
@@ -771,14 +934,6 @@ int wino_launch(const ov_conv1d_wino_params* p, hipStream_t stream) {
   hipLaunchKernelGGL(kernel, dim3((unsigned)nwg), dim3(64 * (4 + NHELP)), 0, stream, *p);
   return hipGetLastError() == hipSuccess ? OV_OK : OV_E_LAUNCH;
 }
-
-// Input channels per LDS fill: by kernel size and by the rows a workgroup covers (128: four row fragments; 64: two row
-// fragments x two column sub-blocks, i.e. twice the V tile per channel; 32: one row fragment x four sub-blocks, K = 11
-// only -- at K = 7 a chunk of two channels would be an odd number of k-steps) -- the packed weight stream is ordered by it.
-constexpr int wino_ci(int K, int mw = 4) {
-  return mw == 1 ? (K == 11 ? 2 : 0) : K == 3 ? (mw == 4 ? 16 : 8) : (K == 7 || K == 11) ? (mw == 4 ? 8 : 4) : 0;
-}
-constexpr int wino_mw(int Cout) { return Cout % 128 == 0 ? 4 : (Cout % 64 == 0 ? 2 : (Cout % 32 == 0 ? 1 : 0)); }
 
 // One translation unit per kernel size (conv1d_wino_k3 / k7 / k11.hip) so that the instances compile in parallel.
 int wino_dispatch_k3(const ov_conv1d_wino_params* p, int nf, hipStream_t stream);

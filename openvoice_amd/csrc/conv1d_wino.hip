@@ -54,9 +54,8 @@ int ov_conv1d_wino_pack_f32(const float* w, int Cout, int Cin, int K, float* dst
   return OV_OK;
 }
 
-int ov_conv1d_wino_f32(const ov_conv1d_wino_params* pin, ov_stream_t stream) {
-  if (!pin) return OV_E_BADARG;
-  ov_conv1d_wino_params q = *pin;
+// The argument checks of one conv; normalises q (default strides, slopes, an ignored column limit) for the launch.
+static int wino_check(ov_conv1d_wino_params& q) {
   if (!q.x || !q.w || !q.bias || !q.out) return OV_E_BADARG;
   if (q.B <= 0 || q.L <= 0 || q.nwg < 0) return OV_E_BADARG;
   if (q.col_limit && (q.col_limit_scale <= 0 || (reinterpret_cast<uintptr_t>(q.col_limit) & 3))) return OV_E_BADARG;
@@ -82,16 +81,58 @@ int ov_conv1d_wino_f32(const ov_conv1d_wino_params* pin, ov_stream_t stream) {
   if (q.B > 1 && (q.x_bstride < (int64_t)q.Cin * q.x_ld || q.out_bstride < (int64_t)q.Cout * q.out_ld ||
                   (q.res && q.res_bstride < (int64_t)q.Cout * q.out_ld) || (q.add && q.add_bstride < (int64_t)q.Cout * q.out_ld)))
     return OV_E_BADARG;
-  hipStream_t st = static_cast<hipStream_t>(stream);
   if (q.frags < 0 || q.frags > 2) return OV_E_BADARG;
+  if (q.dil != 1 && (q.frags ? q.frags : 2) != 2) return OV_E_UNSUPPORTED;       // the dilated instances run two fragments per wave
+  return OV_OK;
+}
+
+int ov_conv1d_wino_f32(const ov_conv1d_wino_params* pin, ov_stream_t stream) {
+  if (!pin) return OV_E_BADARG;
+  ov_conv1d_wino_params q = *pin;
+  if (const int rc = wino_check(q)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
   const int nf = q.frags ? q.frags : 2;
-  if (q.dil != 1 && nf != 2) return OV_E_UNSUPPORTED;       // the dilated instances run two fragments per wave
   switch (q.K) {
     case 3: return wino_dispatch_k3(&q, nf, st);
     case 7: return wino_dispatch_k7(&q, nf, st);
     case 11: return wino_dispatch_k11(&q, nf, st);
   }
   return OV_E_UNSUPPORTED;
+}
+
+int ov_conv1d_wino_multi_f32(const ov_conv1d_wino_params* convs, int n, ov_stream_t stream) {
+  if (!convs || n < 1 || n > 3) return OV_E_BADARG;
+  if (n == 1) return ov_conv1d_wino_f32(convs, stream);
+  wino_multi_args a;
+  std::memset(&a, 0, sizeof(a));
+  for (int i = 0; i < n; ++i) {
+    ov_conv1d_wino_params q = convs[i];
+    if (const int rc = wino_check(q)) return rc;
+    const int slot = q.K == 11 ? 0 : (q.K == 7 ? 1 : 2);
+    a.seg[slot] = q;
+  }
+  // one work list geometry: the convs of a launch differ in their tensors, weights, kernel size and epilogue only.  (Compared on
+  // the CALLER's values: wino_check drops a column limit beyond the table's batch size, for all convs alike.)
+  for (int i = 1; i < n; ++i) {
+    const ov_conv1d_wino_params &u = convs[0], &v = convs[i];
+    if (u.B != v.B || u.L != v.L || u.Cin != v.Cin || u.Cout != v.Cout || u.dil != v.dil || u.col_limit != v.col_limit ||
+        (u.col_limit && u.col_limit_scale != v.col_limit_scale))
+      return OV_E_BADARG;
+  }
+  for (int i = 0; i < n; ++i) {
+    const ov_conv1d_wino_params& v = convs[i];
+    const int bit = 1 << (v.K == 11 ? 0 : (v.K == 7 ? 1 : 2));
+    if (a.present & bit) return OV_E_UNSUPPORTED;          // one conv per kernel size
+    a.present |= bit;
+    if (v.dbg || v.frags == 1 || wino_mw(v.Cout) < 2) return OV_E_UNSUPPORTED;
+  }
+  // An item's cost: its executed products (per tile, times the input channels) and the part that does not depend on them --
+  // epilogue and item set-up -- worth about 380 product-channels at every row count (per-launch times of the three kernel
+  // sizes at C = 256 / 128 / 64, profiles/r08_multi_launch.txt).
+  const int kk[3] = {11, 7, 3};
+  for (int s = 0; s < 3; ++s) a.cost[s] = (long long)wino_products(kk[s]) * convs[0].Cin + 380;
+  a.balance = 1;
+  return wino_multi_dispatch(&a, convs[0].nwg, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -386,6 +386,36 @@ void conv1d_wino_f32(const OptTensor& x, const OptTensor& w, const OptTensor& bi
   finish(ov_conv1d_wino_f32(&p, c.stream()), "ov_conv1d_wino_f32");
 }
 
+// n = 1 .. 3 convs of one launch (ov_conv1d_wino_multi_f32): six tensors per conv in the order of conv1d_wino_f32 (x, w, bias,
+// out, res, add; the slots beyond n are None), one col_limit for all; ip = n x the 15 integers of conv1d_wino_f32, fp = n x
+// its 3 floats
+void conv1d_wino_multi_f32(const OptTensor& x0, const OptTensor& w0, const OptTensor& b0, const OptTensor& o0, const OptTensor& r0,
+                           const OptTensor& a0, const OptTensor& x1, const OptTensor& w1, const OptTensor& b1, const OptTensor& o1,
+                           const OptTensor& r1, const OptTensor& a1, const OptTensor& x2, const OptTensor& w2, const OptTensor& b2,
+                           const OptTensor& o2, const OptTensor& r2, const OptTensor& a2, const OptTensor& col_limit, int64_t n,
+                           at::IntArrayRef ip, at::ArrayRef<double> fp) {
+  TORCH_CHECK(n >= 1 && n <= 3 && (int64_t)ip.size() == 15 * n && (int64_t)fp.size() == 3 * n,
+              "openvoice_amd::conv1d_wino_multi_f32: 1 .. 3 convs, 15 integer and 3 float parameters each");
+  Ctx c{"conv1d_wino_multi_f32", false};
+  const OptTensor* t[3][6] = {{&x0, &w0, &b0, &o0, &r0, &a0}, {&x1, &w1, &b1, &o1, &r1, &a1}, {&x2, &w2, &b2, &o2, &r2, &a2}};
+  ov_conv1d_wino_params ps[3] = {};
+  const int32_t* lim = sptr<int32_t>(col_limit, c, 18);
+  for (int64_t i = 0; i < n; ++i) {
+    ov_conv1d_wino_params& p = ps[i];
+    const int64_t* q = ip.data() + 15 * i;
+    const int k = 6 * (int)i;
+    p.x = sptr<float>(*t[i][0], c, k); p.w = sptr<float>(*t[i][1], c, k + 1); p.bias = sptr<float>(*t[i][2], c, k + 2);
+    p.out = sptr<float>(*t[i][3], c, k + 3); p.res = sptr<float>(*t[i][4], c, k + 4); p.add = sptr<float>(*t[i][5], c, k + 5);
+    p.col_limit = lim; p.col_limit_scale = (int32_t)q[14];
+    p.B = (int32_t)q[0]; p.Cin = (int32_t)q[1]; p.Cout = (int32_t)q[2]; p.L = (int32_t)q[3];
+    p.x_ld = (int32_t)q[4]; p.out_ld = (int32_t)q[5]; p.K = (int32_t)q[6]; p.dil = (int32_t)q[7]; p.nwg = (int32_t)q[8];
+    p.x_bstride = q[9]; p.out_bstride = q[10]; p.res_bstride = q[11]; p.add_bstride = q[12]; p.frags = (int32_t)q[13];
+    p.in_slope = (float)fp[3 * i]; p.scale = (float)fp[3 * i + 1]; p.out_slope = (float)fp[3 * i + 2];
+  }
+  DeviceScope scope(c);
+  finish(ov_conv1d_wino_multi_f32(ps, (int)n, c.stream()), "ov_conv1d_wino_multi_f32");
+}
+
 }  // namespace
 
 TORCH_LIBRARY(openvoice_amd, m) {
@@ -409,6 +439,10 @@ TORCH_LIBRARY(openvoice_amd, m) {
   m.def("conv1d_wino_f32(Tensor? x, Tensor? w, Tensor? bias, Tensor(a!)? out, Tensor? res, Tensor? add, Tensor(b!)? dbg, "
         "Tensor? col_limit, int[] ip, float[] fp) -> ()",
         &conv1d_wino_f32);
+  m.def("conv1d_wino_multi_f32(Tensor? x0, Tensor? w0, Tensor? b0, Tensor(a!)? o0, Tensor? r0, Tensor? a0, Tensor? x1, Tensor? w1, "
+        "Tensor? b1, Tensor(b!)? o1, Tensor? r1, Tensor? a1, Tensor? x2, Tensor? w2, Tensor? b2, Tensor(c!)? o2, Tensor? r2, "
+        "Tensor? a2, Tensor? col_limit, int n, int[] ip, float[] fp) -> ()",
+        &conv1d_wino_multi_f32);
   // ---- device entry points with flat argument lists (schema derived from the C prototype)
   bind_device<&ov_frame_hops_f32>(m, "frame_hops_f32");
   bind_device<&ov_frame_hops_windows_f32>(m, "frame_hops_windows_f32");

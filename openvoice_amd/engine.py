@@ -277,6 +277,9 @@ def wino_policy(C, K, dil):
 # 1.1-1.65x faster).  Batch 1 with the rule: 7.50 -> 6.18 ms.
 WINO_MIN_ITEMS = 136
 
+# Default of ConverterEngine.use_multi_launch (DESIGN.md section 8 has the measurement behind it)
+USE_MULTI_LAUNCH = True
+
 # Opt-in split-precision path (use_split_bf16x3): generator stages with at least this many channels run on ov_conv1d_split3
 SPLIT_MIN_CHANNELS = 128
 
@@ -479,6 +482,12 @@ class _WaveNet:
             self.cond_b_fused = bc[full].contiguous().to(device)
 
 
+def multi_launch_scratch_buffers(cfg):
+    """Decoder scratch buffers a multi-launch MRF needs beyond the workspace's t1 / ra: every ResBlock keeps a t1 and an ra of
+    its own while the three run side by side (generator.scratch_per_frame sizes each)."""
+    return 2 * (len(cfg["resblock_kernel_sizes"]) - 1)
+
+
 _DEC_BUFFERS = 5         # decoder scratch buffers of a workspace: the stage input, the ConvTranspose output, t1 / ra, the MRF sum
 
 
@@ -605,6 +614,11 @@ class ConverterEngine:
         # ResBlock convs in the Winograd domain where wino_policy() says so (ov_conv1d_wino_f32):
         # fp32 arithmetic, 6 G / (4 K) of the direct form's multiplies, ~4x its rounding error
         self.use_winograd = True
+        # The three ResBlocks' convs of one MRF step (k = 3 / 7 / 11, independent of each other) as ONE persistent launch
+        # (ov_conv1d_wino_multi_f32) on the stages whose convs are all Winograd launches; bit-identical to the single
+        # launches (False: one launch per conv, ResBlock by ResBlock)
+        self.use_multi_launch = USE_MULTI_LAUNCH
+        self._cus = None         # compute units of the device (read on first use)
         # opt-in fast generator: bf16 activations, fp32 accumulation (waveform within
         # ~1e-2 of the fp32 path instead of ~1e-5).  Built on first use by bf16_generator().
         self._state_dict_for_bf16 = sd
@@ -647,6 +661,14 @@ class ConverterEngine:
         self._timed("mrf", alg, lambda: wino.launch_conv_wino(layer, x, bs, out, bs, B, L, **kw),
                     alg * wino.PRODUCTS_PER_TILE[layer.K] / (4.0 * layer.K))
 
+    def _wino_multi(self, convs, B, L, **lim):
+        """One ov_conv1d_wino_multi_f32 launch (``wino.launch_convs_wino``); profiled as ONE record under the MRF tag with
+        the algorithmic and the executed FLOPs of all its convs."""
+        from . import wino
+        alg = [2.0 * c["layer"].cout * c["layer"].cin * c["layer"].K * L * B for c in convs]
+        exe = sum(a * wino.PRODUCTS_PER_TILE[c["layer"].K] / (4.0 * c["layer"].K) for a, c in zip(alg, convs))
+        self._timed("mrf", sum(alg), lambda: wino.launch_convs_wino(convs, B, L, **lim), exe)
+
     def _pair(self, c1, c2, x, out, bs, B, L, add, scale, **lim):
         """One fused ResBlock1 iteration; profiled under the same tag as the two launches it replaces, with their
         algorithmic FLOPs (both convs)."""
@@ -687,14 +709,17 @@ class ConverterEngine:
             ws["pre"] = f(B, self.stages[0].cin, Tp)
             dec = _workspace_elems(self.cfg, B, T)[1]
             ws["dec"] = [torch.empty(dec, dtype=torch.float32, device=dev) for _ in range(_DEC_BUFFERS)]
+            # a multi launch keeps every ResBlock's t1 / ra live at once: part of the workspace, not of a step
+            self._chain_scratch(ws, self._multi_launch_scratch(B, T))
             self._ws[key] = ws
         return ws
 
     def workspace_bytes(self, B, T):
-        """Device bytes of the ``_workspace(B, T)`` allocation (the frame-rate tensors and the decoder scratch; the
-        opt-in paths' lazily added buffers not included)."""
+        """Device bytes of the ``_workspace(B, T)`` allocation (the frame-rate tensors and the decoder scratch, the multi
+        launches' ``multi_launch_scratch_buffers`` included while ``use_multi_launch`` is on; the opt-in paths' lazily added
+        buffers not included)."""
         frame_rate, dec = _workspace_elems(self.cfg, B, T)
-        return 4 * (frame_rate + _DEC_BUFFERS * dec)
+        return 4 * (frame_rate + (_DEC_BUFFERS + self._multi_launch_scratch(B, T)) * dec)
 
     def _zeros_like_cached(self, t):
         """An all-zero tensor of ``t``'s shape (the ``zero_g`` conditioning, models.py:495,498) without a fill launch
@@ -711,7 +736,8 @@ class ConverterEngine:
         return self._streams[:n]
 
     def _chain_scratch(self, ws, n):
-        """``n`` more decoder scratch buffers (the concurrent chains' own t1 / ra), allocated on first use."""
+        """``n`` more decoder scratch buffers (the t1 / ra of the ResBlocks beyond the first: concurrent chains and multi
+        launches keep them live at once), allocated on first use."""
         extra = ws.setdefault("dec_extra", [])
         while len(extra) < n:
             extra.append(torch.empty_like(ws["dec"][0]))
@@ -1056,6 +1082,8 @@ class ConverterEngine:
                                    add=add, add_bs=bs, scale=scale, tag="mrf", **lim(rate))
                 cur = dst
 
+        if not concurrent and self._mrf_multi(i, u, t1, ra, acc, ws, B, ch, L, lim(rate)):
+            return
         if not concurrent:
             for j, pairs in enumerate(self.resblocks[i]):
                 chain(j, pairs)
@@ -1073,6 +1101,63 @@ class ConverterEngine:
                     done[j].record(side[j])
             for j in range(nk):                     # every chain's scratch is free again before the next stage
                 main.wait_event(done[j])
+
+    def _multi_launch_stage(self, i, B, ch, L):
+        """Whether the MRF of stage ``i`` runs as multi launches in a (B, ch, L) conversion: the switches, three (or two)
+        ResBlocks of different kernel sizes and equal dilations, every conv a Winograd launch (``resblock_families``: an
+        instance, wino_policy, WINO_MIN_ITEMS) of the 64- or 128-row families -- and more items per conv than the device has
+        CUs.  Up to one item per workgroup there is no tail to level and the three launches already run one item each; with
+        every ResBlock on scratch of its own the stage then only loses the cache hits that shared t1 / ra buffers give a
+        small conversion (batch 1 x 10 s: 6.02 ms against 5.95), so those stay launch by launch."""
+        blocks = self.resblocks[i]
+        nk = len(blocks)
+        ks = [pairs[0][0].K for pairs in blocks]
+        dils = [[c1.dil for c1, _ in pairs] for pairs in blocks]
+        if not (self.use_multi_launch and self.use_winograd and 2 <= nk <= 3 and len(set(ks)) == nk and set(ks) <= {3, 7, 11}
+                and ch % 64 == 0 and all(d == dils[0] for d in dils)):
+            return False
+        if self._cus is None:
+            self._cus = torch.cuda.get_device_properties(self.device).multi_processor_count
+        if wino_items(ch, 1, B, L) <= self._cus:
+            return False
+        fams = [resblock_families(ch, k, d, B, L, self.use_winograd, self.fuse_pairs) for k, d in zip(ks, dils)]
+        return all(f == ("wino", "wino") for fam in fams for f in fam)
+
+    def _multi_launch_scratch(self, B, T):
+        """``multi_launch_scratch_buffers`` when some stage of a (B, T) conversion runs multi launches, else 0."""
+        return (multi_launch_scratch_buffers(self.cfg)
+                if any(self._multi_launch_stage(st.index, B, st.ch, T * st.rate_out) for st in self.stages) else 0)
+
+    def _mrf_multi(self, i, u, t1, ra, acc, ws, B, ch, L, lim):
+        """The MRF of stage ``i`` walked PAIR BY PAIR with the three ResBlocks' convs of a step in one launch
+        (ov_conv1d_wino_multi_f32): c1 of every ResBlock, then c2 of every ResBlock.  The c2 of the LAST pair adds the
+        running MRF sum of the ResBlock before it, so those stay single launches in ResBlock order: the same operations on
+        the same operands as ``_mrf``'s chains, bit for bit.  Returns False -- nothing launched -- where the stage is not made
+        of Winograd launches of one shape (``_mrf`` then runs it launch by launch)."""
+        cfg = self.cfg
+        blocks, wn = self.resblocks[i], self.wino_resblocks[i]
+        nk = len(blocks)
+        dils = [[c1.dil for c1, _ in pairs] for pairs in blocks]
+        if not self._multi_launch_stage(i, B, ch, L):
+            return False
+        need = multi_launch_scratch_buffers(cfg)
+        if torch.cuda.is_current_stream_capturing() and len(ws.get("dec_extra", [])) < need:
+            return False           # the scratch is never allocated from a capturing graph's private pool
+        extra = self._chain_scratch(ws, need)
+        ts, ras = [t1] + extra[0:need:2], [ra] + extra[1:need:2]
+        bs, npairs = ch * L, len(dils[0])
+        cur = [u] * nk
+        for n in range(npairs):
+            self._wino_multi([dict(layer=wn[j][n][0], x=cur[j], out=ts[j], bs=bs, in_slope=LRELU_SLOPE, out_slope=LRELU_SLOPE)
+                              for j in range(nk)], B, L, **lim)
+            if n < npairs - 1:
+                self._wino_multi([dict(layer=wn[j][n][1], x=ts[j], out=ras[j], bs=bs, res=cur[j]) for j in range(nk)], B, L, **lim)
+                cur = list(ras)
+            else:
+                for j in range(nk):
+                    self._wino(wn[j][n][1], ts[j], acc, bs, B, L, res=cur[j], add=acc if j > 0 else None,
+                               scale=1.0 / nk if j == nk - 1 else 1.0, in_slope=1.0, **lim)
+        return True
 
     def _stage(self, st, x, x_ld, x_bs, bufs, out, ws, B, L, cond_d=None, limits=None, keep=None):
         """Generator stage ``st`` (models.py:274-291) on the fp32 kernels: [conv_pre + cond into ``ws["pre"]`` (stage 0)],

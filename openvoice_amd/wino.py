@@ -73,3 +73,35 @@ def launch_conv_wino(layer, x, x_bs, out, out_bs, B, L, in_slope=1.0, scale=1.0,
     p.col_limit, p.col_limit_scale = vp(col_limit), col_limit_scale
     stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
     _lib.check(_lib.load().ov_conv1d_wino_f32(ctypes.byref(p), stream), "ov_conv1d_wino_f32")
+
+
+def launch_convs_wino(convs, B, L, nwg=0, col_limit=None, col_limit_scale=1):
+    """``ov_conv1d_wino_multi_f32``: one to three INDEPENDENT convs of one shape -- the three ResBlocks of an MRF step, kernel
+    sizes 3 / 7 / 11 -- as ONE persistent launch on torch's current stream; bit-identical to a ``launch_conv_wino`` each.
+    ``convs``: dicts with ``layer`` (PackedConvWino), ``x``, ``out``, ``bs`` (batch stride of every tensor of the conv) and
+    optionally ``res``, ``add``, ``scale``, ``in_slope``, ``out_slope`` as ``launch_conv_wino`` takes them; the layers agree on
+    channels and dilation."""
+    n = len(convs)
+    get = lambda c, k, d=None: c.get(k, d)
+    ints = lambda c: [B, c["layer"].cin, c["layer"].cout, L, 0, 0, c["layer"].K, c["layer"].dil, nwg, c["bs"], c["bs"],
+                      c["bs"] if get(c, "res") is not None else 0, c["bs"] if get(c, "add") is not None else 0, 0, col_limit_scale]
+    floats = lambda c: [get(c, "in_slope", 1.0), get(c, "scale", 1.0), get(c, "out_slope", 1.0)]
+    if _lib.use_torch_binding():
+        tensors = []
+        for i in range(3):
+            c = convs[i] if i < n else None
+            tensors += [None] * 6 if c is None else [c["x"], c["layer"].w, c["layer"].bias, c["out"], get(c, "res"), get(c, "add")]
+        _lib.torch_op("conv1d_wino_multi_f32", *tensors, col_limit, n, [v for c in convs for v in ints(c)],
+                      [v for c in convs for v in floats(c)])
+        return
+    ps = (_lib.ConvWinoParams * n)()
+    vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+    for p, c in zip(ps, convs):
+        layer = c["layer"]
+        p.x, p.w, p.bias, p.out, p.res, p.add = vp(c["x"]), vp(layer.w), vp(layer.bias), vp(c["out"]), vp(get(c, "res")), vp(get(c, "add"))
+        (p.B, p.Cin, p.Cout, p.L, p.x_ld, p.out_ld, p.K, p.dil, p.nwg, p.x_bstride, p.out_bstride, p.res_bstride, p.add_bstride,
+         p.frags, p.col_limit_scale) = ints(c)
+        p.in_slope, p.scale, p.out_slope = floats(c)
+        p.col_limit = vp(col_limit)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(convs[0]["x"].device).cuda_stream)
+    _lib.check(_lib.load().ov_conv1d_wino_multi_f32(ps, n, stream), "ov_conv1d_wino_multi_f32")
