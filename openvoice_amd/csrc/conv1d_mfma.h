@@ -61,7 +61,7 @@ __host__ __device__ inline int packed_units(int cin) { return ((cin + UNIT - 1) 
 
 __device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
 
-// ---- epilogue: accumulators (= bias + conv [+ res + add], see conv_preload) -> global ------------------
+// ---- epilogue: accumulators (= bias + conv [+ res], see conv_preload) [+ add] -> global ----------------
 // C/D fragment: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5).
 // Addressing: 64-bit per-utterance base pointers stay scalar; a lane carries ONE 32-bit offset
 // (its column + its half's row offset) and the 16 per-register row offsets are scalar multiples of
@@ -165,11 +165,12 @@ __device__ __forceinline__ void conv_epilogue(const ov_conv1d_params& p, f32x16 
     return;
   } else {
     if constexpr (EPI == OV_EPI_LINEAR) {
-      // Nothing to read back (every conv1 of the MRF, and every conv2: its residual is already in the accumulators):
-      // stores only, back to back.  Kept apart from the general path on purpose -- there the optional operand loads
-      // sit between the fragments' stores and the wait for a load (vmcnt counts in order) is a wait for every store
-      // issued before it: one exposed write round trip per fragment (1 500 cycles per tile, phase timers r02 s13).
-      if (!mrow && !(p.res && !preloaded) && !(p.add && !preloaded)) {
+      // Nothing to read back (every conv1 of the MRF, and every conv2 without a running sum: its residual is already
+      // in the accumulators): stores only, back to back.  Kept apart from the general path on purpose -- there the
+      // optional operand loads sit between the fragments' stores and the wait for a load (vmcnt counts in order) is a
+      // wait for every store issued before it: one exposed write round trip per fragment (1 500 cycles per tile, phase
+      // timers r02 s13).
+      if (!mrow && !(p.res && !preloaded) && !p.add) {
 #pragma unroll
         for (int i = 0; i < WM; ++i) {
           const uint32_t mt = (uint32_t)(mtile0 + i);
@@ -212,9 +213,9 @@ __device__ __forceinline__ void conv_epilogue(const ov_conv1d_params& p, f32x16 
         } else {
           const uint32_t voff = rbase * LD + col;   // the lane's only per-element offset
           if constexpr (EPI == OV_EPI_LINEAR) {
-            // `preloaded`: res and add already sit in the accumulators (conv_preload)
+            // `preloaded`: res already sits in the accumulators (conv_preload); add never does (see there)
             const float* resb = (p.res && !preloaded) ? p.res + (int64_t)b * p.res_bstride : nullptr;
-            const float* addb = (p.add && !preloaded) ? p.add + (int64_t)b * p.add_bstride : nullptr;
+            const float* addb = p.add ? p.add + (int64_t)b * p.add_bstride : nullptr;
             const float mkv = (p.flags & OV_F_MASK_V) ? mk : 1.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) v[r] *= mkv;
@@ -253,7 +254,7 @@ __device__ __forceinline__ void conv_epilogue(const ov_conv1d_params& p, f32x16 
 // ---- accumulator initialisation -------------------------------------------------------------------
 // The accumulators START at everything the epilogue would otherwise have to read back from memory and add:
 //   every kind      bias[row] (+ bias_b[b][row])
-//   LINEAR          + res (+ add)                 the ResBlock residual and the MRF running sum
+//   LINEAR          + res                         the ResBlock residual
 //   RESSKIP         + h (residual rows) / + skip (skip rows, unless OV_F_OUT2_INIT)
 //   COUPLE          + x1 (forward) / - x1 (reverse; the epilogue negates); x1 = res when given, else out (in place)
 // so that the epilogue only scales / masks and stores.  All of these loads -- 16 x WM x WN per lane -- are issued
@@ -263,6 +264,10 @@ __device__ __forceinline__ void conv_epilogue(const ov_conv1d_params& p, f32x16 
 // fragment at a time behind per-fragment branches: 4-8 serialised HBM round trips per tile, which is what made
 // every conv2 (residual) launch of the MRF 0.2 ms slower than its conv1 twin whatever the tap count.
 // fp32 addition order changes (operands first instead of last): ~1 ulp.
+// LINEAR's second addend, the MRF running sum `add`, is NOT preloaded: it is the sum of up to two whole ResBlock
+// outputs, and every one of the Cin * K chained fmas would round at ITS magnitude instead of the conv's -- at
+// Cin * K = 2816 that alone left the element-wise bound of tests/test_gpu_mrf_kernels.py (1.09 of the limit).  The
+// epilogue adds it, (res + bias + conv) + add: the order of the fused pair (conv1d_pair.h), which stays bit-identical.
 // Returns true when the epilogue's operands are now in `acc` (uniform across the workgroup).
 template <int EPI, int WM, int WN>
 __device__ __forceinline__ bool conv_preload(const ov_conv1d_params& p, f32x16 (&acc)[WM][WN], int b, int tcol0,
@@ -350,28 +355,6 @@ __device__ __forceinline__ bool conv_preload(const ov_conv1d_params& p, f32x16 (
         }
 #pragma unroll
         for (int j = 0; j < WN; ++j) acc[i][j] += bv;
-      }
-    }
-  }
-  if constexpr (EPI == OV_EPI_LINEAR) {
-    // second addend (the MRF running sum; 8 of the 72 MRF launches): one fragment's 16 loads at a time, so that
-    // the temporaries stay at 16 registers
-    if (preloaded && p.add) {
-      const uint32_t nfrag = (uint32_t)p.Cout / 32u;
-      const float* addb = p.add + (int64_t)b * p.add_bstride;
-#pragma unroll
-      for (int i = 0; i < WM; ++i) {
-        const uint32_t mt = min((uint32_t)(mtile0 + i), nfrag - 1u);
-#pragma unroll
-        for (int j = 0; j < WN; ++j) {
-          const uint32_t col = min(col0 + 32u * j, L - 1u);
-          const uint32_t voff = (mt * 32u + 4u * half) * LD + col;
-          f32x16 av;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) av[r] = (addb + (size_t)((r & 3) + 8 * (r >> 2)) * LD)[voff];
-          __builtin_amdgcn_sched_barrier(0);   // all 16 loads issued before the first add (hipcc otherwise pairs them off)
-          acc[i][j] += av;
-        }
       }
     }
   }

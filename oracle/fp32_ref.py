@@ -59,6 +59,41 @@ The case one expects to need an allowance of its own -- 1 - a with a = e^-2|t| -
 1 - a of about 3e-4 -- needs none: it is an absolute error of one rounding of a (2^-25) times r <= 1/2, a quarter of
 2^-24 in the table above, far inside G * 2^-24.  For s << 0 the formula's e^-s = inf gives (1 - a) * rcp(inf) = 0 against
 a true value below 2^-126: exact to the table's three decimals.
+
+The MRF kernels (sample rate) -- S32_MRF and S_W, measured the same way
+-----------------------------------------------------------------------
+The direct OV_EPI_LINEAR ResBlock instances (conv1d_inst_a .. f.hip) and the fused pair keep the criterion above with an
+allowance measured on their own operands (``mrf_operands``: C in {32, 64, 128, 256}, every (k, dilation) of 3 / 7 / 11 x
+1 / 3 / 5, seeds 0 .. 4, every length of ``MRF_LS``, B = 3, benign and stress data).  The Winograd-domain kernels sum in the
+transform domain -- per 4-column tile and tap group g they form At [U_g (.) (Bt d_g)], U_g = fp32(G w_g), d_g the six-sample
+window of lrelu(x) -- so their error is proportional to
+    absacc_w = sum over ci, g of |At| (|U_g| (.) (|Bt| |d_g|)) + |bias| + |res| + |add|,  times |scale|
+(a dilated conv = ``dil`` interleaved undilated ones; per column the maximum over the four tile alignments), and their limit
+is S_W * absacc_w.  S_W is measured on an fp32 restatement of the algorithm (``wino_conv``) against the float64 conv.
+``python -m oracle.fp32_ref`` prints, per (C, k, d): max |conv_fp32 - conv_fp64| / absacc of PyTorch's CPU conv, max
+|wino_fp32 - conv_fp64| / absacc_w of the restatement, and the median of absacc_w / absacc on the stress data:
+
+    C=32  k=3  d=1  7.06e-07 2.50e-07 11.53   C=32  k=3  d=3  5.19e-07 2.44e-07 11.26   C=32  k=3  d=5  5.78e-07 2.21e-07 11.30
+    C=32  k=7  d=1  6.44e-07 1.51e-07 11.06   C=32  k=7  d=3  5.71e-07 1.53e-07 11.25   C=32  k=7  d=5  6.26e-07 1.30e-07 10.95
+    C=32  k=11 d=1  6.22e-07 1.39e-07 10.45   C=32  k=11 d=3  5.68e-07 1.64e-07 10.11   C=32  k=11 d=5  5.61e-07 1.34e-07 10.14
+    C=64  k=3  d=1  4.51e-07 2.14e-07 11.47   C=64  k=3  d=3  4.38e-07 2.29e-07 11.12   C=64  k=3  d=5  4.89e-07 2.47e-07 11.01
+    C=64  k=7  d=1  4.21e-07 1.23e-07 11.29   C=64  k=7  d=3  4.48e-07 1.58e-07 11.29   C=64  k=7  d=5  4.20e-07 1.60e-07 11.18
+    C=64  k=11 d=1  4.11e-07 1.05e-07 10.45   C=64  k=11 d=3  4.33e-07 1.33e-07 10.37   C=64  k=11 d=5  3.98e-07 1.58e-07 10.24
+    C=128 k=3  d=1  3.16e-07 2.48e-07 11.10   C=128 k=3  d=3  3.00e-07 3.03e-07 11.18   C=128 k=3  d=5  6.60e-07 2.50e-07 11.08
+    C=128 k=7  d=1  3.16e-07 1.26e-07 11.41   C=128 k=7  d=3  3.69e-07 1.38e-07 11.33   C=128 k=7  d=5  2.78e-07 1.52e-07 11.23
+    C=128 k=11 d=1  2.83e-07 1.04e-07 10.50   C=128 k=11 d=3  2.50e-07 1.58e-07 10.44   C=128 k=11 d=5  2.51e-07 1.52e-07 10.39
+    C=256 k=3  d=1  2.70e-07 2.36e-07 11.17   C=256 k=3  d=3  2.66e-07 2.93e-07 11.26   C=256 k=3  d=5  5.20e-07 2.77e-07 11.19
+    C=256 k=7  d=1  1.86e-07 1.31e-07 11.41   C=256 k=7  d=3  2.13e-07 1.35e-07 11.37   C=256 k=7  d=5  2.53e-07 1.56e-07 11.32
+    C=256 k=11 d=1  1.81e-07 9.75e-08 10.51   C=256 k=11 d=3  1.98e-07 2.23e-07 10.47   C=256 k=11 d=5  1.90e-07 2.05e-07 10.46
+    direct largest 7.056e-07 (above the frame-rate table's 6.531e-07, so the MRF tests get an allowance of their own)
+    Winograd largest 3.030e-07;  median absacc_w / absacc over all stress shapes 11.02
+
+    S32_MRF = 4 * 7.056e-07 = 2.822e-06          S_W = 4 * 3.030e-07 = 1.212e-06
+
+absacc_w is about 11 times absacc: that factor is how much looser Winograd legitimately is (its transforms multiply the
+operands by coefficients up to 8 and cancel them again), beside a transient as elsewhere; S_W itself is below S32_MRF.
+The fused pair stores h in fp32: its limit carries S32_MRF absacc_1 + 2^-24 |h| through |w2| (``pair``).  A row whose
+weights and bias are all zero has the explicit limit of ``_zero_row_lim``.
 """
 import collections
 import math
@@ -69,6 +104,11 @@ import torch.nn.functional as F
 
 S32 = 4 * 6.531e-07     # 4 x the largest measured value (docstring); never widened to make a kernel pass
 G = 4 * 3.377           # 4 x the largest measured value (docstring), in units of 2^-24
+# the sample-rate ResBlock (MRF) kernels (docstring, "The MRF kernels"): 4 x the largest measured values, never widened to
+# make a kernel pass; only tests/test_mrf_criterion_cpu.py and tests/test_gpu_mrf_kernels.py use them
+S32_MRF = 4 * 7.056e-07         # direct kernels and the fused pair: per absacc; set by C = 32, k = 3, dilation 1
+S_W = 4 * 3.030e-07             # Winograd-domain kernels: per absacc_w; set by C = 128, k = 3, dilation 3
+S32_MRF_SET_BY, S_W_SET_BY = (32, 3, 1), (128, 3, 3)
 EPS = 2.0 ** -24
 
 F64, F32 = torch.float64, torch.float32
@@ -438,8 +478,241 @@ def measure_g():
     return table
 
 
+# =====================================================================================================================
+# The sample-rate ResBlock (MRF) kernels: the direct OV_EPI_LINEAR instances of conv1d_inst_a .. f.hip, the fused pair
+# (ov_resblock_pair_f32), the Winograd-domain conv (ov_conv1d_wino_f32) and its multi launch.  The docstring quotes
+# the measurements; tests/test_mrf_criterion_cpu.py and tests/test_gpu_mrf_kernels.py use these mirrors and generators.
+# =====================================================================================================================
+MRF_CS = (32, 64, 128, 256)
+MRF_KD = tuple((k, d) for k in (3, 7, 11) for d in (1, 3, 5))
+# every length the GPU file runs: {4, N - 4, N, N + 4, 2 N + 4} of the direct tiles N = 128 / 256 / 512, the pair's list
+# and the Winograd kernels' list (multiples of 4: the pair and the Winograd kernels take nothing else)
+PAIR_LS = (4, 124, 128, 132, 256, 260, 516)
+WINO_LS = (4, 252, 256, 260, 516)
+MRF_LS = (4, 124, 128, 132, 252, 256, 260, 508, 512, 516, 1028)
+# F(4, 3), points 0, 1, -1, 2, -2, infinity: the matrices of openvoice_amd/wino.py (restated so that the oracle loads
+# without the native library; tests/test_mrf_criterion_cpu.py holds the two copies equal)
+WINO_BT = ((4, 0, -5, 0, 1, 0), (0, -4, -4, 1, 1, 0), (0, 4, -4, -1, 1, 0), (0, -2, -1, 2, 1, 0), (0, 2, -1, -2, 1, 0),
+           (0, 4, 0, -5, 0, 1))
+WINO_G = ((1 / 4, 0, 0), (-1 / 6, -1 / 6, -1 / 6), (-1 / 6, 1 / 6, -1 / 6), (1 / 24, 1 / 12, 1 / 6), (1 / 24, -1 / 12, 1 / 6),
+          (0, 0, 1))
+WINO_AT = ((1, 1, 1, 1, 1, 0), (0, 1, -1, 2, -2, 0), (0, 1, 1, 4, 4, 0), (0, 1, -1, 8, -8, 1))
+WINO_LEAD_TAPS = {3: 0, 7: 1, 11: 0}
+
+
+def mrf_operands(C, K, dil, L, seed=0, stress=False):
+    """One ResBlock conv (and the pair's second, dilation-1 conv): x [B = 3, C, L], w [C, C, K] at scale (C K)^-1/2, bias,
+    res, add, w2, b2.  ``dil`` does not change the operands (it belongs to the conv); it separates the seeds.
+    ``stress``: input channel c by c % 8 (x, and res / add rows alike so that a quiet row stays quiet end to end):
+    0 x 1e3; 1 x 1e-3; 2 exactly zero; 3 all negative (only the leaky branch runs); 4 a 1e-3 row with one loud transient
+    (+1e3 at column L // 2, -1e3 at column L - 1); 5 .. 7 as trained.  Output row o by o % 4: weights (of w and w2) x 1,
+    x 1e-2, x 1e2 and exactly zero with a zero bias -- such a row must come back as exactly res + add (``_zero_row_lim``)."""
+    s = 100 * seed + 7000 + 10 * K + dil
+    sc = (C * K) ** -0.5
+    o = dict(x=rand(B, C, L, seed=s + 1), w=rand(C, C, K, seed=s + 2, scale=sc), bias=rand(C, seed=s + 3, scale=0.1),
+             res=rand(B, C, L, seed=s + 4), add=rand(B, C, L, seed=s + 5), w2=rand(C, C, K, seed=s + 6, scale=sc),
+             b2=rand(C, seed=s + 7, scale=0.1))
+    if stress:
+        c = torch.arange(C)
+        for name in ("x", "res", "add"):
+            t = o[name]
+            t[:, c % 8 == 0] *= 1e3
+            t[:, c % 8 == 1] *= 1e-3
+            t[:, c % 8 == 2] = 0.0
+            t[:, c % 8 == 4] *= 1e-3
+        o["x"][:, c % 8 == 3] = -o["x"][:, c % 8 == 3].abs()
+        o["x"][:, c % 8 == 4, L // 2] = 1e3
+        o["x"][:, c % 8 == 4, L - 1] = -1e3
+        for wn, bn in (("w", "bias"), ("w2", "b2")):
+            o[wn][c % 4 == 1] *= 1e-2
+            o[wn][c % 4 == 2] *= 1e2
+            o[wn][c % 4 == 3] = 0.0
+            o[bn][c % 4 == 3] = 0.0
+    return o
+
+
+def _lrelu64(v, slope):
+    """Leaky ReLU of a float64 mirror value (an fp32 slope, the product not rounded)."""
+    return v if slope == 1.0 else torch.where(v > 0, v, v * f32(slope))
+
+
+def _zero_row_lim(lim, w, bias, terms, scale):
+    """Rows whose weights and bias are all exactly zero: the kernel's sum is (res + add) * scale and nothing else, so
+    the limit is stated explicitly instead of S * absacc: one rounding of res + add and one of the product with scale,
+    2 * 2^-24 (1 + 2^-24) (|res| + |add|) |scale| -- zero without res and add: the output is exactly zero."""
+    zero = (w.reshape(w.shape[0], -1) == 0).all(1) & (bias == 0)
+    if not zero.any():
+        return lim
+    a = sum(t.to(F64).abs() for t in terms if t is not None)
+    lz = a * (2 * EPS * (1 + EPS) * abs(f32(scale))) if torch.is_tensor(a) else torch.zeros_like(lim)
+    return torch.where(zero[None, :, None], lz, lim)
+
+
+def mrf_linear(x, w, bias, dil=1, in_slope=0.1, res=None, add=None, scale=1.0, dtype=F64, S=None, core=None):
+    """A direct OV_EPI_LINEAR ResBlock instance: ``linear`` without mask and batch bias (ov_conv1d_params has no
+    out_slope: nothing to add) with the MRF allowance ``S`` (default S32_MRF) and the explicit limit of all-zero rows.
+    ``core`` = ``_affine``'s (conv + bias, absacc) computed before, for callers that run several operand forms."""
+    S = S32_MRF if S is None else S
+    v, a = _affine(x, w, bias, dil=dil, in_slope=in_slope, dtype=dtype) if core is None else core
+    for t in (res, add):
+        if t is not None:
+            v, a = v + t.to(dtype), a + t.to(F64).abs()
+    a = a * abs(f32(scale))
+    return Ref(v * f32(scale), a, _zero_row_lim(S * a, w, bias, (res, add), scale))
+
+
+def pair(x, w1, b1, w2, b2, K, dil, add=None, scale=1.0, slope=0.1, dtype=F64, S=None):
+    """ov_resblock_pair_f32: out = (c2(lrelu(h)) + b2 + x [+ add]) * scale, h = c1_dil(lrelu(x)) + b1.
+    h is an fp32 STORAGE POINT of the kernel (it stays in LDS): it lies within lim_h = S absacc_1 + 2^-24 |h64| of the
+    float64 h64, its leaky ReLU (1-Lipschitz, one more fp32 product) within lim_h + 2^-24 |lrelu(h64)|, and that error
+    reaches the output through |w2|:  lim = (S absacc_2 + conv(|w2|, lim_h + 2^-24 |lrelu h64|)) |scale|.
+    h outside [0, L) is ZERO -- the second conv zero-pads h itself (reference modules.py:298-301); it is NOT the first conv
+    evaluated on zero-padded x (which would be b1 + the taps that still reach x): ``F.conv1d``'s own padding of h below.
+    ``dtype`` = float32: fp32 conv -> fp32 h -> fp32 conv, the honest stand-in."""
+    S = S32_MRF if S is None else S
+    assert w1.shape[-1] == K and w2.shape[-1] == K
+    h, a1 = _affine(x, w1, b1, dil=dil, in_slope=slope, dtype=dtype)
+    h64 = h if dtype == F64 else _affine(x, w1, b1, dil=dil, in_slope=slope)[0]
+    act64 = _lrelu64(h64, slope)
+    lim_act = S * a1 + EPS * h64.abs() + EPS * act64.abs()
+    act = act64 if dtype == F64 else _lrelu(h, slope)
+    v = _conv(act.to(dtype), w2.to(dtype)) + b2.to(dtype)[None, :, None] + x.to(dtype)
+    a2 = _conv(act64.abs(), w2.to(F64).abs()) + b2.to(F64).abs()[None, :, None] + x.to(F64).abs()
+    if add is not None:
+        v, a2 = v + add.to(dtype), a2 + add.to(F64).abs()
+    sc = abs(f32(scale))
+    lim = (S * a2 + _conv(lim_act, w2.to(F64).abs())) * sc
+    return Ref(v * f32(scale), a2 * sc, _zero_row_lim(lim, w2, b2, (x, add), scale))
+
+
+# ---- the Winograd-domain conv ------------------------------------------------------------------------------------------
+def wino_u(w, K):
+    """U[o][c][g][p] = fp32(sum_k G[p][k] w'[o][c][3 g + k]) of the zero-extended filter w' (``WINO_LEAD_TAPS`` zero taps in
+    front, zeros behind up to 3 G taps), summed in float64 and rounded once: the packer's values."""
+    O, C, _ = w.shape
+    Gn = (K + 2) // 3
+    wp = torch.zeros(O, C, 3 * Gn, dtype=F64)
+    wp[:, :, WINO_LEAD_TAPS[K]:WINO_LEAD_TAPS[K] + K] = w.to(F64)
+    return torch.einsum("pk,ocgk->ocgp", torch.tensor(WINO_G, dtype=F64), wp.view(O, C, Gn, 3)).float()
+
+
+def _wino_phase(s, u, K, bias, a, dtype, absolute):
+    """One dilation-1 problem s [B, C, M] (already activated) with tiles of 4 outputs starting at 4 n - a: At [sum over ci,
+    then g, of U (.) (Bt d)] per tile -- on absolute values when ``absolute`` -- -> [B, O, M].  ``bias`` starts the point-1
+    accumulator, as in the kernel (column 1 of At is all ones)."""
+    Bn, C, M = s.shape
+    Gn = (K + 2) // 3
+    pad, nv = (K - 1) // 2 + WINO_LEAD_TAPS[K], 3 * (Gn - 1) + 6
+    nt = (M + a + 3) // 4
+    bt, at = torch.tensor(WINO_BT, dtype=dtype), torch.tensor(WINO_AT, dtype=dtype)
+    s, u = s.to(dtype), u.to(dtype)
+    if absolute:
+        bt, at, s, u = bt.abs(), at.abs(), s.abs(), u.abs()
+    win = F.pad(s, (pad + a, 4 * (nt - 1) + nv - (pad + a) - M)).unfold(-1, nv, 4)           # [B, C, nt, nv]
+    d = torch.stack([win[..., 3 * g:3 * g + 6] for g in range(Gn)], 3)                          # [B, C, nt, G, 6]
+    v = torch.einsum("pj,bcngj->bcngp", bt, d)
+    y = torch.einsum("ocgp,bcngp->gbonp", u, v)                                               # summed over ci ...
+    acc = y[0]
+    for g in range(1, Gn):                                                                      # ... then over g
+        acc = acc + y[g]
+    if bias is not None:
+        acc = acc.clone()
+        acc[..., 1] += (bias.abs() if absolute else bias).to(dtype)[None, :, None]
+    out = torch.einsum("ip,bonp->boni", at, acc).reshape(Bn, u.shape[0], 4 * nt)
+    return out[..., a:a + M]
+
+
+def wino_conv(x, w, bias, K, dil=1, in_slope=1.0, dtype=F32, absolute=False, aligns=(0,), u=None):
+    """conv(lrelu(x)) + bias computed the Winograd way: a dilated conv is ``dil`` interleaved undilated ones, each on the
+    subsequence of one residue class of columns.  ``dtype`` = float32 is the RESTATEMENT of the kernel's algorithm (fp32 input
+    transform, fp32 U, fp32 products summed over ci then g, fp32 output transform) -- the honest stand-in and the reference of
+    S_W; ``absolute`` the same on absolute values in float64, per column the maximum over the tile alignments ``aligns``."""
+    xin = _lrelu(x.float(), in_slope)
+    u = wino_u(w, K) if u is None else u               # (``u``: a caller's own transformed weights, for wrong variants)
+    out = None
+    for a in aligns:
+        o = torch.empty(x.shape[0], w.shape[0], x.shape[2], dtype=dtype)
+        for ph in range(dil):
+            if ph < x.shape[2]:
+                o[..., ph::dil] = _wino_phase(xin[..., ph::dil], u, K, bias, a, dtype, absolute)
+        out = o if out is None else torch.maximum(out, o)
+    return out
+
+
+def wino_absacc(x, w, bias, K, dil=1, in_slope=1.0):
+    """absacc_w before res / add / scale: where the kernel really sums.  Per output tile of 4 columns and tap group g it forms
+    At [U_g (.) (Bt d_g)], so the sum its roundings are proportional to is
+        sum over ci, g of |At| (|U_g| (.) (|Bt| |d_g|)) + |bias|
+    The value depends on where the tiles start; per column the maximum over the four alignments is taken, which copies no
+    tiling decision of the kernel into the oracle."""
+    return wino_conv(x, w, bias, K, dil, in_slope, dtype=F64, absolute=True, aligns=(0, 1, 2, 3))
+
+
+def wino_linear(x, w, bias, K, dil=1, in_slope=0.1, out_slope=1.0, res=None, add=None, scale=1.0, dtype=F64, S=None,
+                core=None):
+    """ov_conv1d_wino_f32 / ov_conv1d_wino_multi_f32: lrelu_out(((conv_dil(lrelu(x)) + bias) + res + add) * scale).  The
+    float64 ``ref`` is ``linear``'s; ``absacc`` = (``wino_absacc`` + |res| + |add|) |scale|; lim = S_W absacc, plus
+    2^-24 |ref| for the fp32 product of the output activation (``out_slope`` < 1, 1-Lipschitz otherwise).  ``dtype`` =
+    float32: the restatement ``wino_conv``.  ``core`` = (float64 conv + bias, wino_absacc) computed before, for callers
+    that run several operand forms on the same x and w."""
+    S = S_W if S is None else S
+    if core is None:
+        core = (_affine(x, w, bias, dil=dil, in_slope=in_slope)[0], wino_absacc(x, w, bias, K, dil, in_slope))
+    v, a = core
+    if dtype != F64:
+        v = wino_conv(x, w, bias, K, dil, in_slope, dtype=dtype)
+    for t in (res, add):
+        if t is not None:
+            v, a = v + t.to(dtype), a + t.to(F64).abs()
+    v, a = v * f32(scale), a * abs(f32(scale))
+    lim = _zero_row_lim(S * a, w, bias, (res, add), scale)
+    if out_slope != 1.0:
+        v = _lrelu64(v, out_slope) if dtype == F64 else _lrelu(v, out_slope)
+        lim = lim + EPS * (core[0] * f32(scale)).abs()
+    return Ref(v, a, lim)
+
+
+# ---- the measurements behind S32_MRF and S_W ---------------------------------------------------------------------------
+def measure_mrf(cs=MRF_CS, kds=MRF_KD, seeds=range(5), ls=MRF_LS, datas=(False, True)):
+    """(C, K, dil) -> [max |conv_fp32 - conv_fp64| / absacc of PyTorch's CPU fp32 conv,
+                       max |wino_fp32 - conv_fp64| / absacc_w of the fp32 restatement,
+                       median absacc_w / absacc on the stress data]."""
+    table = collections.OrderedDict()
+    for C in cs:
+        for K, dil in kds:
+            row = table.setdefault((C, K, dil), [0.0, 0.0, []])
+            for seed in seeds:
+                for L in ls:
+                    for stress in datas:
+                        o = mrf_operands(C, K, dil, L, seed, stress)
+                        v64, a = _affine(o["x"], o["w"], o["bias"], dil=dil, in_slope=0.1)
+                        v32 = _affine(o["x"], o["w"], o["bias"], dil=dil, in_slope=0.1, dtype=F32)[0]
+                        aw = wino_absacc(o["x"], o["w"], o["bias"], K, dil, 0.1)
+                        w32 = wino_conv(o["x"], o["w"], o["bias"], K, dil, 0.1)
+                        ok = a > 0
+                        if ok.any():
+                            row[0] = max(row[0], ((v32.to(F64) - v64).abs()[ok] / a[ok]).max().item())
+                            row[1] = max(row[1], ((w32.to(F64) - v64).abs()[ok] / aw[ok]).max().item())
+                            if stress:
+                                row[2].append((aw[ok] / a[ok]).median().item())
+    return table
+
+
 def main():
     torch.set_num_threads(max(1, min(4, torch.get_num_threads())))
+    _main_frame()
+    mrf = measure_mrf()
+    print("MRF: max |v_fp32 - v_fp64| / absacc (direct, PyTorch fp32 conv) and / absacc_w (fp32 Winograd restatement),")
+    print("     median absacc_w / absacc on stress data; seeds 0..4, L in", MRF_LS, ", benign and stress")
+    for (C, K, dil), (d, w, m) in mrf.items():
+        print(f"    C={C:<3d} k={K:<2d} d={dil}   direct {d:.2e}   wino {w:.2e}   absacc_w/absacc {float(np.median(m)):.2f}")
+    dtop, wtop = max(v[0] for v in mrf.values()), max(v[1] for v in mrf.values())
+    print(f"    direct largest {dtop:.3e};  4 x largest = {4 * dtop:.3e};  module S32_MRF = {S32_MRF:.3e} (S32 = {S32:.3e})")
+    print(f"    wino   largest {wtop:.3e};  4 x largest = {4 * wtop:.3e};  module S_W = {S_W:.3e}")
+    print(f"    median absacc_w / absacc over all stress shapes {float(np.median([x for v in mrf.values() for x in v[2]])):.2f}")
+
+
+def _main_frame():
     s32 = measure_s32()
     print("S32: max |v_fp32 - v_fp64| / absacc, seeds 0..4, T in", T_EDGES)
     for name, v in s32.items():

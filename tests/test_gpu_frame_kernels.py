@@ -32,6 +32,7 @@ from openvoice_amd.engine import (PackedConv, conv_transpose_as_conv, convt_row_
 from openvoice_amd._lib import (EPI_CONVT, EPI_COUPLE, EPI_GATE, EPI_MAGNITUDE, EPI_POSTERIOR,  # noqa: E402
                                 EPI_RESSKIP, F_CONVT_GROUPED, F_MASK_V, F_OUT2_INIT)
 from oracle import fp32_ref as R  # noqa: E402
+from oracle.nanbuf import Buf  # noqa: E402
 
 DEV = "cuda:0"
 NAN = float("nan")
@@ -74,41 +75,7 @@ def _knobs(inst):
     return dict(tile=TILE_ID[inst[2]], chunk=inst[3], loaders=inst[6])
 
 
-# ---- tensors inside larger NaN-filled buffers ---------------------------------------------------------------------------
-class Buf:
-    """A [B, C, L] block at element offset ``off`` of a flat NaN-filled device buffer: row stride ld > L, batch stride
-    bs > C * ld.  ``layout``: "vec" / "out" = ld % 4 == 0 and a 16-byte base, "odd_ld" = odd row stride, "shift1" = the
-    base one float past a 16-byte boundary."""
-
-    def __init__(self, t, layout="out"):
-        self.B, self.C, self.L = t.shape
-        l4 = (self.L + 3) // 4 * 4
-        self.ld = l4 + 1 if layout == "odd_ld" else l4 + 4
-        self.off = 9 if layout == "shift1" else 8
-        self.bs = self.C * self.ld + 16
-        flat = torch.full((self.off + self.B * self.bs + 8,), NAN)
-        valid = torch.zeros_like(flat, dtype=torch.bool)
-        self._block(flat)[:, :, :self.L] = t
-        self._block(valid)[:, :, :self.L] = True
-        self.flat, self.valid = flat.to(DEV), valid
-        assert self.flat.data_ptr() % 16 == 0
-
-    def _block(self, flat):
-        return flat[self.off:self.off + self.B * self.bs].view(self.B, self.bs)[:, :self.C * self.ld].view(
-            self.B, self.C, self.ld)
-
-    def tail(self):
-        """The buffer from the block's first element on: what a C caller passes as ``ptr + off``."""
-        return self.flat[self.off:]
-
-    def get(self):
-        """The valid block on the host, after checking that nothing outside it was written."""
-        torch.cuda.synchronize()
-        flat = self.flat.cpu()
-        assert torch.isnan(flat[~self.valid]).all(), "written outside the valid [B, C, :L] block"
-        return self._block(flat)[:, :, :self.L].clone()
-
-
+# ---- tensors inside larger NaN-filled buffers: oracle/nanbuf.py ``Buf`` ------------------------------------------------
 def _mask_rows(mask):
     """[B, T] -> device [B, mld] with NaN pad columns; returns (tensor, mld)."""
     T = mask.shape[1]

@@ -6,6 +6,8 @@ summation order; bounds below are ~1e-5 relative to the output scale (stated per
 
 The frame-rate epilogues (GATE, RESSKIP, COUPLE, POSTERIOR, CONVT, MAGNITUDE, frame-rate LINEAR) are also held, instance by
 instance and element by element, to float64 mirrors in tests/test_gpu_frame_kernels.py (oracle/fp32_ref.py).
+The sample-rate ResBlock (MRF) LINEAR instances -- every X(...) line of conv1d_inst_a.hip .. conv1d_inst_f.hip with tile, chunk
+and loader count forced -- are held the same way in tests/test_gpu_mrf_kernels.py; the norm-wise bars below stay, they are weaker.
 """
 import ctypes
 
@@ -364,7 +366,7 @@ def test_forced_variant_that_does_not_exist_is_an_error():
 
 
 def test_residual_is_preloaded_only_without_value_mask():
-    """LINEAR with a residual starts the accumulators at res (+ add); with OV_F_MASK_V the reference
+    """LINEAR with a residual starts the accumulators at res (add joins in the epilogue); with OV_F_MASK_V the reference
     order v*mask + res must be kept (the mask must not touch the residual)."""
     B, C, L, k = 2, 64, 777, 3
     x, res, add = _rand(B, C, L, seed=1), _rand(B, C, L, seed=2), _rand(B, C, L, seed=3)

@@ -2,6 +2,8 @@
 and against the direct fp32 MFMA kernel: every instance, ragged lengths around the 128-column tile, one and several
 M-blocks, residual / running-sum / scale operands, padded rows, forced workgroup counts (items that span utterances).
 Bar: max-abs error vs float64 <= 16x the direct kernel's (measured ~4x) and <= 2e-5 of the output scale.
+Both bars are norm-wise and the first measures a kernel against a kernel: tests/test_gpu_mrf_kernels.py holds every supported
+(C, K, dilation) and the multi launch, element by element, to ``oracle.fp32_ref.wino_linear`` (S_W * absacc_w, its own bound).
 reference: openvoice/modules.py:296-309."""
 import pytest
 import torch
