@@ -616,6 +616,24 @@ int ov_expand_prior_f32(const float* m_tok, const float* logs_tok, int64_t tok_b
                         float* m_p, float* logs_p, float* attn, int B, int C, int Tx, int Ty, int ldy,
                         float noise_scale, ov_stream_t stream);
 
+/* Per-item synthesis controls (additive: same ABI version).  The reference applies sdp_ratio, length_scale and
+ * noise_scale element-wise (models.py:474-487), so the items of a batch may each have their own.
+ *
+ * ov_duration_items_f32 replaces the same lines as ov_duration_f32 (models.py:474-479) with sdp_ratio_b[b] and
+ * length_scale_b[b], two [B] fp32 device vectors, in place of the two scalars.  Row b of logw, cum and y_len holds the
+ * bits ov_duration_f32 writes there when called with item b's pair; the prefix sum is a workgroup scan. */
+int ov_duration_items_f32(const float* z_sdp, int64_t z_bstride, float ea_m, float ea_logs, const float* dp,
+                          int64_t dp_bstride, const float* mask, float* logw, int32_t* cum, int64_t* y_len, int B,
+                          int T, int ld, const float* sdp_ratio_b, const float* length_scale_b, ov_stream_t stream);
+
+/* ov_expand_prior_f32 (models.py:480-487, commons.py:128-142) with noise_scale_b[b], a [B] fp32 device vector, in
+ * place of the scalar: z_p = m_p + noise * exp(logs_p) * noise_scale_b[b].  Every output of item b holds the bits
+ * ov_expand_prior_f32 writes when called with noise_scale_b[b]; Tx <= 2^25. */
+int ov_expand_prior_items_f32(const float* m_tok, const float* logs_tok, int64_t tok_bstride, int ldx,
+                              const int32_t* cum, const int64_t* x_len, const int64_t* y_len, const float* noise,
+                              int64_t noise_bstride, int ldn, float* z_p, float* m_p, float* logs_p, float* attn,
+                              int B, int C, int Tx, int Ty, int ldy, const float* noise_scale_b, ov_stream_t stream);
+
 /* ---- bf16 generator (BASELINE.json configs[4]; reference openvoice/models.py:272-291, modules.py:296-306) ------
  * Channels-last bf16 activations (B, L, C): C contiguous, rows dense.  bf16 values are passed as uint16_t bit
  * patterns.  Accumulation and bias are fp32; outputs are rounded to nearest even. */

@@ -208,6 +208,10 @@ SIGNATURES = {
                                        _i, _i, _i, ctypes.c_float, ctypes.c_float, _fp]),
     "ov_expand_prior_f32": (ctypes.c_int, [_fp, _fp, _i64, _i, _fp, _fp, _fp, _fp, _i64, _i, _fp, _fp, _fp, _fp,
                                            _i, _i, _i, _i, _i, ctypes.c_float, _fp]),
+    "ov_duration_items_f32": (ctypes.c_int, [_fp, _i64, ctypes.c_float, ctypes.c_float, _fp, _i64, _fp, _fp, _fp, _fp,
+                                             _i, _i, _i, _fp, _fp, _fp]),
+    "ov_expand_prior_items_f32": (ctypes.c_int, [_fp, _fp, _i64, _i, _fp, _fp, _fp, _fp, _i64, _i, _fp, _fp, _fp, _fp,
+                                                 _i, _i, _i, _i, _i, _fp, _fp]),
 }
 
 _lib = None

@@ -116,6 +116,31 @@ class BaseSpeakerTTS(OpenVoiceBaseClass):
             out[i, :, :w] = z.reshape(-1, z.shape[-1])[:, :w].to(out.device)
         return out
 
+    @staticmethod
+    def per_sentence(name, value, n, integer=False, positive=False):
+        """A synthesis control that is one value for all ``n`` sentences, or a list / tuple / array / tensor with one
+        per sentence.  Returns ``(False, value)`` for the one value, untouched, and ``(True, [n numbers])`` for the
+        list -- ints where ``integer``, floats otherwise.  A list of another length, a non-finite entry, or (where
+        ``positive``) an entry ``<= 0`` is a ValueError."""
+        if isinstance(value, torch.Tensor):
+            value = value.detach().cpu().numpy()
+        if isinstance(value, np.ndarray):
+            if value.ndim == 0:
+                return False, value.item()
+            value = value.reshape(-1).tolist()
+        if not isinstance(value, (list, tuple)):
+            return False, value
+        if len(value) != n:
+            raise ValueError(f"{name}: one value, or one per sentence ({n}), got {len(value)}")
+        if integer:
+            return True, [int(v) for v in value]
+        vals = [float(v) for v in value]
+        if not all(np.isfinite(vals)):
+            raise ValueError(f"{name}: non-finite value in {vals}")
+        if positive and not all(v > 0 for v in vals):
+            raise ValueError(f"{name}: every value must be positive, got {vals}")
+        return True, vals
+
     @torch.no_grad()
     def infer_padded(self, id_sequences, speaker_id, speed=1.0, noise_scale=0.667, noise_scale_w=0.6, noise_w=None,
                      noise_z=None, *, seed=None, generator="fp32"):
@@ -125,12 +150,20 @@ class BaseSpeakerTTS(OpenVoiceBaseClass):
         explicit forms of ``infer``'s two draws; in the batch each is zero-padded to the widest); ``seed`` (instead of
         them): counter-based noise (``noise.py``), an int ``s`` giving sentence ``i`` the stream ``(s, i)``, or a list
         with one seed / pair per sentence.  ``generator``: ``"fp32"`` (default) or ``"bf16"`` -- the generator on the
-        bf16 kernels, the ragged batch as dense length groups (``TtsEngine.infer``).  This is the launch
+        bf16 kernels, the ragged batch as dense length groups (``TtsEngine.infer``).  ``speaker_id``, ``speed``,
+        ``noise_scale`` and ``noise_scale_w``: one value for the batch, or a list with one per sentence (``per_sentence``)
+        -- sentences of different speakers and speeds then share this one launch sequence (``infer`` with per-item
+        controls), each getting what a batch of its own values gives it.  This is the launch
         sequence behind ``tts_from_ids(batched=True)`` and ``clone.VoiceCloner``."""
         _lib.check_generator(generator)
         noise_mod.exclusive(seed, noise_w=noise_w, noise_z=noise_z)
         device = self.device
         seqs = [torch.as_tensor(s, dtype=torch.long).reshape(-1) for s in id_sequences]
+        many_speakers, speaker_id = self.per_sentence("speaker_id", speaker_id, len(seqs), integer=True)
+        many_speeds, speed = self.per_sentence("speed", speed, len(seqs), positive=True)
+        noise_scale = self.per_sentence("noise_scale", noise_scale, len(seqs))[1]
+        noise_scale_w = self.per_sentence("noise_scale_w", noise_scale_w, len(seqs))[1]
+        length_scale = [1.0 / s for s in speed] if many_speeds else 1.0 / speed
         if seed is not None:
             seed = noise_mod.per_item(seed, len(seqs))
         for name, nz in (("noise_w", noise_w), ("noise_z", noise_z)):
@@ -140,7 +173,10 @@ class BaseSpeakerTTS(OpenVoiceBaseClass):
         x = torch.zeros(len(seqs), int(lengths.max()), dtype=torch.long)
         for i, s in enumerate(seqs):
             x[i, :s.numel()] = s
-        sid = torch.full((len(seqs),), int(speaker_id), dtype=torch.long)
+        if many_speakers:
+            sid = torch.tensor(speaker_id, dtype=torch.long)
+        else:
+            sid = torch.full((len(seqs),), int(speaker_id), dtype=torch.long)
         if noise_w is not None:
             noise_w = self._batch_noise(noise_w, x.shape[1])
         if noise_z is not None:
@@ -148,7 +184,7 @@ class BaseSpeakerTTS(OpenVoiceBaseClass):
         # padded batch: the generator computes length + margin (16-20) frames per sentence, not the longest one's (the
         # samples returned below are bit-identical either way)
         o, _, y_mask, _ = self.model.infer(x.to(device), lengths.to(device), sid=sid.to(device), noise_scale=noise_scale,
-                                           noise_scale_w=noise_scale_w, length_scale=1.0 / speed, noise_w=noise_w,
+                                           noise_scale_w=noise_scale_w, length_scale=length_scale, noise_w=noise_w,
                                            noise_z=noise_z, skip_padding=True, **noise_mod.kw(seed),
                                            **self._generator_kw(generator))
         return o, y_mask[:, 0].sum(1).long()
@@ -170,7 +206,10 @@ class BaseSpeakerTTS(OpenVoiceBaseClass):
         an int ``s`` giving sentence ``i`` the stream ``(s, i)`` in the batched and in the per-sentence loop alike (so
         both draw the same durations), or a list with one seed / pair per sentence; a seeded call is reproducible
         without anyone guessing ``Ty``.  ``generator``: ``"fp32"`` (default) or ``"bf16"``, the generator's kernels in
-        either loop (``TtsEngine.infer``).  Returns a list of float32 numpy waveforms."""
+        either loop (``TtsEngine.infer``).  ``speaker_id``, ``speed``, ``noise_scale`` and ``noise_scale_w``: one value,
+        or a list with one per sentence -- in the per-sentence loop sentence ``i`` runs with its own scalars, in the
+        batched path the lists become ``infer``'s per-item vectors (``infer_padded``).  Returns a list of float32 numpy
+        waveforms."""
         _lib.check_generator(generator)
         noise_mod.exclusive(seed, noise_w=noise_w, noise_z=noise_z)
         device = self.device
@@ -182,8 +221,14 @@ class BaseSpeakerTTS(OpenVoiceBaseClass):
                 if nz is not None and len(nz) != len(seqs):
                     raise ValueError(f"{name}: one tensor per sentence ({len(seqs)}), got {len(nz)}")
             row = lambda nz, i: None if nz is None else torch.as_tensor(nz[i], dtype=torch.float32)[None]
+            # sentence i gets its own scalars: every call below is the scalar launch sequence
+            controls = [self.per_sentence("speaker_id", speaker_id, len(seqs), integer=True),
+                        self.per_sentence("speed", speed, len(seqs), positive=True),
+                        self.per_sentence("noise_scale", noise_scale, len(seqs)),
+                        self.per_sentence("noise_scale_w", noise_scale_w, len(seqs))]
             out = []
             for i, s in enumerate(seqs):
+                speaker_id, speed, noise_scale, noise_scale_w = (v[i] if many else v for many, v in controls)
                 o = self.model.infer(s[None].to(device), torch.LongTensor([s.numel()]).to(device),
                                      sid=torch.LongTensor([speaker_id]).to(device), noise_scale=noise_scale,
                                      noise_scale_w=noise_scale_w, length_scale=1.0 / speed, noise_w=row(noise_w, i),

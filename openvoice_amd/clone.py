@@ -20,6 +20,10 @@ Contract: ``speak_ids_many`` equals, bit for bit, the chain made of the public p
 ~13 frames of a sentence depend on whether it is the longest of its batch (``tts_from_ids`` says so), so the result
 depends on the batch composition: on the other requests of the call and on ``max_sentences_per_launch``, never on
 timing.
+
+``mixed=True`` (off by default) lets requests of different speeds and base speakers share ``infer`` launches:
+``sentence_batches`` then makes one pool of all sentences, and each batch is one ``infer_padded`` with a speaker and a
+speed per sentence.  The contract reads the same with that call as the public piece.
 """
 import numpy as np
 
@@ -124,13 +128,15 @@ def join_segments(o, lengths, groups, gap):
     return [dst[b:b + t] for b, t in zip(bases, totals)]
 
 
-def sentence_batches(lengths, keys, max_sentences_per_launch=DEFAULT_SENTENCES_PER_LAUNCH):
+def sentence_batches(lengths, keys, max_sentences_per_launch=DEFAULT_SENTENCES_PER_LAUNCH, mixed=False):
     """Which sentences share an ``infer`` launch: a pure function of its arguments.  ``lengths[r]``: the id counts of
-    request r's sentences; ``keys[r]``: what one ``infer`` call has a single value of -- ``(speed, speaker id)``:
-    ``length_scale`` is per call, and so is the speaker of ``tts_from_ids``, which the contract is stated against.
+    request r's sentences; ``keys[r]``: what a keyed ``infer`` call has a single value of -- ``(speed, speaker id)``,
+    the scalar ``speed`` and ``speaker_id`` of ``tts_from_ids``, which the keyed contract is stated against.
     Requests of one key (taken in order of first appearance) pool their sentences, longest first (ties: request, then
     sentence order) so that padding is small, and the pool is cut into batches of at most ``max_sentences_per_launch``.
-    Returns ``[(key, [(request, sentence), ...]), ...]``; every sentence appears exactly once."""
+    ``mixed=True``: one pool for all requests whatever their key (``infer`` with per-item controls), ordered and cut
+    the same way; the key of every such batch is None and the caller takes each item's speed and speaker from its
+    request.  Returns ``[(key, [(request, sentence), ...]), ...]``; every sentence appears exactly once."""
     m = int(max_sentences_per_launch)
     if m < 1:
         raise ValueError(f"max_sentences_per_launch = {max_sentences_per_launch}")
@@ -138,7 +144,7 @@ def sentence_batches(lengths, keys, max_sentences_per_launch=DEFAULT_SENTENCES_P
         raise ValueError("one key per request")
     pools = {}
     for r, (lens, key) in enumerate(zip(lengths, keys)):
-        pools.setdefault(key, []).extend((-int(n), r, s) for s, n in enumerate(lens))
+        pools.setdefault(None if mixed else key, []).extend((-int(n), r, s) for s, n in enumerate(lens))
     batches = []
     for key, pool in pools.items():
         pool.sort()
@@ -208,17 +214,24 @@ class VoiceCloner:
 
     # ---- the chain ---------------------------------------------------------------------------------------------------
     def synthesize_many(self, reqs, noise_w=None, noise_z=None, noise_scale=0.667, noise_scale_w=0.6,
-                        max_sentences_per_launch=DEFAULT_SENTENCES_PER_LAUNCH, generator="fp32"):
+                        max_sentences_per_launch=DEFAULT_SENTENCES_PER_LAUNCH, generator="fp32", mixed=False):
         """Steps 1 and 2 for parsed requests: the joined base-speaker waveforms, one 1-D device tensor per request at
-        the TTS model's rate.  ``generator``: ``"fp32"`` (default) or ``"bf16"``, handed to ``infer_padded``."""
+        the TTS model's rate.  ``generator``: ``"fp32"`` (default) or ``"bf16"``, handed to ``infer_padded``.
+        ``mixed``: False (default) -- one launch sequence per ``(speed, speaker)`` key; True -- the sentences of all
+        requests in shared launches (``sentence_batches(mixed=True)``), ``infer_padded`` getting one speaker and one
+        speed per sentence."""
         import torch
         gen_kw = {} if _lib.check_generator(generator) == "fp32" else {"generator": generator}
         batches = sentence_batches([[s.shape[0] for s in r.ids] for r in reqs], [(r.speed, r.speaker) for r in reqs],
-                                   max_sentences_per_launch)
+                                   max_sentences_per_launch, mixed=bool(mixed))
         self.last_batches = batches
         pick = lambda nz, items: None if nz is None else [nz[r][s] for r, s in items]
         outs, counts = [], []
-        for (speed, speaker), items in batches:
+        for key, items in batches:
+            if key is None:         # a mixed batch: every sentence brings its request's speaker and speed
+                speaker, speed = [reqs[r].speaker for r, _ in items], [reqs[r].speed for r, _ in items]
+            else:
+                speed, speaker = key
             o, frames = self.tts.infer_padded([reqs[r].ids[s] for r, s in items], speaker, speed=speed,
                                               noise_scale=noise_scale, noise_scale_w=noise_scale_w,
                                               noise_w=pick(noise_w, items), noise_z=pick(noise_z, items), **gen_kw)
@@ -249,7 +262,7 @@ class VoiceCloner:
                        message="default", window_frames=longform.DEFAULT_WINDOW_FRAMES,
                        windows_per_launch=longform.DEFAULT_MANY_WINDOWS_PER_LAUNCH,
                        max_sentences_per_launch=DEFAULT_SENTENCES_PER_LAUNCH, noise_scale=0.667, noise_scale_w=0.6,
-                       generator="fp32"):
+                       generator="fp32", mixed=False):
         """Many "say this in that voice" requests in shared launches.  ``requests[i]``: ``(id sequences, speaker, src_se,
         tgt_se[, speed[, out_sr]])`` (or a dict with those keys) -- the sentences as symbol ids (blanks interspersed by
         the caller if the config asks for it), the base speaker's name or id, the two ``[1, 256, 1]`` embeddings, the
@@ -260,7 +273,9 @@ class VoiceCloner:
         result equals the chain of the public pieces (module docstring) and depends on the batch composition.
         ``generator``: ``"fp32"`` (default) or ``"bf16"`` -- both halves of the chain run their generator on those
         kernels (``tts_from_ids(generator=)``, ``convert_many(generator=)``; the contract above holds with the same
-        keyword on the public pieces)."""
+        keyword on the public pieces).  ``mixed=True``: requests of different speeds and base speakers share ``infer``
+        launches too (``synthesize_many``); the public piece is then ``infer_padded`` with the per-sentence speaker and
+        speed lists of each batch of ``last_batches``.  The default keeps one launch sequence per ``(speed, speaker)``."""
         import torch
         from . import audio_io
         _lib.check_generator(generator)
@@ -271,7 +286,7 @@ class VoiceCloner:
             return []
         with torch.no_grad():
             waves = self.synthesize_many(reqs, noise_w, noise_z, noise_scale, noise_scale_w, max_sentences_per_launch,
-                                         **gen_kw)
+                                         mixed=mixed, **gen_kw)
             msr = int(conv.hps.data.sampling_rate)
             waves = rates.resample_many(waves, [(self.tts_sr, msr)] * len(waves), self.device)
             outs = conv._windowed(window_frames, windows_per_launch).convert_many(
@@ -288,20 +303,22 @@ class VoiceCloner:
         return audios
 
     def speak_ids(self, id_sequences, speaker, src_se, tgt_se, speed=1.0, out_sr=None, output_path=None, noise_w=None,
-                  noise_z=None, noise=None, generator="fp32", **kwargs):
-        """``speak_ids_many`` of one request: its audio (and ``output_path`` written when given)."""
+                  noise_z=None, noise=None, generator="fp32", mixed=False, **kwargs):
+        """``speak_ids_many`` of one request: its audio (and ``output_path`` written when given).  ``mixed``: as for
+        ``speak_ids_many`` (one request has one key: the same sentences share the launches either way, ``mixed=True``
+        runs them on the per-item kernels)."""
         _lib.check_generator(generator)
         one = lambda x: None if x is None else [x]
         return self.speak_ids_many([(id_sequences, speaker, src_se, tgt_se, speed, out_sr)], noise_w=one(noise_w),
                                    noise_z=one(noise_z), noise=one(noise), output_paths=one(output_path),
-                                   generator=generator, **kwargs)[0]
+                                   generator=generator, mixed=mixed, **kwargs)[0]
 
     def speak_many(self, texts, speaker, src_se, tgt_se, language="English", speed=1.0, out_sr=None, generator="fp32",
-                   **kwargs):
+                   mixed=False, **kwargs):
         """``speak_ids_many`` of texts, each through ``BaseSpeakerTTS.text_to_ids`` (sentence pieces, language marks,
         ``get_text``: exactly what ``tts`` does; the same RuntimeError when no text front end is registered).
         ``speaker`` / ``src_se`` / ``tgt_se`` / ``language`` / ``speed`` / ``out_sr``: one for all, or a list with one
-        per text; ``generator``: as for ``speak_ids_many``."""
+        per text; ``generator`` and ``mixed``: as for ``speak_ids_many``."""
         _lib.check_generator(generator)
         texts = list(texts)
         per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * len(texts)
@@ -310,7 +327,7 @@ class VoiceCloner:
             raise ValueError("speak_many: one value, or one per text")
         requests = [(self.tts.text_to_ids(t, lang), spk, s, g, spd, r)
                     for t, spk, s, g, lang, spd, r in zip(texts, *cols)]
-        return self.speak_ids_many(requests, generator=generator, **kwargs)
+        return self.speak_ids_many(requests, generator=generator, mixed=mixed, **kwargs)
 
     def speak(self, text, speaker, src_se, tgt_se, language="English", speed=1.0, out_sr=None, output_path=None,
               noise_w=None, noise_z=None, noise=None, generator="fp32", **kwargs):

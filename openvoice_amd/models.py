@@ -148,6 +148,8 @@ class SynthesizerTrn(nn.Module):
         reference's two RNG draws (optional); ``seed`` draws both counter-based (``noise.py``: row ``b`` of an int
         ``s`` is stream ``(s, b)``, ``noise_w`` purpose 1 over the tokens, ``noise_z`` purpose 2 over the frames).
         ``generator``: ``"fp32"`` (default) or ``"bf16"``, the generator's kernels (``TtsEngine.infer``).
+        ``noise_scale``, ``length_scale``, ``noise_scale_w`` and ``sdp_ratio`` each take one number, as in the
+        reference, or a sequence / tensor with one value per item of the batch (``tts_engine.item_controls``).
         Returns ``(o, attn, y_mask, (z, z_p, m_p, logs_p))``."""
         _lib.check_generator(generator)
         if self.n_speakers == 0:

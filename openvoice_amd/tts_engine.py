@@ -16,6 +16,7 @@ stores whole 32-row fragments); the Flips between the spline flows are not mater
 alternate); of ``sdp.flows.0`` (ElementwiseAffine) only channel 0 is ever read, so it is two scalars.
 """
 import math
+import numbers
 
 import torch
 
@@ -36,6 +37,39 @@ def check_token_count(Tx):
     if Tx > MAX_TOKENS:
         raise ValueError(f"infer: token axis of {Tx} tokens, but the text encoder's attention kernel holds at most "
                          f"{MAX_TOKENS}; split the text into shorter pieces (BaseSpeakerTTS splits by sentence)")
+
+
+CONTROLS = ("noise_scale", "length_scale", "noise_scale_w", "sdp_ratio")
+
+
+def _is_number(v):
+    """One value for the whole batch: a Python (or numpy) number, or a tensor / array of exactly zero dimensions."""
+    return isinstance(v, numbers.Real) or (hasattr(v, "ndim") and v.ndim == 0)
+
+
+def item_controls(B, noise_scale, length_scale, noise_scale_w, sdp_ratio):
+    """The four synthesis controls of ``infer`` as per-item values.  Each is one number for the batch or a sequence /
+    tensor of ``B`` numbers.  All four plain numbers: returns None (the scalar kernels run).  Any of them per item:
+    returns ``{name: [B floats]}`` with the plain numbers broadcast.  A per-item control of the wrong length, a
+    non-finite value in it, or a per-item ``length_scale <= 0`` is a ValueError.  ``sdp_ratio`` is not confined to
+    [0, 1]: the reference's ``sdp * r + dp * (1 - r)`` (models.py:474) extrapolates outside it and so do the kernels."""
+    given = dict(zip(CONTROLS, (noise_scale, length_scale, noise_scale_w, sdp_ratio)))
+    if all(_is_number(v) for v in given.values()):
+        return None
+    out = {}
+    for name, v in given.items():
+        if _is_number(v):
+            out[name] = [float(v)] * B
+            continue
+        vals = [float(x) for x in (v.detach().reshape(-1).cpu().tolist() if isinstance(v, torch.Tensor) else list(v))]
+        if len(vals) != B:
+            raise ValueError(f"infer: {name} has {len(vals)} values for a batch of {B}; give one number, or one per item")
+        if not all(math.isfinite(x) for x in vals):
+            raise ValueError(f"infer: {name} holds a non-finite value: {vals}")
+        if name == "length_scale" and not all(x > 0 for x in vals):
+            raise ValueError(f"infer: length_scale must be positive for every item, got {vals}")
+        out[name] = vals
+    return out
 
 
 def _pad_rows(w, b, rows):
@@ -158,11 +192,21 @@ class TtsEngine:
         (``bf16.GeneratorBf16``, built on first use; ``use_bf16_generator`` is neither read nor set), everything before
         it unchanged: ``attn``, ``y_mask`` and the four latents are the fp32 call's bits.  With ``skip_padding`` the
         padded batch then runs as a few dense length groups (``GeneratorBf16.decode_groups``: valid samples the bits of
-        the padded bf16 run, the tail zero), without it as one padded ``GeneratorBf16.decode``."""
+        the padded bf16 run, the tail zero), without it as one padded ``GeneratorBf16.decode``.
+        ``noise_scale`` / ``length_scale`` / ``noise_scale_w`` / ``sdp_ratio``: each one number for the batch, or a
+        sequence / tensor with one value per item (``item_controls``).  Four plain numbers are the scalar launches
+        (``ov_duration_f32``, ``ov_expand_prior_f32``); otherwise all four become ``[B]`` device vectors and
+        ``ov_duration_items_f32`` / ``ov_expand_prior_items_f32`` run in their place: item ``b`` gets the durations,
+        alignment and prior that a call with item ``b``'s four numbers gives it, bit for bit; everything downstream
+        (flow, generator, ``skip_padding``, ``seed``) is per item already."""
         _lib.check_generator(generator)
         dev = self.device
         noise_mod.exclusive(seed, noise_w=noise_w, noise_z=noise_z)
         check_token_count(tokens.shape[-1])
+        items = item_controls(tokens.shape[0], noise_scale, length_scale, noise_scale_w, sdp_ratio)
+        if items is not None:       # one host -> device copy: row i is control i of CONTROLS, one value per item
+            ctl = torch.tensor([items[name] for name in CONTROLS], dtype=torch.float32).to(dev)
+            noise_scale_b, length_scale_b, noise_scale_w_b, sdp_ratio_b = ctl[0], ctl[1], ctl[2], ctl[3]
         tokens = tokens.to(dev, torch.int64).contiguous()
         lengths = lengths.to(dev, torch.int64).contiguous()
         sid = sid.to(dev, torch.int64).reshape(-1)
@@ -219,7 +263,10 @@ class TtsEngine:
         elif noise_w is None:
             noise_w = torch.randn(B, 2, Tx, dtype=torch.float32, device=dev)
         zw = f(B, 2, Lx)
-        zw[:, :, :Tx].copy_(noise_w.to(dev, torch.float32) * float(noise_scale_w))
+        if items is None:
+            zw[:, :, :Tx].copy_(noise_w.to(dev, torch.float32) * float(noise_scale_w))
+        else:                       # a product of two fp32 numbers has one result: the scalar path's bits per item
+            zw[:, :, :Tx].copy_(noise_w.to(dev, torch.float32) * noise_scale_w_b.view(B, 1, 1))
         c0, c1 = 1, 0                                                           # a Flip precedes every ConvFlow
         for fl in self.sdp_flows:
             _lib.call("ov_expand1_f32", (zw, c0 * Lx), 2 * Lx, fl["pre_w"], fl["pre_b"], xs, hflow, B, Fs, Tx, Lx)
@@ -232,8 +279,12 @@ class TtsEngine:
         logw = f(B, Lx)
         cum = torch.zeros(B, Lx, dtype=torch.int32, device=dev)
         y_len = torch.zeros(B, dtype=torch.int64, device=dev)
-        _lib.call("ov_duration_f32", zw, 2 * Lx, self.ea_m, self.ea_logs, dp_out, 32 * Lx, mask, logw, cum, y_len,
-                  B, Tx, Lx, float(sdp_ratio), float(length_scale))
+        if items is None:
+            _lib.call("ov_duration_f32", zw, 2 * Lx, self.ea_m, self.ea_logs, dp_out, 32 * Lx, mask, logw, cum, y_len,
+                      B, Tx, Lx, float(sdp_ratio), float(length_scale))
+        else:
+            _lib.call("ov_duration_items_f32", zw, 2 * Lx, self.ea_m, self.ea_logs, dp_out, 32 * Lx, mask, logw, cum,
+                      y_len, B, Tx, Lx, sdp_ratio_b, length_scale_b)
         if generator == "bf16":       # the same one sync, carrying every length: decode_groups plans on the host
             y_host = y_len.cpu().tolist()
             Ty = max(y_host)
@@ -253,8 +304,12 @@ class TtsEngine:
         m_p, logs_p = f(B, C, Ly), f(B, C, Ly)
         attn = f(B, Ty, Tx) if return_attn else None
         z_p, z = ws["z_p"], ws["z_hat"]
-        _lib.call("ov_expand_prior_f32", stats, (stats, C * Lx), 2 * C * Lx, Lx, cum, lengths, y_len, ws["noise"],
-                  C * Ly, Ly, z_p, m_p, logs_p, attn, B, C, Tx, Ty, Ly, float(noise_scale))
+        if items is None:
+            _lib.call("ov_expand_prior_f32", stats, (stats, C * Lx), 2 * C * Lx, Lx, cum, lengths, y_len, ws["noise"],
+                      C * Ly, Ly, z_p, m_p, logs_p, attn, B, C, Tx, Ty, Ly, float(noise_scale))
+        else:
+            _lib.call("ov_expand_prior_items_f32", stats, (stats, C * Lx), 2 * C * Lx, Lx, cum, lengths, y_len,
+                      ws["noise"], C * Ly, Ly, z_p, m_p, logs_p, attn, B, C, Tx, Ty, Ly, noise_scale_b)
         cond_flow = [core._wn_cond(cp["wn"], g) for cp in core.couplings]
         core._flow(z_p, z, ws, B, Ty, cond_flow, mask_y, reverse=True)      # z_p -> z, no copy
         cond_d = core._linear(g, core.dec_cond_w, core.dec_cond_b)
