@@ -260,6 +260,31 @@ size_t ov_wn_wino_pack_size(int rows, int cin, int K);
  * 0..5, group 1 points 0..4 and a zero; one zero record group closes the stream (HOST dst). */
 int ov_wn_wino_pack_f32(const float* w, int rows, int cin, int K, float* dst);
 
+/* The same layer (reference openvoice/modules.py:192-209, commons.py:100-107) on the bf16 matrix pipe
+ * (openvoice_amd/csrc/wn_layer_bf16.hip): the STATE stays fp32, only the matrix operands are rounded, each once, to the
+ * nearest even bf16:
+ *   x_in = in_layer_bf16(bf16(x)) + b_in + cond;  acts = bf16(tanh(x_in[:H]) * sigmoid(x_in[H:]))      fp32 sums and gate
+ *   rs   = res_skip_layer_bf16(acts) + b_rs;      out = (x + rs[:H]) * mask with the UNROUNDED x;  skip (+)= rs[H:]
+ * Same parameter struct, layouts, argument rules, alignment rules, error codes and reads beyond column T as
+ * ov_wn_layer_f32 (a 16-byte vector of x / skip / mask is read iff its first column, a multiple of 4, is < T), except:
+ * w_in / w_rs point to BF16 data, ov_wn_bf16_pack of the dense fp32 weights described there (gate row order for w_in;
+ * the last layer's w_rs padded to 2H rows); dbg must be NULL (OV_E_BADARG); row_split / acts are ignored: always one
+ * launch, `acts` stays in LDS.  One workgroup per (utterance, tile of `width` = 16 .. 128 columns, 0 = chosen by
+ * ov_wn_layer_bf16_tile).  The value of an output element does not depend on the tile width, the tile index, B or the
+ * item's row (one fixed summation order: 32-channel chunk, then tap): bit-identical across all of them.  H = 192, K = 5
+ * only (OV_E_UNSUPPORTED otherwise).  (Added within 2.12: additive symbols.) */
+int ov_wn_layer_bf16(const ov_wn_layer_params* p, ov_stream_t stream);
+/* 1 for (hidden channels, taps) = (192, 5), else 0. */
+int ov_wn_layer_bf16_supported(int H, int K);
+/* bf16 elements written by ov_wn_bf16_pack (0 when rows % 128 or cin % 32). */
+size_t ov_wn_bf16_pack_size(int rows, int cin, int K);
+/* Dense HOST fp32 w[rows][cin][K] -> bf16 (nearest even, once) in 16x16x32 A-fragment order, [wave = rows / 8][k-step =
+ * (32-channel chunk, tap)][row fragment][lane][8 channels], one zero k-step closing each wave's stream (HOST dst). */
+int ov_wn_bf16_pack(const float* w, int rows, int cin, int K, uint16_t* dst);
+/* Tile width the launcher of ov_wn_layer_bf16 uses for (B, T) on the current device (width > 0: validated and returned;
+ * 0 = invalid). */
+int ov_wn_layer_bf16_tile(int B, int T, int width);
+
 /* Framing for the linear spectrogram, reference openvoice/mel_processing.py:54-58 (reflect pad) and the framing
  * step of torch.stft at :61-72: hops[b][c][u] = ypad[hop*u + c] for u < U, with ypad the waveform [B][N]
  * reflect-padded by `pad` samples on each side (zero beyond that).  hops is (B, hop, U) with rows ld apart.
@@ -845,7 +870,8 @@ int ov_conv1d_wino_pack_f32(const float* w, int Cout, int Cin, int K, float* dst
  * was `reserved`; the struct grew by one pointer at its end).  2.06: ov_polyphase_fir_f32.  2.07: ov_conv1d_wino_f32 (+ _supported, _chunk,
  * _pack_size, _pack_f32).  2.08: ov_conv1d_wino_f32 instances for Cout % 32 == 0 at K = 11 (one 32-row fragment per
  * workgroup; ov_conv1d_wino_chunk(11, 32) = 2 where 2.07 returned 0).  2.09: ov_conv1d_wino_params.out_slope (the field that
- * was `reserved0`: same size and offset, 0 = none).  2.10: ov_frame_hops_windows_f32, ov_stitch_window_cores_f32.  2.11: ov_frame_hops_multi_f32.  2.12: ov_carry_rows_f32 (and, added later within 2.12 without a version change, ov_polyphase_fir_rows_f32 and ov_vad_frame_energy_f32, ov_vad_segments_i32, ov_vad_compact_f32, ov_rows_f32_to_cl_bf16, ov_cl_bf16_to_rows_f32: additive symbols, which the Python binding looks up by name when it loads the library; likewise ov_wn_layer_wino_f32, ov_wn_layer_wino_tile, ov_wn_wino_pack_size and ov_wn_wino_pack_f32, and ov_join_segments_f32, and ov_pack_groups_cl_bf16 and ov_unpack_groups_f32).  The Python binding
+ * was `reserved0`: same size and offset, 0 = none).  2.10: ov_frame_hops_windows_f32, ov_stitch_window_cores_f32.  2.11: ov_frame_hops_multi_f32.  2.12: ov_carry_rows_f32 (and, added later within 2.12 without a version change, ov_polyphase_fir_rows_f32 and ov_vad_frame_energy_f32, ov_vad_segments_i32, ov_vad_compact_f32, ov_rows_f32_to_cl_bf16, ov_cl_bf16_to_rows_f32: additive symbols, which the Python binding looks up by name when it loads the library; likewise ov_wn_layer_wino_f32, ov_wn_layer_wino_tile, ov_wn_wino_pack_size and ov_wn_wino_pack_f32, and ov_join_segments_f32, and ov_pack_groups_cl_bf16 and ov_unpack_groups_f32, and ov_wn_layer_bf16, ov_wn_layer_bf16_supported,
+ * ov_wn_layer_bf16_tile, ov_wn_bf16_pack_size and ov_wn_bf16_pack).  The Python binding
  * refuses a library older than the entry points it calls (openvoice_amd/_lib.py MIN_VERSION). */
 int ov_version(void);
 /* The version THIS header describes.  Parameter structs grow at their END in minor versions (2.04, 2.05, 2.07 did): a

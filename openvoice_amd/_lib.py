@@ -141,6 +141,11 @@ SIGNATURES = {
     "ov_wn_layer_wino_tile": (ctypes.c_int, []),
     "ov_wn_wino_pack_size": (ctypes.c_size_t, [_i, _i, _i]),
     "ov_wn_wino_pack_f32": (ctypes.c_int, [_fp, _i, _i, _i, _fp]),
+    "ov_wn_layer_bf16": (ctypes.c_int, [ctypes.POINTER(WnLayerParams), _fp]),
+    "ov_wn_layer_bf16_supported": (ctypes.c_int, [_i, _i]),
+    "ov_wn_bf16_pack_size": (ctypes.c_size_t, [_i, _i, _i]),
+    "ov_wn_bf16_pack": (ctypes.c_int, [_fp, _i, _i, _i, _fp]),
+    "ov_wn_layer_bf16_tile": (ctypes.c_int, [_i, _i, _i]),
     "ov_conv_post_tanh_f32": (ctypes.c_int, [_fp, _fp, _fp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                              ctypes.c_int, ctypes.c_float, _fp]),
     "ov_conv_post_tanh_limited_f32": (ctypes.c_int, [_fp, _fp, _fp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -239,6 +244,25 @@ def generator_kw(generator):
     return {} if generator is None else {"generator": generator}
 
 
+WAVENETS = ("fp32", "bf16")
+
+
+def check_wavenet(wavenet, optional=False):
+    """The ``wavenet=`` keyword of the same entry points: the kernels of the posterior encoder's and the flow's WaveNet
+    layers, ``"fp32"`` or ``"bf16"`` (and None where ``optional``: follow the engine's ``use_bf16_wavenet`` switch);
+    anything else is an ``OvError``.  Independent of ``generator=``."""
+    if wavenet is None and optional:
+        return None
+    if not isinstance(wavenet, str) or wavenet not in WAVENETS:
+        raise OvError(f"wavenet must be 'fp32' or 'bf16'{' (or None)' if optional else ''}, got {wavenet!r}")
+    return wavenet
+
+
+def wavenet_kw(wavenet):
+    """``{"wavenet": w}`` for a callee that takes the keyword, nothing when the caller left it at None."""
+    return {} if wavenet is None else {"wavenet": wavenet}
+
+
 def load():
     """Load (once) and return the ctypes handle; raises if the library was not built."""
     global _lib
@@ -290,7 +314,8 @@ VALUE_FUNCS = {"ov_version", "ov_build_experiment", "ov_conv1d_pack_size", "ov_c
                "ov_conv1d_bf16_pack_size", "ov_resblock_pair_supported", "ov_wn_layer_supported", "ov_wn_layer_tile",
                "ov_resblock_pair_bf16_supported", "ov_resblock_pair2_bf16_supported", "ov_conv1d_split3_pack_size",
                "ov_conv1d_split3_supported", "ov_conv1d_wino_supported", "ov_conv1d_wino_chunk", "ov_conv1d_wino_pack_size",
-               "ov_wn_layer_wino_tile", "ov_wn_wino_pack_size"}
+               "ov_wn_layer_wino_tile", "ov_wn_wino_pack_size", "ov_wn_layer_bf16_supported", "ov_wn_bf16_pack_size",
+               "ov_wn_layer_bf16_tile"}
 
 
 def binding():

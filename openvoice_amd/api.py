@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib, audio_io, longform, rates, utils
+from .engine import wavenet_keyword
 from . import noise as noise_mod
 from .mel_processing import spectrogram_torch
 from .models import SynthesizerTrn
@@ -141,6 +142,10 @@ class BaseSpeakerTTS(OpenVoiceBaseClass):
             raise ValueError(f"{name}: every value must be positive, got {vals}")
         return True, vals
 
+    def _wavenet_cores(self):
+        return self.model._wavenet_cores()
+
+    @wavenet_keyword
     @torch.no_grad()
     def infer_padded(self, id_sequences, speaker_id, speed=1.0, noise_scale=0.667, noise_scale_w=0.6, noise_w=None,
                      noise_z=None, *, seed=None, generator="fp32"):
@@ -194,6 +199,7 @@ class BaseSpeakerTTS(OpenVoiceBaseClass):
         """The keyword for ``infer``, left out for the default so that the fp32 call is today's call."""
         return {} if generator == "fp32" else {"generator": generator}
 
+    @wavenet_keyword
     @torch.no_grad()
     def tts_from_ids(self, id_sequences, speaker_id, speed=1.0, batched=False, noise_scale=0.667,
                      noise_scale_w=0.6, noise_w=None, noise_z=None, *, seed=None, generator="fp32"):
@@ -256,6 +262,7 @@ class BaseSpeakerTTS(OpenVoiceBaseClass):
             ids.append(self.get_text(t, self.hps, False))
         return ids
 
+    @wavenet_keyword
     def tts(self, text, output_path, speaker, language="English", speed=1.0, batched=False, *, seed=None,
             generator="fp32"):
         """reference: openvoice/api.py:73-98.  ``seed``: as for ``tts_from_ids`` (sentence ``i`` on stream ``(seed,
@@ -468,6 +475,10 @@ class ToneColorConverter(OpenVoiceBaseClass):
         se = (acc / torch.tensor(counts, dtype=torch.float32).to(g.device)[:, None]).unsqueeze(-1).detach()
         return (se, g.detach()) if return_pieces else se
 
+    def _wavenet_cores(self):
+        return self.model._wavenet_cores()
+
+    @wavenet_keyword
     @torch.no_grad()
     def convert_batch(self, waveforms, src_se, tgt_se, tau=0.3, noise=None, *, seed=None):
         """Batched conversion, everything on the device.
@@ -550,6 +561,7 @@ class ToneColorConverter(OpenVoiceBaseClass):
             return out, torch.tensor(frames, dtype=torch.int64, device=self.device) * hop
         return out
 
+    @wavenet_keyword
     def convert(self, audio_src_path, src_se, tgt_se, output_path=None, tau=0.3, message="default", *, seed=None):
         """reference: openvoice/api.py:141-160.  A file at or beyond the one-pass launch limit
         (``longform.one_pass_limit_frames``: 63 551 frames = 12.3 min for the released configuration), which one pass
@@ -573,11 +585,11 @@ class ToneColorConverter(OpenVoiceBaseClass):
         audio_io.write(output_path, audio, hps.data.sampling_rate)
 
     # ---- recordings of any length (openvoice_amd/longform.py) -----------------------------------------------------------
-    def _windowed(self, window_frames, windows_per_launch=1):
+    def _windowed(self, window_frames, windows_per_launch=1, wavenet=None):
         d = self.hps.data
         return longform.WindowedConverter(self.model, n_fft=d.filter_length, hop=d.hop_length, window_frames=window_frames,
                                           windows_per_launch=windows_per_launch, graph=self.use_graphs,
-                                          model_sr=d.sampling_rate)
+                                          model_sr=d.sampling_rate, wavenet=wavenet)
 
     def _to_model_rate(self, audio_or_path, sr):
         """(device waveform at the model rate, its rate before resampling or None): a path is decoded and resampled on
@@ -600,6 +612,7 @@ class ToneColorConverter(OpenVoiceBaseClass):
             audio = audio_io.resample_on_device(torch.from_numpy(audio).to(self.device), msr, out_sr).cpu().numpy()
         return audio
 
+    @wavenet_keyword
     def convert_long(self, audio_or_path, src_se, tgt_se, output_path=None, tau=0.3, message="default",
                      window_frames=longform.DEFAULT_WINDOW_FRAMES, windows_per_launch=longform.DEFAULT_WINDOWS_PER_LAUNCH,
                      noise=None, sr=None, out_sr=None, *, seed=None):
@@ -623,7 +636,7 @@ class ToneColorConverter(OpenVoiceBaseClass):
         audio_io.write(output_path, audio, self.hps.data.sampling_rate if out_sr is None else out_sr)
 
     def stream(self, src_se, tgt_se, tau=0.3, window_frames=longform.DEFAULT_STREAM_WINDOW_FRAMES, noise=None, sr_in=None,
-               sr_out=None, *, seed=None):
+               sr_out=None, *, seed=None, wavenet=None):
         """A ``longform.ConversionStream``: ``push(samples)`` -> newly finished converted samples (device tensor, maybe
         empty), ``close()`` -> the rest, ``latency_samples`` = ``(window_frames - 1) * hop + n_fft - (n_fft - hop) / 2``
         at the model rate.  ``sr_in`` / ``sr_out``: the rate of the pushes / of the output (None: the model rate); the
@@ -633,28 +646,29 @@ class ToneColorConverter(OpenVoiceBaseClass):
         ``seed`` (stream ``(seed, 0)``, or a pair), which needs no length and keeps no noise tensor.  The
         output equals ``convert_long(..., windows_per_launch=1)`` of the whole input, bit for bit -- with rates, of the
         input resampled to the model rate, and resampled to ``sr_out`` after (``audio_io.resample_on_device``)."""
-        return self._windowed(window_frames, 1).stream(src_se, tgt_se, tau=tau, noise=noise, sr_in=sr_in, sr_out=sr_out,
+        return self._windowed(window_frames, 1, wavenet).stream(src_se, tgt_se, tau=tau, noise=noise, sr_in=sr_in, sr_out=sr_out,
                                                        **noise_mod.kw(seed))
 
     # ---- many streams and recordings in shared launches -------------------------------------------------------------
     def stream_pool(self, tau=0.3, window_frames=longform.DEFAULT_STREAM_WINDOW_FRAMES,
-                    max_windows_per_launch=longform.DEFAULT_POOL_WINDOWS_PER_LAUNCH):
+                    max_windows_per_launch=longform.DEFAULT_POOL_WINDOWS_PER_LAUNCH, *, wavenet=None):
         """A ``longform.StreamPool``: many live streams (``open(src_se, tgt_se, noise=None, sr_in=None, sr_out=None,
         seed=None)`` ->
         handle, ``push(h, samples)``, ``close(h)``), whose ready windows one ``step()`` converts together, up to
         ``max_windows_per_launch`` per launch -> ``{handle: newly finished samples}``; streams at rates of their own are
         resampled in one launch per direction and step.  Each stream's output equals a ``stream(...)`` fed the same
         samples with the same noise and rates.  One ``tau`` for the whole pool."""
-        return self._windowed(window_frames, 1).stream_pool(tau=tau, max_windows_per_launch=max_windows_per_launch)
+        return self._windowed(window_frames, 1, wavenet).stream_pool(tau=tau, max_windows_per_launch=max_windows_per_launch)
 
     # ---- low-latency live streams ------------------------------------------------------------------------------------
     def live_stream(self, src_se, tgt_se, tau=0.3, chunk_frames=15, noise=None, sr_in=None, sr_out=None,
-                    generator="fp32", *, seed=None):
+                    generator="fp32", *, seed=None, wavenet=None):
         """A ``live.LiveStream``: the conversion as a cascade of units that carry their recent input as state.
         ``push(samples)`` -> newly finished samples, ``close()`` -> the rest, ``latency_samples`` =
         ``live.live_latency_samples`` (1.45 s at 15 frames).  ``chunk_frames``: a positive multiple of 15 (the Winograd
         grid).  ``generator``: ``"fp32"`` (default) or ``"bf16"`` -- the kernels of the generator units of THIS stream
-        (posterior encoder and flow stay fp32; same latency and state); the engine-wide switches stay off (ValueError
+        (same latency and state); ``wavenet`` (keyword only): None follows ``use_bf16_wavenet``, ``"fp32"`` / ``"bf16"``
+        choose the WaveNet layers' kernels of the posterior-encoder and flow units of THIS stream; the engine-wide switches stay off (ValueError
         with use_bf16_generator / enable_split_bf16x3).  Never graph-captured.
         ``sr_in`` / ``sr_out``: the rate of the pushes / of the output (None: the model rate); ``latency_samples`` (in
         output samples) and ``latency_seconds`` then include the resamplers' waits (``rates.stream_latency``).  With
@@ -667,20 +681,24 @@ class ToneColorConverter(OpenVoiceBaseClass):
         d = self.hps.data
         return live.LiveStream(self.model, src_se, tgt_se, tau=tau, chunk_frames=chunk_frames, noise=noise,
                                n_fft=d.filter_length, hop=d.hop_length, sr_in=sr_in, sr_out=sr_out,
-                               model_sr=d.sampling_rate, generator=generator, **noise_mod.kw(seed))
+                               model_sr=d.sampling_rate, generator=generator, wavenet=wavenet, **noise_mod.kw(seed))
 
-    def live_pool(self, tau=0.3, chunk_frames=15, max_streams_per_launch=32, generator="fp32"):
+    def live_pool(self, tau=0.3, chunk_frames=15, max_streams_per_launch=32, generator="fp32", *, wavenet=None):
         """A ``live.LivePool``: many live streams (``open(src_se, tgt_se, noise=None, sr_in=None, sr_out=None,
         seed=None)`` /
         ``push`` / ``close``), every stream with a ready chunk converted by one ``step()`` in launches of up to
         ``max_streams_per_launch`` rows per unit; streams at rates of their own are resampled in one launch per direction
         and step.  Each stream equals its solo ``live_stream``.  One ``tau`` and one ``generator`` (``"fp32"`` or
-        ``"bf16"``) for the pool; pools of both kinds may be open on one converter at once."""
+        ``"bf16"``) for the pool; pools of both kinds may be open on one converter at once.  ``wavenet`` (keyword only):
+        the WaveNet layers' kernels of the pool's posterior-encoder and flow units, None (follow ``use_bf16_wavenet``),
+        ``"fp32"`` or ``"bf16"``."""
         from . import live
         d = self.hps.data
         return live.LivePool(self.model, tau=tau, chunk_frames=chunk_frames, max_streams_per_launch=max_streams_per_launch,
-                             n_fft=d.filter_length, hop=d.hop_length, model_sr=d.sampling_rate, generator=generator)
+                             n_fft=d.filter_length, hop=d.hop_length, model_sr=d.sampling_rate, generator=generator,
+                             wavenet=wavenet)
 
+    @wavenet_keyword
     def convert_many(self, items, src_se, tgt_se, tau=0.3, window_frames=longform.DEFAULT_WINDOW_FRAMES,
                      windows_per_launch=longform.DEFAULT_MANY_WINDOWS_PER_LAUNCH, noise=None, output_paths=None,
                      message="default", sr=None, out_sr=None, *, seed=None, generator=None):

@@ -28,6 +28,7 @@ speed per sentence.  The contract reads the same with that call as the public pi
 import numpy as np
 
 from . import _lib, longform, rates
+from .engine import wavenet_keyword
 
 RECORD_FIELDS = 4           # ov_join_segments_f32's record: (src_off, n, dst_off, gap)
 MAX_RECORDS = 65535
@@ -258,6 +259,11 @@ class VoiceCloner:
         self.last_launches = {"infer": len(batches), "join": len(batches)}
         return [dst[b:b + t] for b, t in zip(bases, totals)]
 
+    def _wavenet_cores(self):
+        """Both halves of the chain: the TTS model's flow and the converter's posterior encoder and flow."""
+        return tuple(self.tts._wavenet_cores()) + tuple(self.converter._wavenet_cores())
+
+    @wavenet_keyword
     def speak_ids_many(self, requests, tau=0.3, noise_w=None, noise_z=None, noise=None, output_paths=None,
                        message="default", window_frames=longform.DEFAULT_WINDOW_FRAMES,
                        windows_per_launch=longform.DEFAULT_MANY_WINDOWS_PER_LAUNCH,

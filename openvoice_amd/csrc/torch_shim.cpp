@@ -293,6 +293,12 @@ void wn_layer_wino_f32(const OptTensor& x, const OptTensor& out, const OptTensor
   wn_layer_any<&ov_wn_layer_wino_f32>("wn_layer_wino_f32", "ov_wn_layer_wino_f32", x, out, skip, w_in, b_in, cond, w_rs, b_rs, mask, dbg,
                                       acts, ip);
 }
+// the same layer on the bf16 matrix pipe: same arguments (w_in / w_rs = ov_wn_bf16_pack data viewed as float32)
+void wn_layer_bf16(const OptTensor& x, const OptTensor& out, const OptTensor& skip, const OptTensor& w_in,
+                   const OptTensor& b_in, const OptTensor& cond, const OptTensor& w_rs, const OptTensor& b_rs,
+                   const OptTensor& mask, const OptTensor& dbg, const OptTensor& acts, at::IntArrayRef ip) {
+  wn_layer_any<&ov_wn_layer_bf16>("wn_layer_bf16", "ov_wn_layer_bf16", x, out, skip, w_in, b_in, cond, w_rs, b_rs, mask, dbg, acts, ip);
+}
 
 // ip = [B, L, Cin, Cout, K, dil, phase_s, bias_bstride, layout];  fp = [in_slope, scale, out_slope]
 void conv1d_bf16cl(const OptTensor& x, const OptTensor& w, const OptTensor& bias, const OptTensor& out,
@@ -428,6 +434,8 @@ TORCH_LIBRARY(openvoice_amd, m) {
         "Tensor? b_rs, Tensor? mask, Tensor(c!)? dbg, Tensor(d!)? acts, int[] ip) -> ()", &wn_layer_f32);
   m.def("wn_layer_wino_f32(Tensor? x, Tensor(a!)? out, Tensor(b!)? skip, Tensor? w_in, Tensor? b_in, Tensor? cond, Tensor? w_rs, "
         "Tensor? b_rs, Tensor? mask, Tensor(c!)? dbg, Tensor(d!)? acts, int[] ip) -> ()", &wn_layer_wino_f32);
+  m.def("wn_layer_bf16(Tensor? x, Tensor(a!)? out, Tensor(b!)? skip, Tensor? w_in, Tensor? b_in, Tensor? cond, Tensor? w_rs, "
+        "Tensor? b_rs, Tensor? mask, Tensor(c!)? dbg, Tensor(d!)? acts, int[] ip) -> ()", &wn_layer_bf16);
   m.def("conv1d_bf16cl(Tensor? x, Tensor? w, Tensor? bias, Tensor(a!)? out, Tensor? res, Tensor? add, Tensor(b!)? dbg, "
         "int[] ip, float[] fp) -> ()", &conv1d_bf16cl);
   m.def("resblock_pair_bf16cl(Tensor? x, Tensor? w1, Tensor? b1, Tensor? w2, Tensor? b2, Tensor(a!)? out, Tensor? add, "
@@ -492,6 +500,10 @@ TORCH_LIBRARY(openvoice_amd, m) {
   bind_host<&ov_wn_wino_pack_f32>(m, "wn_wino_pack_f32");
   bind_value<&ov_wn_wino_pack_size>(m, "wn_wino_pack_size");
   bind_value<&ov_wn_layer_wino_tile>(m, "wn_layer_wino_tile");
+  bind_host<&ov_wn_bf16_pack>(m, "wn_bf16_pack");
+  bind_value<&ov_wn_bf16_pack_size>(m, "wn_bf16_pack_size");
+  bind_value<&ov_wn_layer_bf16_supported>(m, "wn_layer_bf16_supported");
+  bind_value<&ov_wn_layer_bf16_tile>(m, "wn_layer_bf16_tile");
   bind_host<&ov_conv1d_bf16_pack>(m, "conv1d_bf16_pack");
   bind_host<&ov_conv1d_bf16_pack16>(m, "conv1d_bf16_pack16");
   bind_host<&ov_conv1d_split3_pack>(m, "conv1d_split3_pack");

@@ -10,7 +10,9 @@ Reference path being replaced: SynthesizerTrn.voice_conversion (openvoice/models
 PosteriorEncoder (models.py:212-221) -> ResidualCouplingBlock forward with g_src and reverse with
 g_tgt (models.py:390-397) -> Generator (models.py:272-291).
 """
+import contextlib
 import ctypes
+import functools
 import os
 
 import torch
@@ -93,6 +95,25 @@ def on_own_device(method):
             dev = (getattr(self, "engine", None) or kwargs.get("engine") or args[0]).device
         with torch.cuda.device(dev):
             return method(self, *args, **kwargs)
+    return wrapper
+
+
+def wavenet_keyword(method):
+    """Gives a public method the keyword-only ``wavenet=None | "fp32" | "bf16"``: the kernels of the WaveNet layers of
+    the posterior encoder and the flow for the launches the call issues (``ConverterEngine.wavenet_scope`` on every
+    engine of ``self._wavenet_cores()``).  None follows ``use_bf16_wavenet``; a string chooses for this call without
+    touching the switch; anything else is an ``OvError``.  Independent of ``generator=``."""
+    @functools.wraps(method)
+    def wrapper(self, *args, wavenet=None, **kwargs):
+        if _lib.check_wavenet(wavenet, optional=True) is None:
+            return method(self, *args, **kwargs)          # the default: today's call, nothing looked up
+        with contextlib.ExitStack() as stack:
+            for core in self._wavenet_cores():
+                stack.enter_context(core.wavenet_scope(wavenet))
+            return method(self, *args, **kwargs)
+    wrapper.__doc__ = (method.__doc__ or "") + ("\n        ``wavenet`` (keyword only): None follows ``use_bf16_wavenet``; "
+                                               "``\"fp32\"`` / ``\"bf16\"`` choose the WaveNet layers' kernels for this call "
+                                               "(``engine.wavenet_keyword``).")
     return wrapper
 
 
@@ -379,6 +400,18 @@ def wn_pack(w_dense, device):
     return packed.to(device)
 
 
+def wn_bf16_pack(w_dense, device):
+    """Dense fp32 [rows][cin][K] -> bf16 (nearest even) in the 16x16x32 fragment order of ``ov_wn_bf16_pack``: a device
+    tensor of bf16 data VIEWED as float32 (``ov_wn_layer_params.w_in`` / ``w_rs`` are ``const float*`` fields)."""
+    w_dense = w_dense.detach().to(torch.float32).cpu().contiguous()
+    rows, cin, k = w_dense.shape
+    n = _lib.call("ov_wn_bf16_pack_size", rows, cin, k)
+    assert n > 0 and n % 2 == 0, (rows, cin, k)
+    packed = torch.empty(n, dtype=torch.bfloat16)
+    _lib.call("ov_wn_bf16_pack", w_dense, rows, cin, k, packed)
+    return packed.view(torch.float32).to(device)
+
+
 # The Winograd-domain layer (csrc/wn_layer_wino.hip) deals (utterance, 128-column tile) items to one workgroup per CU, in
 # rounds of one item per CU, and a round costs what a full one costs (168 us per layer on 256 CUs); the direct layer
 # (csrc/wn_layer.hip) chooses tiles of 16 .. 128 columns that fill the CUs whatever the batch and costs 0.9-1.0 us per 128
@@ -415,22 +448,27 @@ def wn_wino_pack(w_dense, device):
 
 
 def launch_wn_layer(layer, x, out, skip, mask, B, T, ld, cond=None, cond_off=0, cond_bs=0, first=False, last=False,
-                    width=0, mask_bs=0, dbg=None, acts=None, row_split=0, winograd=False):
+                    width=0, mask_bs=0, dbg=None, acts=None, row_split=0, winograd=False, bf16=False):
     """One fused WaveNet layer (``ov_wn_layer_f32``): out = (x + res) * mask, skip (+)= rs; ``layer`` is a dict of
     the packed tensors built by ``_WaveNet``; x / out / skip are [B][H][ld].  ``acts`` ([B][H][ld] scratch) lets the
     launcher run one or two utterances as the row-split launch pair (bit-identical results); ``row_split`` 1 / 3 force
     the fused / the split form.  ``winograd``: the same layer with its gate conv in the Winograd domain
-    (``ov_wn_layer_wino_f32``, ``layer["w_in_wino"]``; one launch, 128-column tiles)."""
+    (``ov_wn_layer_wino_f32``, ``layer["w_in_wino"]``; one launch, 128-column tiles).  ``bf16``: the same layer with its
+    matrix operands rounded to bf16 and the state kept fp32 (``ov_wn_layer_bf16``, ``layer["w_in_bf16"]`` /
+    ``layer["w_rs_bf16"]``; one launch; ``acts`` / ``row_split`` / ``winograd`` are ignored)."""
     entry, w_in = ("wn_layer_wino_f32", layer["w_in_wino"]) if winograd else ("wn_layer_f32", layer["w_in"])
+    w_rs = layer["w_rs"]
+    if bf16:
+        entry, w_in, w_rs, acts, row_split = "wn_layer_bf16", layer["w_in_bf16"], layer["w_rs_bf16"], None, 0
     if _lib.use_torch_binding():
         H = layer["hidden"]
-        _lib.torch_op(entry, x, out, skip, w_in, layer["b_in"], cond, layer["w_rs"], layer["b_rs"],
+        _lib.torch_op(entry, x, out, skip, w_in, layer["b_in"], cond, w_rs, layer["b_rs"],
                       mask, dbg, acts, [B, H, T, ld, layer["K"], int(first), int(last), width, H * ld, cond_bs, mask_bs,
                                         cond_off, row_split])
         return
     p = _lib.WnLayerParams()
     p.x, p.out, p.skip = _ptr(x), _ptr(out), _ptr(skip)
-    p.w_in, p.b_in, p.w_rs, p.b_rs = _ptr(w_in), _ptr(layer["b_in"]), _ptr(layer["w_rs"]), _ptr(layer["b_rs"])
+    p.w_in, p.b_in, p.w_rs, p.b_rs = _ptr(w_in), _ptr(layer["b_in"]), _ptr(w_rs), _ptr(layer["b_rs"])
     p.cond = _ptr(cond, cond_off) if cond is not None else None
     p.mask = _ptr(mask)
     H = layer["hidden"]
@@ -451,6 +489,7 @@ class _WaveNet:
         order = gate_row_order(hidden)
         self.hidden, self.n_layers = hidden, n_layers
         self.in_layers, self.rs_layers, self.fused_layers = [], [], []
+        self.device, self._sd, self._prefix = device, sd, prefix      # a reference: bf16_layers() derives its weights from it
         K = sd[f"{prefix}.in_layers.0.weight_v"].shape[2] if f"{prefix}.in_layers.0.weight_v" in sd else \
             sd[f"{prefix}.in_layers.0.weight"].shape[2]
         self.fused = bool(_lib.call("ov_wn_layer_supported", hidden, K))
@@ -480,6 +519,22 @@ class _WaveNet:
             full = torch.cat([forder + 2 * hidden * i for i in range(n_layers)])
             self.cond_w_fused = wc[full].contiguous().to(device)
             self.cond_b_fused = bc[full].contiguous().to(device)
+
+    def bf16_layers(self):
+        """The fused layers with ``w_in_bf16`` / ``w_rs_bf16`` (``ov_wn_bf16_pack``), packed on first use -- as
+        ``ConverterEngine.bf16_generator`` builds its weights -- from the same gate row order as the fp32 packing."""
+        if not (self.fused and _lib.call("ov_wn_layer_bf16_supported", self.hidden, self.fused_layers[0]["K"])):
+            raise _lib.OvError(f"no bf16 WaveNet layer kernel for hidden = {self.hidden}: a missing kernel is an error")
+        if "w_in_bf16" not in self.fused_layers[0]:
+            forder = wn_fused_row_order(self.hidden)
+            for i, layer in enumerate(self.fused_layers):
+                w_rs = effective_weight(self._sd, f"{self._prefix}.res_skip_layers.{i}")
+                if w_rs.shape[0] == self.hidden:      # last layer: skip rows only, padded as for the fp32 packing
+                    w_rs = torch.cat([torch.zeros_like(w_rs), w_rs])
+                layer["w_in_bf16"] = wn_bf16_pack(effective_weight(self._sd, f"{self._prefix}.in_layers.{i}")[forder],
+                                                  self.device)
+                layer["w_rs_bf16"] = wn_bf16_pack(w_rs, self.device)
+        return self.fused_layers
 
 
 def multi_launch_scratch_buffers(cfg):
@@ -624,6 +679,9 @@ class ConverterEngine:
         self._state_dict_for_bf16 = sd
         self.generator_bf16 = None
         self._bf16_on = False
+        # opt-in: the WaveNet layers of the posterior encoder and of the flow on the bf16 matrix pipe with fp32 state
+        # (ov_wn_layer_bf16).  _wn_choice: a call's own wavenet= while it runs (wavenet_scope).
+        self._wn_bf16_on, self._wn_choice = False, None
         # opt-in split-precision MRF stages: fp32-level products on the bf16 matrix pipe
         self._split3_on = False
         self.split3_products = 6
@@ -749,6 +807,21 @@ class ConverterEngine:
         whose own epilogue multiplies by the same 0/1 mask, which makes it a no-op."""
         H, Tp = wn.hidden, ws["Tp"]
         cbs = 0 if cond.shape[0] == 1 else cond.shape[1]
+        if self.wavenet_bf16():
+            # every layer of the stack as one ov_wn_layer_bf16 launch; use_winograd / wn_wino_policy / wn_row_split do not
+            # apply.  The cond rows are in the fused gate order (_wn_cond), which this kernel shares.
+            if not self.fuse_wn:
+                raise _lib.OvError("wavenet='bf16' runs the fused layer kernel: fuse_wn must be on")
+            layers = wn.bf16_layers()
+            src, dst = ws["h"], ws["h2"]
+            for i in range(wn.n_layers):
+                layer, last = layers[i], i == wn.n_layers - 1
+                self._timed("wn_layer_bf16", 2.0 * (2 * H * H * layer["K"] + (H if last else 2 * H) * H) * T * B,
+                            lambda: launch_wn_layer(layer, src, dst, ws["skip"], mask, B, T, Tp, cond=cond,
+                                                    cond_off=2 * H * i, cond_bs=cbs, first=i == 0, last=last,
+                                                    mask_bs=Tp, bf16=True))
+                src, dst = dst, src
+            return
         if self.fuse_wn and wn.fused:
             # one launch per layer; h ping-pongs between two buffers (a tile reads its neighbours' halo columns)
             src, dst = ws["h"], ws["h2"]
@@ -789,11 +862,14 @@ class ConverterEngine:
                        mask_bs=Tp, x_ld=Tp, out_ld=Tp, scale=-1.0 if reverse else 1.0, tag="cpl_post",
                        res=src if n < 2 else None, res_off=x1_off, res_bs=C * Tp)
 
+    def _wavenet_cores(self):
+        return (self,)
+
     # ---- the path ----------------------------------------------------------------------------------
     @torch.no_grad()
     @on_own_device
     def voice_conversion(self, spec, spec_lengths, sid_src, sid_tgt, tau=1.0, noise=None, skip_padding=False, *,
-                         seed=None, generator=None):
+                         seed=None, generator=None, wavenet=None):
         """Same contract as the reference seam (openvoice/models.py:492-499):
         ``(o_hat [B,1,256T], y_mask [B,1,T], (z, z_p, z_hat) [B,192,T])``.  ``noise`` [B,192,T]
         replaces the reference's ``torch.randn_like`` draw (models.py:220); when omitted it is drawn
@@ -807,10 +883,16 @@ class ConverterEngine:
         computation, and everything beyond them in ``o_hat`` is zero instead of the reference's bias-driven junk.
         ``generator``: None follows the ``use_bf16_generator`` switch; ``"fp32"`` / ``"bf16"`` choose the generator's
         kernels for this call, whatever the switch says and without touching it (the bf16 generator is built on first
-        use, as for a bf16 live pool)."""
+        use, as for a bf16 live pool).  ``wavenet``: the same for the WaveNet layers of the posterior encoder and of the
+        flow -- None follows ``use_bf16_wavenet``, ``"fp32"`` / ``"bf16"`` choose for this call (``ov_wn_layer_bf16``:
+        bf16 matrix operands, fp32 state); independent of ``generator``."""
         use_bf16 = self._bf16_on
         if _lib.check_generator(generator, optional=True) is not None:
             use_bf16 = generator == "bf16"
+        with self.wavenet_scope(wavenet):
+            return self._voice_conversion(spec, spec_lengths, sid_src, sid_tgt, tau, noise, skip_padding, seed, use_bf16)
+
+    def _voice_conversion(self, spec, spec_lengths, sid_src, sid_tgt, tau, noise, skip_padding, seed, use_bf16):
         dev = self.device
         spec = spec.to(dev, torch.float32)
         B, F, T = spec.shape
@@ -839,6 +921,7 @@ class ConverterEngine:
         # (measured and dropped: issuing this part -- ~100 launches of <= 1.3 tiles per workgroup slot -- as 2 / 4
         # independent sub-batch chains on separate HIP streams, so that one chain's tiles would fill the other's
         # launch tails, takes 16.1 / 14.0 ms instead of 12.1 ms: profiles/r02_s7_frame_streams_ab.txt)
+        # Its 48 WaveNet layers run the fp32 kernels unless wavenet= / use_bf16_wavenet chooses ov_wn_layer_bf16 (_wavenet).
         self._frames(ws, 0, B, spec, conds, tau)
         z, z_p, z_hat = ws["z"], ws["z_p"], ws["z_hat"]
         # ---- generator (models.py:272-291); z_hat * y_mask is the identity (z_hat already masked) --
@@ -891,15 +974,45 @@ class ConverterEngine:
         """``voice_conversion`` for one fixed (B, T, tau) as a captured HIP graph (see ``GraphedConversion``);
         the most recent ``max_cached`` shapes stay resident."""
         key = (int(B), int(T), float(tau), int(src_rows), int(tgt_rows), self._bf16_on,
-               bool(skip_padding), bool(self._split3_on), self.split3_products)
+               bool(skip_padding), bool(self._split3_on), self.split3_products, self.wavenet_bf16())
         cache = self._graphs
         g = cache.pop(key, None)
         if g is None:
-            g = GraphedConversion(self, B, T, tau, src_rows, tgt_rows, skip_padding=skip_padding)
+            g = GraphedConversion(self, B, T, tau, src_rows, tgt_rows, skip_padding=skip_padding,
+                                  wavenet="bf16" if key[-1] else "fp32")
             while len(cache) >= max_cached:
                 cache.pop(next(iter(cache)))
         cache[key] = g     # re-inserted last: the dict is the LRU order
         return g
+
+    def use_bf16_wavenet(self, enable=True):
+        """Run every WaveNet layer of the posterior encoder and of both flow passes on ``ov_wn_layer_bf16``: bf16 matrix
+        operands, fp32 state.  Off by default: the fp32 layers are the ones held to the 1e-3
+        parity bar.  Independent of ``use_bf16_generator``; a call's ``wavenet=`` overrides it for that call."""
+        self._wn_bf16_on = bool(enable)
+        self._graphs.clear()                      # captured graphs hold the other path's launches
+        return self
+
+    def wavenet_bf16(self):
+        """True where a WaveNet stack launched NOW runs the bf16 layers: the running call's ``wavenet=`` if it gave one,
+        else the ``use_bf16_wavenet`` switch."""
+        return self._wn_bf16_on if self._wn_choice is None else self._wn_choice == "bf16"
+
+    @contextlib.contextmanager
+    def wavenet_scope(self, wavenet):
+        """``wavenet=`` of one call: None follows the switch; ``"fp32"`` / ``"bf16"`` choose for the launches issued
+        inside the ``with`` block without touching the switch (anything else: ``OvError``).  Scopes nest: an inner None
+        keeps the outer choice.  The choice is state of THIS engine while the block runs, like its workspaces and its
+        other switches: not re-entrant -- two threads, or two interleaved callers, on one engine would see each other's
+        choice (an engine serves one caller at a time; streams and pools re-enter their own scope at every launch)."""
+        if _lib.check_wavenet(wavenet, optional=True) is None:
+            yield self
+            return
+        saved, self._wn_choice = self._wn_choice, wavenet
+        try:
+            yield self
+        finally:
+            self._wn_choice = saved
 
     def use_bf16_generator(self, enable=True):
         """Route ``voice_conversion``'s generator through the bf16 kernels (BASELINE.json configs[4]).  Off by
@@ -1463,7 +1576,7 @@ class GraphedConversion:
     this shape is pinned for the life of the graph.  Reference contract unchanged: openvoice/models.py:492-499."""
 
     @on_own_device
-    def __init__(self, engine, B, T, tau, src_rows=1, tgt_rows=1, skip_padding=False):
+    def __init__(self, engine, B, T, tau, src_rows=1, tgt_rows=1, skip_padding=False, wavenet=None):
         dev = engine.device
         self.engine, self.B, self.T, self.tau = engine, int(B), int(T), float(tau)
         f = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
@@ -1472,7 +1585,7 @@ class GraphedConversion:
         self.g_src, self.g_tgt = f(src_rows, engine.gin, 1), f(tgt_rows, engine.gin, 1)
         self.noise = f(B, engine.inter, T)
         run = lambda: engine.voice_conversion(self.spec, self.lengths, self.g_src, self.g_tgt, tau=self.tau,
-                                              noise=self.noise, skip_padding=skip_padding)
+                                              noise=self.noise, skip_padding=skip_padding, **_lib.wavenet_kw(wavenet))
         saved, engine.profile = engine.profile, None       # event records are not capturable
         try:
             side = torch.cuda.Stream(dev)                      # torch's rule: warm up off the default stream

@@ -32,7 +32,8 @@ step first resamples the new input of every such stream to the model rate in one
 resamples every stream's new output in one more launch.
 
 ``generator="bf16"`` (pool or stream) runs the ``g`` units on the bf16 channels-last generator (``bf16.GeneratorBf16``)
-instead of the fp32 kernels; ``q``, ``f`` and ``r`` stay fp32.  The cascade, the reaches, the arena and the carries are
+instead of the fp32 kernels; ``q``, ``f`` and ``r`` keep their fp32 kernels (``wavenet="bf16"``
+chooses their WaveNet layers separately).  The cascade, the reaches, the arena and the carries are
 the same -- state stays fp32 channels-first -- so each ``g`` unit changes layout on the way in
 (``ov_rows_f32_to_cl_bf16``) and on the way out (``ov_cl_bf16_to_rows_f32``; the last stage writes fp32 itself).  What
 one stage hands the next is a bf16 value held in fp32, so the arena adds no rounding: the stream computes the one-pass
@@ -270,13 +271,18 @@ class LivePool:
     rounds and its end run narrower), padded up to the ``launch_ladder`` sizes.  ``tau`` is one scalar for the pool.
     Live units run eagerly, never from a captured graph.  ``generator``: ``"fp32"`` (default) or ``"bf16"`` -- the
     kernels of the ``g`` units (module docstring); everything else, the latency and the state size included, is the
-    same for both."""
+    same for both.  ``wavenet``: None (follow ``ConverterEngine.use_bf16_wavenet``), ``"fp32"`` or ``"bf16"`` -- the
+    WaveNet layers of the ``q`` / ``f`` / ``r`` units on ``ov_wn_layer_bf16`` (bf16 matrix operands, fp32 state); the
+    layer's results do not depend on tile, row or batch, so a stream still equals the one-pass conversion with the same
+    keyword."""
 
     def __init__(self, model, tau=0.3, chunk_frames=DEFAULT_CHUNK_FRAMES,
                  max_streams_per_launch=DEFAULT_LIVE_STREAMS_PER_LAUNCH, n_fft=1024, hop=256, model_sr=rates.MODEL_RATE,
-                 generator="fp32"):
+                 generator="fp32", wavenet=None):
         self.model, self.tau = model, float(tau)
         self.generator = check_generator(generator)
+        # the WaveNet layers' kernels of the q / f / r units: None follows the engine's use_bf16_wavenet switch
+        self.wavenet = _lib.check_wavenet(wavenet, optional=True)
         self.cfg = model.model_cfg
         self.chunk = check_chunk(self.cfg, chunk_frames)
         eng = model.engine()
@@ -545,6 +551,10 @@ class LivePool:
                 self._carry(recs)
 
     def _launch(self, k, rows, B, L):
+        with self.engine.wavenet_scope(self.wavenet):
+            self._launch_unit(k, rows, B, L)
+
+    def _launch_unit(self, k, rows, B, L):
         u, eng, mem = self.units[k], self.engine, self.mem
         bf16 = u["kind"] == "g" and self.generator == "bf16"
         ws = (eng.live_workspace_bf16 if bf16 else eng.live_workspace)((u["name"], self.width[k]), B, self.width[k],
@@ -659,10 +669,10 @@ class LiveStream:
     the model rate).  ``generator``: as for ``LivePool``."""
 
     def __init__(self, model, src_se, tgt_se, tau=0.3, chunk_frames=DEFAULT_CHUNK_FRAMES, noise=None, n_fft=1024,
-                 hop=256, sr_in=None, sr_out=None, model_sr=rates.MODEL_RATE, generator="fp32", seed=None):
+                 hop=256, sr_in=None, sr_out=None, model_sr=rates.MODEL_RATE, generator="fp32", seed=None, wavenet=None):
         noise_mod.exclusive(seed, noise=noise)
         self._pool = LivePool(model, tau=tau, chunk_frames=chunk_frames, max_streams_per_launch=1, n_fft=n_fft, hop=hop,
-                              model_sr=model_sr, generator=generator)
+                              model_sr=model_sr, generator=generator, wavenet=wavenet)
         self._h = self._pool.open(src_se, tgt_se, noise=noise, sr_in=sr_in, sr_out=sr_out, **noise_mod.kw(seed))
         self.latency_seconds, self.latency_samples = self._pool.latency_of(self._h)
         self._closed = False

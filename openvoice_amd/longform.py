@@ -24,6 +24,7 @@ import math
 import torch
 
 from . import _lib, rates
+from .engine import wavenet_keyword
 from . import noise as noise_mod
 from .generator import GENERATOR_MARGIN, generator_margin_frames, generator_stages, samples_per_frame
 from .params import ENC_Q_KERNEL, ENC_Q_LAYERS, FLOW_KERNEL, FLOW_LAYERS, N_FLOWS
@@ -158,8 +159,11 @@ class WindowedConverter:
     captures at most three shapes: full batches, the last partial batch, and the single-window case)."""
 
     def __init__(self, model, n_fft=1024, hop=256, window_frames=DEFAULT_WINDOW_FRAMES,
-                 windows_per_launch=DEFAULT_WINDOWS_PER_LAUNCH, graph=False, model_sr=rates.MODEL_RATE):
+                 windows_per_launch=DEFAULT_WINDOWS_PER_LAUNCH, graph=False, model_sr=rates.MODEL_RATE, wavenet=None):
         self.model = model
+        # the WaveNet layers' kernels of every launch of THIS converter (its streams and pools included): None follows
+        # the engine's use_bf16_wavenet switch or the running call's wavenet=
+        self.wavenet = _lib.check_wavenet(wavenet, optional=True)
         self.model_sr = int(model_sr)
         self.cfg = model.model_cfg
         self.n_fft, self.hop, self.pad = int(n_fft), int(hop), (int(n_fft) - int(hop)) // 2
@@ -189,7 +193,7 @@ class WindowedConverter:
         spec = self._spectrogram().windows(wave, n_samples, firsts_dev, Tw)
         lengths = torch.full((W,), Tw, dtype=torch.int64, device=wave.device)
         o_hat = self.model.voice_conversion(spec, lengths, sid_src=src_se, sid_tgt=tgt_se, tau=tau, noise=nz,
-                                            graph=self.graph, **noise_mod.kw(seed))[0]
+                                            graph=self.graph, **noise_mod.kw(seed), **_lib.wavenet_kw(self.wavenet))[0]
         _lib.call("ov_stitch_window_cores_f32", o_hat, plan_dev, W, Tw, self.spf, out, out.numel(), out_frame0)
 
     def _launch_multi(self, pool, records_dev, Tw, src_se, tgt_se, tau, nz, out, stitch_dev, n_out, seed=None,
@@ -202,7 +206,8 @@ class WindowedConverter:
         spec = self._spectrogram().windows_multi(pool, records_dev, Tw)
         lengths = torch.full((W,), Tw, dtype=torch.int64, device=pool.device)
         o_hat = self.model.voice_conversion(spec, lengths, sid_src=src_se, sid_tgt=tgt_se, tau=tau, noise=nz,
-                                            graph=self.graph, **noise_mod.kw(seed), **_lib.generator_kw(generator))[0]
+                                            graph=self.graph, **noise_mod.kw(seed), **_lib.generator_kw(generator),
+                                            **_lib.wavenet_kw(self.wavenet))[0]
         _lib.call("ov_stitch_window_cores_f32", o_hat, stitch_dev, n_out, Tw, self.spf, out, out.numel(), 0)
 
     def _run_jobs(self, sources, jobs, tau, out, max_windows, ladder=None, generator=None):
@@ -273,7 +278,11 @@ class WindowedConverter:
                 raise ValueError(f"noise must be [1, {self.inter}, >= {T}], got {tuple(noise.shape)}")
         return wave, T, noise
 
+    def _wavenet_cores(self):
+        return self.model._wavenet_cores()
+
     @torch.no_grad()
+    @wavenet_keyword
     def convert_many(self, waves, src_ses, tgt_ses, tau=0.3, noises=None, *, seeds=None, generator=None):
         """``convert`` of many recordings with their windows packed across recordings into launches of up to
         ``windows_per_launch`` (``ov_frame_hops_multi_f32``: each window framed from its own recording).  ``src_ses`` /
@@ -311,6 +320,7 @@ class WindowedConverter:
         return [out[o * self.spf:(o + T) * self.spf] for o, (_, T, _) in zip(offs, items)]
 
     @torch.no_grad()
+    @wavenet_keyword
     def convert(self, wave, src_se, tgt_se, tau=0.3, noise=None, *, seed=None):
         """``wave``: 1-D float32 waveform at the model rate (host or device).  ``noise``: ``[1, inter, >= T]`` or None
         (then ``torch.randn(1, inter, T)`` on the device: the stream of a seeded one-pass ``convert``); ``seed``

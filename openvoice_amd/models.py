@@ -14,7 +14,7 @@ from torch import nn
 
 from . import _lib
 from . import noise as noise_mod
-from .engine import ConverterEngine, validate_config
+from .engine import ConverterEngine, validate_config, wavenet_keyword
 from .params import converter_param_spec, tts_full_param_spec
 
 
@@ -98,6 +98,11 @@ class SynthesizerTrn(nn.Module):
             self._engine_key = key
         return self._engine
 
+    def _wavenet_cores(self):
+        eng = self.engine()
+        return (eng.core if self.n_speakers != 0 else eng,)
+
+    @wavenet_keyword
     def voice_conversion(self, y, y_lengths, sid_src, sid_tgt, tau=1.0, noise=None, graph=False, skip_padding=False, *,
                          seed=None, generator=None):
         """reference: openvoice/models.py:492-499; ``noise`` is the explicit form of the
@@ -142,6 +147,7 @@ class SynthesizerTrn(nn.Module):
             graph=graph)
         return conv.convert(y, sid_src, sid_tgt, tau=tau, noise=noise, **noise_mod.kw(seed)).view(1, 1, -1)
 
+    @wavenet_keyword
     def infer(self, x, x_lengths, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1., sdp_ratio=0.2,
               max_len=None, noise_w=None, noise_z=None, skip_padding=False, *, seed=None, generator="fp32"):
         """reference: openvoice/models.py:467-490; ``noise_w`` / ``noise_z`` are the explicit forms of the

@@ -23,7 +23,7 @@ import torch
 from . import _lib
 from . import noise as noise_mod
 from ._lib import F_MASK_V, LN_POST_GELU, LN_PRE_RELU
-from .engine import ConverterEngine, PackedConv, on_own_device, padded_frames
+from .engine import ConverterEngine, PackedConv, on_own_device, padded_frames, wavenet_keyword
 from .params import ATTN_WINDOW, SDP_DDS_LAYERS, SDP_FLOWS, SDP_KERNEL, SDP_NUM_BINS, SDP_TAIL_BOUND
 
 LN_EPS = 1e-5   # modules.LayerNorm / attentions.LayerNorm default
@@ -173,6 +173,10 @@ class TtsEngine:
                      flags=LN_POST_GELU)
 
     # ---- the path ----------------------------------------------------------------------------------------
+    def _wavenet_cores(self):
+        return (self.core,)
+
+    @wavenet_keyword
     @torch.no_grad()
     @on_own_device
     def infer(self, tokens, lengths, sid, noise_scale=1.0, length_scale=1.0, noise_scale_w=1.0, sdp_ratio=0.2,
