@@ -53,7 +53,7 @@ enum {
   OV_EPI_COUPLE = 3,
   /* posterior sample, reference openvoice/models.py:218-220 (rows paired like OV_EPI_GATE:
    * m = tile 2q, logs = tile 2q+1): out = (m*mask + res*scale*exp(logs*mask))*mask,
-   * res = noise, scale = tau                                                                   */
+   * res = noise, scale = tau (or, per batch item, scale_b[b])                                  */
   OV_EPI_POSTERIOR = 4,
   /* ConvTranspose1d (k = 2*phase_s, padding phase_s/2) written as a 3-tap conv over stride-many output phases,
    * reference openvoice/models.py:279 (weights packed with row = cout*phase_s + phase):
@@ -74,8 +74,10 @@ enum {
   OV_F_MASK_V = 1,    /* LINEAR: multiply v by mask[b][t] before the residual add */
   OV_F_OUT2_INIT = 2, /* RESSKIP: out2 = v instead of out2 += v (first WaveNet layer) */
   OV_F_CONVT_GROUPED = 4, /* CONVT, phase_s 8 / 2: rows packed by phase group (see OV_EPI_CONVT); M % 64 == 0 */
-  OV_F_NO_XCD_MAP = 8 /* measurement knob: walk the tile list round-robin over the workgroups instead of giving each
+  OV_F_NO_XCD_MAP = 8,/* measurement knob: walk the tile list round-robin over the workgroups instead of giving each
                        * XCD (workgroup id % 8) a contiguous eighth of it; results are identical either way */
+  OV_F_SCALE_B = 16   /* the struct has the trailing field scale_b (ov_conv1d_params): without this bit the library
+                       * does not read it, so a caller compiled against the struct that ended at reserved0 is safe */
 };
 
 /* One Conv1d launch.  Input length == output length L ('same' padding, stride 1), as every conv
@@ -128,6 +130,13 @@ typedef struct ov_conv1d_params {
   const int32_t* col_limit;
   int32_t col_limit_scale; /* columns of this launch per unit of col_limit (e.g. the stage's upsampling factor) */
   int32_t reserved0;
+  /* OV_EPI_POSTERIOR only, and read only when flags has OV_F_SCALE_B: one scale (tau) per batch item.  DEVICE
+   * pointer, fp32 [B], 4-byte aligned, or NULL.  Non-NULL: item b computes with scale_b[b] in place of `scale` -- the
+   * same expression in the same order, so item b holds the bits of a launch whose scalar `scale` is scale_b[b];
+   * `scale` is then ignored.  NULL (or no OV_F_SCALE_B): `scale`, as before the field existed.  Dense like col_limit,
+   * the other one-value-per-item vector (no stride: a launch over the items [b0, b1) of a larger batch passes
+   * scale_b + b0).  Every other epilogue ignores the field. */
+  const float* scale_b;
 } ov_conv1d_params;
 
 /* ---- host-side helpers -------------------------------------------------------------------- */
@@ -871,7 +880,9 @@ int ov_conv1d_wino_pack_f32(const float* w, int Cout, int Cin, int K, float* dst
  * _pack_size, _pack_f32).  2.08: ov_conv1d_wino_f32 instances for Cout % 32 == 0 at K = 11 (one 32-row fragment per
  * workgroup; ov_conv1d_wino_chunk(11, 32) = 2 where 2.07 returned 0).  2.09: ov_conv1d_wino_params.out_slope (the field that
  * was `reserved0`: same size and offset, 0 = none).  2.10: ov_frame_hops_windows_f32, ov_stitch_window_cores_f32.  2.11: ov_frame_hops_multi_f32.  2.12: ov_carry_rows_f32 (and, added later within 2.12 without a version change, ov_polyphase_fir_rows_f32 and ov_vad_frame_energy_f32, ov_vad_segments_i32, ov_vad_compact_f32, ov_rows_f32_to_cl_bf16, ov_cl_bf16_to_rows_f32: additive symbols, which the Python binding looks up by name when it loads the library; likewise ov_wn_layer_wino_f32, ov_wn_layer_wino_tile, ov_wn_wino_pack_size and ov_wn_wino_pack_f32, and ov_join_segments_f32, and ov_pack_groups_cl_bf16 and ov_unpack_groups_f32, and ov_wn_layer_bf16, ov_wn_layer_bf16_supported,
- * ov_wn_layer_bf16_tile, ov_wn_bf16_pack_size and ov_wn_bf16_pack).  The Python binding
+ * ov_wn_layer_bf16_tile, ov_wn_bf16_pack_size and ov_wn_bf16_pack; and ov_conv1d_params.scale_b, one pointer appended
+ * to the struct and read only under OV_F_SCALE_B, a flag no older caller sets: the version stays 212 and a caller built
+ * against the shorter struct stays binary compatible).  The Python binding
  * refuses a library older than the entry points it calls (openvoice_amd/_lib.py MIN_VERSION). */
 int ov_version(void);
 /* The version THIS header describes.  Parameter structs grow at their END in minor versions (2.04, 2.05, 2.07 did): a

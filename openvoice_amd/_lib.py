@@ -30,6 +30,7 @@ F_MASK_V = 1
 F_OUT2_INIT = 2
 F_CONVT_GROUPED = 4
 F_NO_XCD_MAP = 8      # measurement knob: round-robin tile order instead of XCD-contiguous (include/openvoice_amd.h)
+F_SCALE_B = 16        # ConvParams.scale_b is present and may be read (EPI_POSTERIOR: one tau per batch item)
 
 _fp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -53,6 +54,7 @@ class ConvParams(ctypes.Structure):
         ("chunk", ctypes.c_int32),
         ("in_slope", ctypes.c_float), ("scale", ctypes.c_float),
         ("col_limit", _fp), ("col_limit_scale", ctypes.c_int32), ("reserved0", ctypes.c_int32),
+        ("scale_b", _fp),       # read by the library only under F_SCALE_B
     ]
 
 

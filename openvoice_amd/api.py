@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib, audio_io, longform, rates, utils
-from .engine import wavenet_keyword
+from .engine import item_tau, wavenet_keyword
 from . import noise as noise_mod
 from .mel_processing import spectrogram_torch
 from .models import SynthesizerTrn
@@ -491,8 +491,12 @@ class ToneColorConverter(OpenVoiceBaseClass):
         differ from a per-utterance run (hard part 6); trim with the returned
         lengths.  ``seed`` (instead of ``noise``): counter-based noise (``openvoice_amd.noise``) -- an int ``s`` gives
         item ``b`` the stream ``(s, b)``, a list holds one seed or ``(seed, stream)`` pair per item; item ``b`` then
-        draws ``noise.normal((s, b), 192, 0, T)``, whatever the batch it is in."""
+        draws ``noise.normal((s, b), 192, 0, T)``, whatever the batch it is in.  ``tau``: one number, or one value per
+        waveform (a sequence, or a 1-D float32 device tensor; ``engine.item_tau``): item ``b`` is then converted with
+        ``tau[b]`` in the same launches, bit for bit what the batch gives with that number for all (a per-item ``tau``
+        runs eagerly: captured graphs are keyed on one ``tau``)."""
         noise_mod.exclusive(seed, noise=noise)
+        tau = item_tau(len(waveforms), tau)
         hop = self.hps.data.hop_length
         ragged = isinstance(waveforms, (list, tuple))
         if ragged:
@@ -531,8 +535,9 @@ class ToneColorConverter(OpenVoiceBaseClass):
         every rank receives the whole ``[N, 1, hop*T_max]`` batch (one all-gather), else ``(local_o_hat, (start,
         end))``.  ``noise`` [N, 192, T] is per utterance, so the result does not depend on the number of ranks.  For a
         list the return value is ``(o_hat, lengths_in_samples [N])`` as from ``convert_batch`` (every rank knows every
-        length, so the padded width is agreed on without a collective).  Without a process group this is
-        ``convert_batch``."""
+        length, so the padded width is agreed on without a collective).  ``tau``: one number, or one value per
+        utterance of the WHOLE batch, the same on every rank; rank r converts its utterances with its slice
+        (``parallel.convert_sharded(tau=...)``).  Without a process group this is ``convert_batch``."""
         from . import parallel
         gin = self.model.model_cfg["gin_channels"]
         d = self.hps.data
@@ -547,7 +552,9 @@ class ToneColorConverter(OpenVoiceBaseClass):
             frames = [frames_of(items.shape[1])] * len(items)
         width = max(frames) * hop                        # samples of the padded batch, the same on every rank
 
-        def convert(shard, s, t, nz):
+        tau = item_tau(len(items), tau)
+
+        def convert(shard, s, t, nz, tau):
             if len(shard) == 0:         # more ranks than utterances: an empty shard of the agreed width
                 return torch.zeros(0, 1, width, dtype=torch.float32, device=self.device)
             # (nz arrives cut to the shard's own longest length: parallel.convert_sharded(frames=...))
@@ -556,7 +563,7 @@ class ToneColorConverter(OpenVoiceBaseClass):
                 o = torch.nn.functional.pad(o, (0, width - o.shape[2]))
             return o
         out = parallel.convert_sharded(convert, items, src_se, tgt_se, gin, self.device, noise=noise, gather=gather,
-                                       frames=frames)
+                                       frames=frames, tau=tau)
         if ragged and gather:
             return out, torch.tensor(frames, dtype=torch.int64, device=self.device) * hop
         return out
@@ -657,7 +664,8 @@ class ToneColorConverter(OpenVoiceBaseClass):
         handle, ``push(h, samples)``, ``close(h)``), whose ready windows one ``step()`` converts together, up to
         ``max_windows_per_launch`` per launch -> ``{handle: newly finished samples}``; streams at rates of their own are
         resampled in one launch per direction and step.  Each stream's output equals a ``stream(...)`` fed the same
-        samples with the same noise and rates.  One ``tau`` for the whole pool."""
+        samples with the same noise and rates.  ``tau`` is the pool's default: ``open(..., tau=None)`` gives a stream its
+        own for life, and windows of streams with different ``tau`` still share launches (one value per launch row)."""
         return self._windowed(window_frames, 1, wavenet).stream_pool(tau=tau, max_windows_per_launch=max_windows_per_launch)
 
     # ---- low-latency live streams ------------------------------------------------------------------------------------
@@ -688,7 +696,9 @@ class ToneColorConverter(OpenVoiceBaseClass):
         seed=None)`` /
         ``push`` / ``close``), every stream with a ready chunk converted by one ``step()`` in launches of up to
         ``max_streams_per_launch`` rows per unit; streams at rates of their own are resampled in one launch per direction
-        and step.  Each stream equals its solo ``live_stream``.  One ``tau`` and one ``generator`` (``"fp32"`` or
+        and step.  Each stream equals its solo ``live_stream``.  ``tau`` is the pool's default: ``open(..., tau=None)``
+        gives a stream its own for life, and streams with different ``tau`` share the pool's launches (one value per
+        launch row).  One ``generator`` (``"fp32"`` or
         ``"bf16"``) for the pool; pools of both kinds may be open on one converter at once.  ``wavenet`` (keyword only):
         the WaveNet layers' kernels of the pool's posterior-encoder and flow units, None (follow ``use_bf16_wavenet``),
         ``"fp32"`` or ``"bf16"``."""
@@ -713,7 +723,9 @@ class ToneColorConverter(OpenVoiceBaseClass):
         arrays (watermark hook applied
         per item, at the model rate), or writes ``output_paths[i]`` (at its ``out_sr``) instead.  Each item equals
         ``convert_long`` of it with the same ``window_frames``, noise and rates.  ``generator`` (keyword only): None
-        follows ``use_bf16_generator``, ``"fp32"`` / ``"bf16"`` choose the generator's kernels for this call."""
+        follows ``use_bf16_generator``, ``"fp32"`` / ``"bf16"`` choose the generator's kernels for this call.  ``tau``:
+        one number, or one per item; windows of items with different ``tau`` share launches, and each item still equals
+        its ``convert_long`` with its own ``tau``."""
         _lib.check_generator(generator, optional=True)
         hps = self.hps
         msr = hps.data.sampling_rate

@@ -28,7 +28,7 @@ speed per sentence.  The contract reads the same with that call as the public pi
 import numpy as np
 
 from . import _lib, longform, rates
-from .engine import wavenet_keyword
+from .engine import item_tau, rows_tau, wavenet_keyword
 
 RECORD_FIELDS = 4           # ov_join_segments_f32's record: (src_off, n, dst_off, gap)
 MAX_RECORDS = 65535
@@ -155,7 +155,7 @@ def sentence_batches(lengths, keys, max_sentences_per_launch=DEFAULT_SENTENCES_P
 
 
 class _Request:
-    __slots__ = ("ids", "speaker", "src_se", "tgt_se", "speed", "out_sr")
+    __slots__ = ("ids", "speaker", "src_se", "tgt_se", "speed", "out_sr", "tau")
 
 
 class VoiceCloner:
@@ -185,9 +185,9 @@ class VoiceCloner:
         reqs = []
         for i, q in enumerate(requests):
             if isinstance(q, dict):
-                q = (q["ids"], q["speaker"], q["src_se"], q["tgt_se"], q.get("speed", 1.0), q.get("out_sr"))
-            if not 4 <= len(q) <= 6:
-                raise ValueError(f"request {i}: (id sequences, speaker, src_se, tgt_se[, speed[, out_sr]])")
+                q = (q["ids"], q["speaker"], q["src_se"], q["tgt_se"], q.get("speed", 1.0), q.get("out_sr"), q.get("tau"))
+            if not 4 <= len(q) <= 7:
+                raise ValueError(f"request {i}: (id sequences, speaker, src_se, tgt_se[, speed[, out_sr[, tau]]])")
             r = _Request()
             r.ids = [np.asarray(s, dtype=np.int64).reshape(-1) for s in q[0]]
             if not r.ids or any(s.shape[0] == 0 for s in r.ids):
@@ -197,6 +197,9 @@ class VoiceCloner:
             if not r.speed > 0:
                 raise ValueError(f"request {i}: speed {q[4]!r}")
             r.out_sr = rates.check_rate(q[5] if len(q) > 5 else None, "out_sr")
+            r.tau = item_tau(1, q[6]) if len(q) > 6 and q[6] is not None else None      # None: the call's tau=
+            if r.tau is not None and not isinstance(r.tau, float):
+                raise _lib.OvError(f"request {i}: tau is one number per request")
             reqs.append(r)
         n = len(reqs)
         for name, per_request in (("noise_w", noise_w), ("noise_z", noise_z)):
@@ -270,9 +273,11 @@ class VoiceCloner:
                        max_sentences_per_launch=DEFAULT_SENTENCES_PER_LAUNCH, noise_scale=0.667, noise_scale_w=0.6,
                        generator="fp32", mixed=False):
         """Many "say this in that voice" requests in shared launches.  ``requests[i]``: ``(id sequences, speaker, src_se,
-        tgt_se[, speed[, out_sr]])`` (or a dict with those keys) -- the sentences as symbol ids (blanks interspersed by
+        tgt_se[, speed[, out_sr[, tau]]])`` (or a dict with those keys) -- the sentences as symbol ids (blanks interspersed by
         the caller if the config asks for it), the base speaker's name or id, the two ``[1, 256, 1]`` embeddings, the
-        speed (default 1.0) and the rate of the result (None: the converter's).  Explicit noise makes a call
+        speed (default 1.0), the rate of the result (None: the converter's) and the request's own ``tau`` (None: the
+        ``tau=`` of the call, one number or one per request).  Requests with different ``tau`` still go through ONE
+        ``convert_many``, their windows sharing its launches.  Explicit noise makes a call
         reproducible: ``noise_w[i][s]`` ``[2, Tx]`` and ``noise_z[i][s]`` ``[192, >= Ty]`` per sentence, ``noise[i]``
         ``[1, 192, >= T]`` per request for the converter; None: drawn on the device.  Returns one float32 numpy array
         per request (watermark hook applied at the converter's rate), and writes ``output_paths[i]`` when given.  The
@@ -290,6 +295,11 @@ class VoiceCloner:
         reqs = self._parse(requests, noise_w, noise_z, noise, output_paths)
         if not reqs:
             return []
+        tau = item_tau(len(reqs), tau)
+        if torch.is_tensor(tau):
+            tau = tau.tolist()
+        tau = rows_tau([(tau if isinstance(tau, float) else tau[i]) if r.tau is None else r.tau
+                        for i, r in enumerate(reqs)])
         with torch.no_grad():
             waves = self.synthesize_many(reqs, noise_w, noise_z, noise_scale, noise_scale_w, max_sentences_per_launch,
                                          mixed=mixed, **gen_kw)

@@ -137,6 +137,15 @@ __device__ __forceinline__ void conv_epilogue(const ov_conv1d_params& p, f32x16 
     // q = pair index: packed tiles 2q (tanh | m), 2q+1 (sigmoid | logs)
     if ((uint32_t)q * 32u >= Cout) return;
     const float* resb = p.res ? p.res + (int64_t)b * p.res_bstride : nullptr;
+    // POSTERIOR: tau of utterance b when the launch carries one per utterance (ov_conv1d_params.scale_b).  b is
+    // wave-uniform: one load per wave and 32 x 128-column fragment row (every lane the same address; the kernel has
+    // stored to global memory by then, so the compiler does not make it a scalar load), moved into an SGPR, where
+    // `scale` lives too.  The expression below is the same either way.
+    float tau = scale;
+    if constexpr (EPI == OV_EPI_POSTERIOR) {
+      if (p.scale_b)
+        tau = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p.scale_b[b])));
+    }
 #pragma unroll
     for (int j = 0; j < WN; ++j) {
       const uint32_t col = col0 + 32u * j;
@@ -158,7 +167,7 @@ __device__ __forceinline__ void conv_epilogue(const ov_conv1d_params& p, f32x16 
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const uint32_t rr = (r & 3) + 8 * (r >> 2);
-          (outb + (size_t)rr * LD)[voff] = (v0[r] * mk + nz[r] * scale * expf(v1[r] * mk)) * mk;
+          (outb + (size_t)rr * LD)[voff] = (v0[r] * mk + nz[r] * tau * expf(v1[r] * mk)) * mk;
         }
       }
     }

@@ -2,6 +2,7 @@
 // Signatures and reference citations: include/openvoice_amd.h.
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -293,7 +294,15 @@ int ov_conv1d_pack_f32(const float* w, int Cout, int Cin, int K, float* dst) {
 
 int ov_conv1d_f32(const ov_conv1d_params* pin, ov_stream_t stream) {
   if (!pin || !pin->x || !pin->w || !pin->out) return OV_E_BADARG;
-  ov_conv1d_params q = *pin;   // defaults filled in below; the kernels see the normalised copy
+  // defaults filled in below; the kernels see the normalised copy.  Without OV_F_SCALE_B the caller's struct may end
+  // before scale_b (it was appended within 2.12): nothing from there on is read.
+  ov_conv1d_params q;
+  if (pin->flags & OV_F_SCALE_B) {
+    q = *pin;
+  } else {
+    std::memcpy(&q, pin, offsetof(ov_conv1d_params, scale_b));
+    q.scale_b = nullptr;
+  }
   ov_conv1d_params* p = &q;
   if (p->B <= 0 || p->Cin <= 0 || p->L <= 0 || p->M <= 0 || p->Cout <= 0 || p->K <= 0 || p->dil <= 0)
     return OV_E_BADARG;
@@ -326,6 +335,7 @@ int ov_conv1d_f32(const ov_conv1d_params* pin, ov_stream_t stream) {
   if ((reinterpret_cast<uintptr_t>(p->w) & 15)) return OV_E_ALIGN;
   if (p->col_limit && (p->col_limit_scale <= 0 || (reinterpret_cast<uintptr_t>(p->col_limit) & 3))) return OV_E_BADARG;
   if (p->col_limit && p->B > ovk::LIMIT_MAX_BATCH) p->col_limit = nullptr;   // documented: whole tensor
+  if (p->scale_b && (reinterpret_cast<uintptr_t>(p->scale_b) & 3)) return OV_E_BADARG;
   if (p->chunk != 0 && p->chunk != 16 && p->chunk != 32) return OV_E_BADARG;
   if (p->tile < 0 || p->tile > 4 ||
       (p->loaders != 0 && p->loaders != 1 && p->loaders != 2 && p->loaders != 4))

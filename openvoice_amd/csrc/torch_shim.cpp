@@ -211,12 +211,12 @@ void finish(int rc, const char* what) { TORCH_CHECK(rc == OV_OK, what, " failed:
 
 // ip = [B, Cin, L, x_ld, out_ld, M, Cout, K, dil, epi, flags, split, phase_s, tiles_per_wg, tile, loaders, chunk,
 //       x_bstride, out_bstride, res_bstride, add_bstride, out2_bstride, bias_b_bstride, mask_bstride,
-//       x_off, out_off, res_off, bias_b_off, col_limit_scale]   (strides and offsets in elements);
-// fp = [in_slope, scale]
+//       x_off, out_off, res_off, bias_b_off, col_limit_scale, scale_b_off]   (strides and offsets in elements);
+// fp = [in_slope, scale];  scale_b: a tensor sets OV_F_SCALE_B, None leaves the field NULL
 void conv1d_f32(const OptTensor& x, const OptTensor& w, const OptTensor& bias, const OptTensor& out, const OptTensor& res,
                 const OptTensor& add, const OptTensor& out2, const OptTensor& mask, const OptTensor& bias_b,
-                const OptTensor& col_limit, at::IntArrayRef ip, at::ArrayRef<double> fp) {
-  TORCH_CHECK(ip.size() == 29 && fp.size() == 2, "openvoice_amd::conv1d_f32: 29 integer and 2 float parameters");
+                const OptTensor& col_limit, const OptTensor& scale_b, at::IntArrayRef ip, at::ArrayRef<double> fp) {
+  TORCH_CHECK(ip.size() == 30 && fp.size() == 2, "openvoice_amd::conv1d_f32: 30 integer and 2 float parameters");
   Ctx c{"conv1d_f32", false};
   ov_conv1d_params p{};
   p.x = sptr<float>(x, c, 0, ip[24]);
@@ -237,6 +237,11 @@ void conv1d_f32(const OptTensor& x, const OptTensor& w, const OptTensor& bias, c
   p.x_bstride = ip[17]; p.out_bstride = ip[18]; p.res_bstride = ip[19]; p.add_bstride = ip[20];
   p.out2_bstride = ip[21]; p.bias_b_bstride = ip[22]; p.mask_bstride = ip[23];
   p.in_slope = (float)fp[0]; p.scale = (float)fp[1];
+  p.scale_b = sptr<float>(scale_b, c, 10, ip[29]);
+  if (p.scale_b) {
+    TORCH_CHECK(scale_b->numel() - ip[29] >= p.B, "openvoice_amd::conv1d_f32: scale_b holds fewer than B values");
+    p.flags |= OV_F_SCALE_B;
+  }
   DeviceScope scope(c);
   finish(ov_conv1d_f32(&p, c.stream()), "ov_conv1d_f32");
 }
@@ -427,7 +432,7 @@ void conv1d_wino_multi_f32(const OptTensor& x0, const OptTensor& w0, const OptTe
 TORCH_LIBRARY(openvoice_amd, m) {
   // ---- parameter-struct entry points
   m.def("conv1d_f32(Tensor? x, Tensor? w, Tensor? bias, Tensor(a!)? out, Tensor? res, Tensor? add, Tensor(b!)? out2, "
-        "Tensor? mask, Tensor? bias_b, Tensor? col_limit, int[] ip, float[] fp) -> ()", &conv1d_f32);
+        "Tensor? mask, Tensor? bias_b, Tensor? col_limit, Tensor? scale_b, int[] ip, float[] fp) -> ()", &conv1d_f32);
   m.def("resblock_pair_f32(Tensor? x, Tensor? w1, Tensor? b1, Tensor? w2, Tensor? b2, Tensor(a!)? out, Tensor? add, "
         "Tensor(b!)? dbg, Tensor? col_limit, int[] ip, float[] fp) -> ()", &resblock_pair_f32);
   m.def("wn_layer_f32(Tensor? x, Tensor(a!)? out, Tensor(b!)? skip, Tensor? w_in, Tensor? b_in, Tensor? cond, Tensor? w_rs, "

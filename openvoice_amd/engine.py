@@ -13,6 +13,8 @@ g_tgt (models.py:390-397) -> Generator (models.py:272-291).
 import contextlib
 import ctypes
 import functools
+import math
+import numbers
 import os
 
 import torch
@@ -149,6 +151,58 @@ def padded_frames(T):
     return (T + 3) // 4 * 4
 
 
+def item_tau(B, tau, device=None):
+    """The ``tau=`` of a conversion of ``B`` items (the conversion's counterpart of ``tts_engine.item_controls``, which
+    re-exports it; it lives here because ``tts_engine`` imports this module).  Returns
+
+    * a float for one number (or a zero-dimensional tensor / array): the launch scalar, ``scale_b`` stays NULL;
+    * a list of ``B`` floats for a sequence, an array or a HOST tensor of ``B`` numbers, each checked to be finite;
+    * the tensor itself for a 1-D float32 DEVICE tensor of ``B`` values (on ``device`` when that is given): it is used
+      as it is and its values are not read, so that nothing synchronises.
+
+    ``OvError`` on anything else: a wrong length, a bool or a string (alone or as an element), a non-finite element, a
+    device tensor of another dtype, rank or device."""
+    def bad(why):
+        raise _lib.OvError(f"tau must be one number or one finite number per item ({B}): {why}")
+
+    if isinstance(tau, (bool, str, bytes)):
+        bad(f"got {tau!r}")
+    if isinstance(tau, numbers.Real) or (hasattr(tau, "ndim") and tau.ndim == 0):
+        return float(tau)
+    if isinstance(tau, torch.Tensor):
+        if tau.ndim != 1 or tau.shape[0] != B:
+            bad(f"got a tensor of shape {tuple(tau.shape)}")
+        if tau.is_cuda:
+            if tau.dtype != torch.float32:
+                bad(f"a device tensor must be float32, got {tau.dtype}")
+            if device is not None and tau.device != torch.device(device):
+                bad(f"the tensor is on {tau.device}, the conversion runs on {device}")
+            return tau.contiguous()
+        if not (tau.dtype.is_floating_point or tau.dtype in (torch.int8, torch.int16, torch.int32, torch.int64)):
+            bad(f"got a tensor of {tau.dtype}")
+        vals = tau.tolist()
+    else:
+        try:
+            vals = list(tau)
+        except TypeError:
+            bad(f"got {type(tau).__name__}")
+    if len(vals) != B:
+        bad(f"got {len(vals)} values")
+    for v in vals:
+        if isinstance(v, bool) or not isinstance(v, numbers.Real):
+            bad(f"element {v!r}")
+        if not math.isfinite(v):
+            bad(f"non-finite element in {vals}")
+    return [float(v) for v in vals]
+
+
+def rows_tau(taus):
+    """The ``tau`` of one launch from the taus of its rows: the number itself when the rows agree (the scalar launch,
+    which a captured graph can serve), else the list (one value per row: ``ov_conv1d_params.scale_b``)."""
+    taus = [float(t) for t in taus]
+    return taus[0] if all(t == taus[0] for t in taus) else taus
+
+
 def ref_enc_lengths(T, n_convs=len(REF_ENC_FILTERS)):
     """Frames an item of ``T`` spectrogram frames has at the input of each ReferenceEncoder conv and after the last one:
     ``[T, T1, ..., T_n]`` with ``T_{k+1} = (T_k - 1) // 2 + 1`` (3x3, stride 2, padding 1; reference
@@ -206,17 +260,26 @@ if _EXTRA_CONV_FLAGS & ~_lib.F_NO_XCD_MAP:
 def launch_conv(layer, x, x_off, x_bs, out, out_off, out_bs, B, L, epi=EPI_LINEAR, flags=0, in_slope=1.0,
                 scale=1.0, res=None, res_off=0, res_bs=0, add=None, add_bs=0, out2=None, out2_bs=0, mask=None,
                 bias_b=None, bias_b_off=0, bias_b_bs=0, split=0, phase_s=1, cin=None, rows=None, tiles_per_wg=0,
-                x_ld=0, out_ld=0, mask_bs=0, tile=0, loaders=0, chunk=0, col_limit=None, col_limit_scale=1):
+                x_ld=0, out_ld=0, mask_bs=0, tile=0, loaders=0, chunk=0, col_limit=None, col_limit_scale=1,
+                scale_b=None, scale_b_off=0):
     """Fill ``ov_conv1d_params`` and launch on torch's current stream of ``x``'s device.
     Offsets, row strides (``*_ld``, 0 = dense) and batch strides are in elements.  ``col_limit`` (int32 [B] on the
-    device) x ``col_limit_scale`` = output columns per utterance that matter: tiles beyond are not computed."""
+    device) x ``col_limit_scale`` = output columns per utterance that matter: tiles beyond are not computed.
+    ``scale_b`` (``EPI_POSTERIOR``; contiguous fp32 on the device, ``B`` values from element ``scale_b_off`` on): one
+    ``scale`` per batch item, ``scale`` itself is then ignored; the other epilogues ignore it."""
     flags |= _EXTRA_CONV_FLAGS
+    if scale_b is not None:
+        if not (scale_b.dtype == torch.float32 and scale_b.is_contiguous() and scale_b_off >= 0
+                and scale_b.numel() - scale_b_off >= B):
+            raise _lib.OvError(f"launch_conv: scale_b must be contiguous float32 with {B} values from element "
+                               f"{scale_b_off} on, got {scale_b.dtype} x {scale_b.numel()}")
+        flags |= _lib.F_SCALE_B
     if _lib.use_torch_binding():
         ip = [B, layer.cin if cin is None else cin, L, x_ld, out_ld, layer.rows if rows is None else rows, layer.cout,
               layer.K, layer.dil, epi, flags, split, phase_s, tiles_per_wg, tile, loaders, chunk,
               x_bs, out_bs, res_bs, add_bs, out2_bs, bias_b_bs, mask_bs, x_off, out_off, res_off, bias_b_off,
-              col_limit_scale]
-        _lib.torch_op("conv1d_f32", x, layer.w, layer.bias, out, res, add, out2, mask, bias_b, col_limit, ip,
+              col_limit_scale, scale_b_off]
+        _lib.torch_op("conv1d_f32", x, layer.w, layer.bias, out, res, add, out2, mask, bias_b, col_limit, scale_b, ip,
                       [in_slope, scale])
         return
     p = ConvParams()
@@ -239,6 +302,7 @@ def launch_conv(layer, x, x_off, x_bs, out, out_off, out_bs, B, L, epi=EPI_LINEA
     p.x_ld, p.out_ld, p.mask_bstride = x_ld, out_ld, mask_bs
     p.col_limit = ctypes.c_void_p(col_limit.data_ptr()) if col_limit is not None else None
     p.col_limit_scale = col_limit_scale
+    p.scale_b = _ptr(scale_b, scale_b_off) if scale_b is not None else None
     stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
     _lib.check(_lib.load().ov_conv1d_f32(ctypes.byref(p), stream), "ov_conv1d_f32")
 
@@ -885,17 +949,31 @@ class ConverterEngine:
         kernels for this call, whatever the switch says and without touching it (the bf16 generator is built on first
         use, as for a bf16 live pool).  ``wavenet``: the same for the WaveNet layers of the posterior encoder and of the
         flow -- None follows ``use_bf16_wavenet``, ``"fp32"`` / ``"bf16"`` choose for this call (``ov_wn_layer_bf16``:
-        bf16 matrix operands, fp32 state); independent of ``generator``."""
+        bf16 matrix operands, fp32 state); independent of ``generator``.  ``tau``: one number for the batch, or one per
+        item -- a sequence (uploaded once per call as a float32 device vector) or a 1-D float32 device tensor of ``B``
+        values (used as it is, nothing synchronises); see ``item_tau``.  Per item it reaches the one place ``tau``
+        enters, the ``q_proj`` epilogue, as ``ov_conv1d_params.scale_b``: the same launches as with a number, and item
+        ``b`` holds the bits of the batch run with the number ``tau[b]``."""
         use_bf16 = self._bf16_on
         if _lib.check_generator(generator, optional=True) is not None:
             use_bf16 = generator == "bf16"
         with self.wavenet_scope(wavenet):
             return self._voice_conversion(spec, spec_lengths, sid_src, sid_tgt, tau, noise, skip_padding, seed, use_bf16)
 
+    def _tau_args(self, B, tau):
+        """``(scale, scale_b)`` of a ``q_proj`` launch of ``B`` rows from a ``tau=`` argument (``item_tau``)."""
+        tau = item_tau(B, tau, self.device)
+        if isinstance(tau, float):
+            return tau, None
+        if isinstance(tau, list):
+            tau = torch.tensor(tau, dtype=torch.float32).to(self.device)
+        return 1.0, tau
+
     def _voice_conversion(self, spec, spec_lengths, sid_src, sid_tgt, tau, noise, skip_padding, seed, use_bf16):
         dev = self.device
         spec = spec.to(dev, torch.float32)
         B, F, T = spec.shape
+        tau = self._tau_args(B, tau)
         assert F == self.spec_channels
         # rows may be padded (the native spectrogram returns a [B, F, T] view of 16-byte aligned rows)
         if not (spec.stride(2) == 1 and spec.stride(1) >= T and spec.stride(0) >= F * spec.stride(1)):
@@ -952,7 +1030,8 @@ class ConverterEngine:
                        C, dst)
 
     def _frames(self, ws, b0, b1, spec, conds, tau):
-        """Posterior encoder and the two flow passes for the utterances [b0, b1) (views of the whole-batch workspace)."""
+        """Posterior encoder and the two flow passes for the utterances [b0, b1) (views of the whole-batch workspace);
+        ``tau``: the whole batch's ``(scale, scale_b)`` (``_tau_args``)."""
         nb, T, Tp = b1 - b0, spec.shape[2], ws["Tp"]
         C, H = self.inter, self.hidden
         sub = {k: (v[b0:b1] if torch.is_tensor(v) else v) for k, v in ws.items() if k != "dec"}
@@ -965,14 +1044,19 @@ class ConverterEngine:
         self._wavenet(self.q_wn, sub, nb, T, rows(conds["q"]), mask)
         z, z_p, z_hat = sub["z"], sub["z_p"], sub["z_hat"]
         self._conv(self.q_proj, sub["skip"], 0, H * Tp, z, 0, C * Tp, nb, T, epi=EPI_POSTERIOR, res=sub["noise"],
-                   res_bs=C * Tp, scale=float(tau), mask=mask, mask_bs=Tp, rows=2 * C, x_ld=Tp, out_ld=Tp, tag="q_proj")
+                   res_bs=C * Tp, scale=tau[0], scale_b=tau[1], scale_b_off=b0, mask=mask, mask_bs=Tp, rows=2 * C, x_ld=Tp,
+                   out_ld=Tp, tag="q_proj")
         # ---- flow forward with g_src, reverse with g_tgt (models.py:496-497) -----------------------
         self._flow(z, z_p, sub, nb, T, [rows(c) for c in conds["src"]], mask, reverse=False)
         self._flow(z_p, z_hat, sub, nb, T, [rows(c) for c in conds["tgt"]], mask, reverse=True)
 
     def graphed(self, B, T, tau, src_rows=1, tgt_rows=1, max_cached=4, skip_padding=False):
         """``voice_conversion`` for one fixed (B, T, tau) as a captured HIP graph (see ``GraphedConversion``);
-        the most recent ``max_cached`` shapes stay resident."""
+        the most recent ``max_cached`` shapes stay resident.  ``tau`` is one number here: it is part of the key and a
+        constant of the captured launch.  A per-item ``tau`` takes the ungraphed path (``voice_conversion``)."""
+        if not isinstance(item_tau(B, tau), float):
+            raise _lib.OvError("graphed: a captured conversion is keyed on one tau; a per-item tau takes the ungraphed "
+                               "path (voice_conversion)")
         key = (int(B), int(T), float(tau), int(src_rows), int(tgt_rows), self._bf16_on,
                bool(skip_padding), bool(self._split3_on), self.split3_products, self.wavenet_bf16())
         cache = self._graphs
@@ -1389,14 +1473,16 @@ class ConverterEngine:
     def live_posterior(self, spec, spec_ld, spec_bs, noise, noise_bs, out, ld, bs, B, L, cond_q, tau, ws):
         """Posterior encoder unit (models.py:212-221: q_pre, the 16-layer WaveNet, q_proj with ``OV_EPI_POSTERIOR``):
         ``spec`` [B rows of ``spec_bs``][513][``spec_ld``] -> ``out`` z [B rows of ``bs``][inter][``ld``]; ``noise``
-        [B rows of ``noise_bs``][inter][``ld``]; ``L`` columns; ``cond_q`` the rows' gate biases (``live_conds``).""" 
+        [B rows of ``noise_bs``][inter][``ld``]; ``L`` columns; ``cond_q`` the rows' gate biases (``live_conds``);
+        ``tau`` one number or one per row (``item_tau``)."""
+        scale, scale_b = self._tau_args(B, tau)
         H, C, Tp = self.hidden, self.inter, ws["Tp"]
         mask = self._live_mask(ws, B, L)
         self._conv(self.q_pre, spec, 0, spec_bs, ws["h"], 0, H * Tp, B, L, flags=F_MASK_V, mask=mask, mask_bs=Tp,
                    x_ld=spec_ld, out_ld=Tp, tag="q_pre")
         self._wavenet(self.q_wn, ws, B, L, cond_q, mask)
         self._conv(self.q_proj, ws["skip"], 0, H * Tp, out, 0, bs, B, L, epi=EPI_POSTERIOR, res=noise, res_bs=noise_bs,
-                   scale=float(tau), mask=mask, mask_bs=Tp, rows=2 * C, x_ld=Tp, out_ld=ld, tag="q_proj")
+                   scale=scale, scale_b=scale_b, mask=mask, mask_bs=Tp, rows=2 * C, x_ld=Tp, out_ld=ld, tag="q_proj")
 
     @torch.no_grad()
     @on_own_device
@@ -1577,6 +1663,7 @@ class GraphedConversion:
 
     @on_own_device
     def __init__(self, engine, B, T, tau, src_rows=1, tgt_rows=1, skip_padding=False, wavenet=None):
+        # one number: a constant of the captured q_proj launch (a per-item tau runs ungraphed, ConverterEngine.graphed)
         dev = engine.device
         self.engine, self.B, self.T, self.tau = engine, int(B), int(T), float(tau)
         f = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)

@@ -45,6 +45,7 @@ import torch
 
 from . import _lib, rates
 from . import noise as noise_mod
+from .engine import item_tau, rows_tau
 from .generator import generator_stages, samples_per_frame
 from .longform import launch_ladder, stream_end_frames, winograd_grid_frames
 from .params import ENC_Q_KERNEL, ENC_Q_LAYERS, FLOW_KERNEL, FLOW_LAYERS, N_FLOWS
@@ -268,7 +269,9 @@ class LivePool:
     rounds) -> ``{handle: newly finished samples}`` (device tensors); ``close(h)`` marks the end of h's input.  Rounds:
     every ready stream advances by one chunk per round, each unit runs its streams' buffers in launches of up to
     ``max_streams_per_launch`` rows grouped by buffer width (steady-state streams share one width; a stream's first
-    rounds and its end run narrower), padded up to the ``launch_ladder`` sizes.  ``tau`` is one scalar for the pool.
+    rounds and its end run narrower), padded up to the ``launch_ladder`` sizes.  ``tau`` is the pool's default;
+    ``open(..., tau=)`` gives a stream its own, kept for life, and the rows of a posterior-encoder launch each carry
+    their stream's (``ov_conv1d_params.scale_b``; a launch whose rows agree is the scalar launch it always was).
     Live units run eagerly, never from a captured graph.  ``generator``: ``"fp32"`` (default) or ``"bf16"`` -- the
     kernels of the ``g`` units (module docstring); everything else, the latency and the state size included, is the
     same for both.  ``wavenet``: None (follow ``ConverterEngine.use_bf16_wavenet``), ``"fp32"`` or ``"bf16"`` -- the
@@ -280,6 +283,7 @@ class LivePool:
                  max_streams_per_launch=DEFAULT_LIVE_STREAMS_PER_LAUNCH, n_fft=1024, hop=256, model_sr=rates.MODEL_RATE,
                  generator="fp32", wavenet=None):
         self.model, self.tau = model, float(tau)
+        self._tau_rows = {}         # taus of a launch's rows -> their float32 device vector (uploaded once)
         self.generator = check_generator(generator)
         # the WaveNet layers' kernels of the q / f / r units: None follows the engine's use_bf16_wavenet switch
         self.wavenet = _lib.check_wavenet(wavenet, optional=True)
@@ -375,13 +379,17 @@ class LivePool:
     def active(self):
         return list(self._streams)
 
-    def open(self, src_se, tgt_se, noise=None, sr_in=None, sr_out=None, *, seed=None):
-        """A new stream -> its handle.  ``sr_in`` / ``sr_out``: the rate of its pushes / of its output (None or the
+    def open(self, src_se, tgt_se, noise=None, sr_in=None, sr_out=None, *, seed=None, tau=None):
+        """A new stream -> its handle.  ``tau``: None = the pool's, else this stream's own number, for life.
+        ``sr_in`` / ``sr_out``: the rate of its pushes / of its output (None or the
         model rate: no resampler in that direction).  ``noise`` ``[1, inter, >= T]``, or ``seed`` (an int: stream
         ``(seed, 0)``, or a pair): counter-based noise (``noise.py``) generated chunk by chunk into the staging rows --
         the stream then equals ``convert_long(seed=...)`` of its whole input whatever the push sizes and whoever shares
         the pool, and holds no noise tensor; neither: drawn from torch's generator per chunk."""
         noise_mod.exclusive(seed, noise=noise)
+        tau = self.tau if tau is None else item_tau(1, tau)
+        if not isinstance(tau, float):
+            raise _lib.OvError("LivePool.open: tau is one number per stream")
         sr_in, sr_out = rates.check_rate(sr_in, "sr_in"), rates.check_rate(sr_out, "sr_out")
         if not self._free_slots:                 # the arena doubles: streams already open keep their slots
             grown = max(1, 2 * self._slots)
@@ -392,7 +400,7 @@ class LivePool:
         h = self._next
         self._next += 1
         st = _Live(self, slot, src_se, tgt_se, noise, seed=seed)
-        st.sr_in, st.sr_out = sr_in, sr_out
+        st.sr_in, st.sr_out, st.tau = sr_in, sr_out, tau
         st.rin = st.rout = None
         if sr_in is not None and sr_in != self.model_sr:
             st.rin = self._rin.open(sr_in, self.model_sr)
@@ -566,7 +574,7 @@ class LivePool:
         if u["kind"] == "q":
             cond = cat([st.conds["q"] for st, _ in rows])
             eng.live_posterior(x, ldi, R * ldi, mem[self.in_off[k] + self.bins * ldi:], R * ldi, out, ldo, C * ldo, B,
-                               L, cond, self.tau, ws)
+                               L, cond, self._launch_tau(rows), ws)
         elif u["kind"] in ("f", "r"):
             key = "src" if u["kind"] == "f" else "tgt"
             conds = [torch.cat([st.conds[key][f] for st, _ in rows]) for f in range(len(rows[0][0].conds[key]))]
@@ -577,6 +585,20 @@ class LivePool:
         else:
             cond = cat([st.conds["d"] for st, _ in rows]) if u["stage"] == 0 else None
             eng.live_generator_stage(u["stage"], x, ldi, R * ldi, out, B, L, ws, cond_d=cond)
+
+    def _launch_tau(self, rows):
+        """``tau`` of a posterior-encoder launch: the number when its rows agree, else their per-row device vector --
+        uploaded the first time this combination of rows is launched, so a steady pool uploads nothing per tick."""
+        tau = rows_tau([st.tau for st, _ in rows])
+        if isinstance(tau, float):
+            return tau
+        key = tuple(tau)
+        vec = self._tau_rows.get(key)
+        if vec is None:
+            if len(self._tau_rows) >= 256:          # pools whose membership keeps changing: start over, stay bounded
+                self._tau_rows.clear()
+            vec = self._tau_rows[key] = torch.tensor(tau, dtype=torch.float32).to(self.device)
+        return vec
 
     def _scatter(self, k, chunk, L, outputs):
         """Records moving unit k's kept output columns of a launch's rows into unit k + 1's state (or into the round's

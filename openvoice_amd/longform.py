@@ -24,7 +24,7 @@ import math
 import torch
 
 from . import _lib, rates
-from .engine import wavenet_keyword
+from .engine import item_tau, rows_tau, wavenet_keyword
 from . import noise as noise_mod
 from .generator import GENERATOR_MARGIN, generator_margin_frames, generator_stages, samples_per_frame
 from .params import ENC_Q_KERNEL, ENC_Q_LAYERS, FLOW_KERNEL, FLOW_LAYERS, N_FLOWS
@@ -217,7 +217,9 @@ class WindowedConverter:
         ``dst`` the packed output frame of the core's first frame.  Jobs of equal ``Tw`` share
         launches of up to ``max_windows`` in the given order; a partial launch is padded up to the next ``ladder`` size
         (None: launched as it is) with copies of its last window.  ``generator``: handed to ``voice_conversion`` when
-        not None.  Returns the number of launches."""
+        not None.  ``tau``: one number, or a list with one per SOURCE; a launch whose windows' sources disagree carries
+        one value per row (``rows_tau``), so sources with different ``tau`` share launches.  Returns the number of
+        launches."""
         if not jobs:
             return 0
         bases, acc = [], 0
@@ -252,7 +254,8 @@ class WindowedConverter:
                                     for w, j in enumerate(rows) if seeded[w]], self.inter, nz)
                 g_src = torch.cat([j[6].reshape(1, -1, 1) for j in rows])
                 g_tgt = torch.cat([j[7].reshape(1, -1, 1) for j in rows])
-                self._launch_multi(pool, recs_dev[:W], Tw, g_src, g_tgt, tau, nz, out, recs_dev[W:], r,
+                launch_tau = rows_tau([tau[j[0]] for j in rows]) if isinstance(tau, list) else tau
+                self._launch_multi(pool, recs_dev[:W], Tw, g_src, g_tgt, launch_tau, nz, out, recs_dev[W:], r,
                                    **noise_mod.kw(seed), **_lib.generator_kw(generator))
                 launches += 1
         return launches
@@ -295,10 +298,14 @@ class WindowedConverter:
         output), each equal to ``convert`` of that recording with the same noise (bit for bit with direct kernels).
         ``generator`` (keyword only): None follows the engine's ``use_bf16_generator`` switch, ``"fp32"`` / ``"bf16"``
         choose the generator's kernels for this call (``ConverterEngine.voice_conversion``); the windows of a launch
-        have one length, so the bf16 generator runs them as the dense batch they are."""
+        have one length, so the bf16 generator runs them as the dense batch they are.  ``tau``: one number, or one per
+        recording (``engine.item_tau``); every window carries the ``tau`` of its recording."""
         _lib.check_generator(generator, optional=True)
         dev = self._device()
         n = len(waves)
+        tau = item_tau(n, tau)
+        if torch.is_tensor(tau):        # windows are regrouped on the host: a device vector is read back once
+            tau = tau.tolist()
         if len(src_ses) != n or len(tgt_ses) != n or (noises is not None and len(noises) != n):
             raise ValueError("convert_many: one src / tgt embedding (and noise) per recording")
         noise_mod.exclusive(seeds, noises=noises)
@@ -550,14 +557,18 @@ class StreamPool:
     Launch sizes come from a fixed ladder (``launch_ladder``: 1, 2, 4, ..., max_windows_per_launch); a partial launch
     is padded with copies of one of its windows whose output is dropped, and the engine keeps one workspace per ladder
     size resident (``ConverterEngine.resident_workspaces`` is raised to len(ladder) + 1, the one spare for the T-frame
-    final windows of streams shorter than a window).  ``tau`` is one launch scalar for the whole pool.
+    final windows of streams shorter than a window).  ``tau`` is the pool's default; ``open(..., tau=)`` gives a stream
+    its own, kept for life, and the windows of a launch each carry their stream's (``ov_conv1d_params.scale_b``; a
+    launch whose windows agree is the scalar launch it always was).
 
     ``open(..., sr_in=None, sr_out=None)``: the stream's pushes / output at rates of their own.  A ``step()`` then first
     resamples the new input of every such stream to the model rate in ONE launch (``rates.ResamplerBank``) and, after the
     windows, the new output of every such stream in one more; ``latency_of(h)`` is the stream's own bound."""
 
     def __init__(self, conv, tau=0.3, max_windows_per_launch=DEFAULT_POOL_WINDOWS_PER_LAUNCH):
-        self.conv, self.tau = conv, tau
+        self.conv, self.tau = conv, item_tau(1, tau)
+        if not isinstance(self.tau, float):
+            raise _lib.OvError("StreamPool: the pool's tau is one number; give a stream its own with open(tau=)")
         self.ladder = launch_ladder(max_windows_per_launch)
         self.max_windows_per_launch = self.ladder[-1]
         self._streams = {}          # handle -> _StreamState, in handle order
@@ -584,8 +595,13 @@ class StreamPool:
         c = self.conv
         return (c.window_frames - 1) * c.hop + c.n_fft - c.pad
 
-    def open(self, src_se, tgt_se, noise=None, sr_in=None, sr_out=None, *, seed=None):
+    def open(self, src_se, tgt_se, noise=None, sr_in=None, sr_out=None, *, seed=None, tau=None):
+        """A new stream -> its handle.  ``tau``: None = the pool's, else this stream's own number, for life."""
+        tau = self.tau if tau is None else item_tau(1, tau)
+        if not isinstance(tau, float):
+            raise _lib.OvError("StreamPool.open: tau is one number per stream")
         st = _StreamState(self.conv, src_se, tgt_se, noise, sr_in=sr_in, sr_out=sr_out, seed=seed)
+        st.tau = tau
         msr = self.conv.model_sr
         if st.sr_in is not None and st.sr_in != msr:
             st.rin = self._rin.open(st.sr_in, msr)
@@ -655,7 +671,7 @@ class StreamPool:
         for key, y in self._rin.step().items():
             self._rin_owner[key]._append(y)
         routs = {h: st.rout for h, st in self._streams.items() if st.rout is not None}
-        sources, jobs, spans, acc = [], [], {}, 0
+        sources, taus, jobs, spans, acc = [], [], [], {}, 0
         for h, st in self._streams.items():
             if st._closed:
                 recs = st._tail
@@ -674,13 +690,14 @@ class StreamPool:
                              acc))
                 acc += hi - lo
             sources.append(st._buf[:st._len])
+            taus.append(st.tau)
             spans[h] = (first, acc, recs[-1][0])
         if not jobs:
             return {}
         out = torch.empty(acc * c.spf, dtype=torch.float32, device=sources[0].device)
         # windows of full length first (the ladder's shapes), then the T-frame final windows grouped by length
         jobs.sort(key=lambda j: j[4] != c.window_frames)
-        c._run_jobs(sources, jobs, self.tau, out, self.max_windows_per_launch, ladder=self.ladder)
+        c._run_jobs(sources, jobs, taus, out, self.max_windows_per_launch, ladder=self.ladder)
         outs = {}
         for h, (a, b, (f0, _, hi)) in spans.items():
             outs[h] = out[a * c.spf:b * c.spf]

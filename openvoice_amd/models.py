@@ -14,7 +14,7 @@ from torch import nn
 
 from . import _lib
 from . import noise as noise_mod
-from .engine import ConverterEngine, validate_config, wavenet_keyword
+from .engine import ConverterEngine, item_tau, validate_config, wavenet_keyword
 from .params import converter_param_spec, tts_full_param_spec
 
 
@@ -114,7 +114,9 @@ class SynthesizerTrn(nn.Module):
         batches): the generator computes only ``length + limit_margin`` (16-20) frames per utterance -- valid samples
         bit-identical, the padded tail of ``o_hat`` zero (``ConverterEngine.voice_conversion``).  ``generator``: None
         follows the engine's ``use_bf16_generator`` switch; ``"fp32"`` / ``"bf16"`` choose for this call (eager calls
-        only: a captured graph follows the switch)."""
+        only: a captured graph follows the switch).  ``tau``: one number, or one per item (a sequence or a 1-D float32
+        device tensor of ``B`` values, ``engine.item_tau``); graphs are keyed on one ``tau``, so a per-item ``tau`` runs
+        eagerly even with ``graph=True`` and returns fresh tensors."""
         _lib.check_generator(generator, optional=True)
         eng = self.engine()
         if self.n_speakers != 0:
@@ -122,7 +124,7 @@ class SynthesizerTrn(nn.Module):
         if graph and generator is not None:
             raise _lib.OvError("voice_conversion: generator= chooses per eager call; a captured graph (graph=True) follows "
                                "use_bf16_generator")
-        if graph:
+        if graph and isinstance(item_tau(y.shape[0], tau), float):
             g = eng.graphed(y.shape[0], y.shape[2], tau, sid_src.shape[0], sid_tgt.shape[0], skip_padding=skip_padding)
             return g(y, y_lengths, sid_src, sid_tgt, noise=noise, **noise_mod.kw(seed))
         return eng.voice_conversion(y, y_lengths, sid_src, sid_tgt, tau=tau, noise=noise, skip_padding=skip_padding,

@@ -64,7 +64,7 @@ def gather_waveforms(local_wave, group=None, counts=None):
 
 
 def convert_sharded(convert_fn, waveforms, src_se, tgt_se, gin, device, noise=None, gather=True, root=0, group=None,
-                    frames=None):
+                    frames=None, tau=None):
     """Convert a batch of independent utterances across the ranks of the process group.
 
     Every rank passes the same ``waveforms`` ([N, samples] tensor, or a list of N waveforms) and, optionally, the same
@@ -76,7 +76,11 @@ def convert_sharded(convert_fn, waveforms, src_se, tgt_se, gin, device, noise=No
 
     ``frames`` (ragged batches): every utterance's frame count.  ``noise`` is [N, C, max(frames)] -- the width of the
     WHOLE batch -- while a shard is converted at its OWN longest length, so the noise handed to ``convert_fn`` is cut
-    to ``max(frames[start:end])`` frames: per-utterance noise, the same result however the batch is cut."""
+    to ``max(frames[start:end])`` frames: per-utterance noise, the same result however the batch is cut.
+
+    ``tau`` (None: ``convert_fn`` takes four arguments, as above): one number, or one value per utterance (a sequence or
+    a 1-D tensor of N).  It is handed on as ``convert_fn(..., tau=...)`` -- the number as it is, per-utterance values cut
+    to ``[start:end]`` like the waveforms, so utterance i is converted with ``tau[i]`` however the batch is cut."""
     world = dist.get_world_size(group) if _initialised() else 1
     rank = dist.get_rank(group) if _initialised() else 0
     n = len(waveforms)
@@ -86,7 +90,13 @@ def convert_sharded(convert_fn, waveforms, src_se, tgt_se, gin, device, noise=No
     nz = None if noise is None else noise[start:end]
     if nz is not None and frames is not None and end > start:
         nz = nz[:, :, :max(int(f) for f in frames[start:end])]
-    local = convert_fn(shard, src_se, tgt_se, nz)
+    if tau is None:
+        local = convert_fn(shard, src_se, tgt_se, nz)
+    else:
+        per_item = hasattr(tau, "__len__") and not (hasattr(tau, "ndim") and tau.ndim == 0)
+        if per_item and len(tau) != n:
+            raise ValueError(f"convert_sharded: tau has {len(tau)} values for {n} utterances")
+        local = convert_fn(shard, src_se, tgt_se, nz, tau=tau[start:end] if per_item else tau)
     if not gather:
         return local, (start, end)
     counts = [shard_range(n, r, world)[1] - shard_range(n, r, world)[0] for r in range(world)]

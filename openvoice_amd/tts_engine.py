@@ -23,7 +23,7 @@ import torch
 from . import _lib
 from . import noise as noise_mod
 from ._lib import F_MASK_V, LN_POST_GELU, LN_PRE_RELU
-from .engine import ConverterEngine, PackedConv, on_own_device, padded_frames, wavenet_keyword
+from .engine import ConverterEngine, PackedConv, item_tau, on_own_device, padded_frames, wavenet_keyword  # noqa: F401
 from .params import ATTN_WINDOW, SDP_DDS_LAYERS, SDP_FLOWS, SDP_KERNEL, SDP_NUM_BINS, SDP_TAIL_BOUND
 
 LN_EPS = 1e-5   # modules.LayerNorm / attentions.LayerNorm default
@@ -52,7 +52,8 @@ def item_controls(B, noise_scale, length_scale, noise_scale_w, sdp_ratio):
     tensor of ``B`` numbers.  All four plain numbers: returns None (the scalar kernels run).  Any of them per item:
     returns ``{name: [B floats]}`` with the plain numbers broadcast.  A per-item control of the wrong length, a
     non-finite value in it, or a per-item ``length_scale <= 0`` is a ValueError.  ``sdp_ratio`` is not confined to
-    [0, 1]: the reference's ``sdp * r + dp * (1 - r)`` (models.py:474) extrapolates outside it and so do the kernels."""
+    [0, 1]: the reference's ``sdp * r + dp * (1 - r)`` (models.py:474) extrapolates outside it and so do the kernels.
+    (The conversion's per-item control, ``tau``, is validated by ``item_tau``, defined in ``engine`` and re-exported here.)"""
     given = dict(zip(CONTROLS, (noise_scale, length_scale, noise_scale_w, sdp_ratio)))
     if all(_is_number(v) for v in given.values()):
         return None
