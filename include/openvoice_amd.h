@@ -668,6 +668,33 @@ int ov_expand_prior_items_f32(const float* m_tok, const float* logs_tok, int64_t
                               int64_t noise_bstride, int ldn, float* z_p, float* m_p, float* logs_p, float* attn,
                               int B, int C, int Tx, int Ty, int ldy, const float* noise_scale_b, ov_stream_t stream);
 
+/* The streaming form of the same prior sample (csrc/tts_live.hip, openvoice_amd/tts_live.py): ONE launch gives every
+ * stream that is ready its next piece of z_p, written straight into the state row of its first live unit.  records is a
+ * DEVICE int64 [R][13], record r one stream's piece:
+ *   [0] seed, [1] stream   the (seed, stream) pair of its noise_z (purpose 2), as for ov_normal_philox_f32
+ *   [2] f0, [3] nf         the frames [f0, f0 + nf) of the sentence
+ *   [4] x_len, [5] y_len   the sentence's tokens and frames
+ *   [6] m_off, [7] m_ld, [8] logs_off, [9] logs_ld   its token-rate m / logs rows (the two halves of the encoder's
+ *                          projection) in tok: m[c][j] = tok[m_off + c * m_ld + j], logs likewise
+ *   [10] cum_off           its row of inclusive duration prefix sums: cum[j] = cum_base[cum_off + j]
+ *   [11] dst_off, [12] dst_ld   where the piece goes
+ * all offsets in elements.  For c < C, i < nf, t = f0 + i and j the token with cum[j-1] <= t < cum[j] (m = logs = 0
+ * when no token owns t):
+ *   dst[dst_off + c * dst_ld + i] = m[c][j] + n(seed, stream, 2, c, t) * exp(logs[c][j]) * noise_scale_r[r]
+ * and nothing else is written.  Each value holds the bits ov_normal_philox_f32 followed by ov_expand_prior_items_f32
+ * writes to z_p[c][t] (the three kernels share the Philox / Box-Muller and the expansion arithmetic as device
+ * functions).  One thread owns one Philox block, as in ov_normal_philox_f32, so a value does not depend on f0's phase,
+ * on alignment, on R or on its neighbours; a block wholly inside the piece at a 16-byte aligned address is one vector
+ * store.  noise_scale_r: an fp32 DEVICE vector of R values.  max_frames = the largest nf of the launch sizes the grid
+ * only.  Host checks: null pointers, R outside [1, 65535], C <= 0, tok_elems / cum_elems / dst_elems <= 0,
+ * max_frames < 0 (OV_E_BADARG); pointers 4-byte aligned (OV_E_ALIGN).  The kernel checks every record: one with a
+ * negative field, stream >= 2^32, x_len or y_len outside [1, 2^31), nf < 1, f0 + nf > y_len, nf > dst_ld, or whose
+ * m / logs / cum rows leave [0, tok_elems) / [0, cum_elems) or whose piece leaves [0, dst_elems) writes nothing.
+ * Additive to ABI 2.12: found by name, like ov_normal_philox_f32. */
+int ov_expand_prior_rows_f32(const int64_t* records, int R, int C, const float* tok, int64_t tok_elems,
+                             const int32_t* cum, int64_t cum_elems, const float* noise_scale_r, float* dst,
+                             int64_t dst_elems, int64_t max_frames, ov_stream_t stream);
+
 /* ---- bf16 generator (BASELINE.json configs[4]; reference openvoice/models.py:272-291, modules.py:296-306) ------
  * Channels-last bf16 activations (B, L, C): C contiguous, rows dense.  bf16 values are passed as uint16_t bit
  * patterns.  Accumulation and bias are fp32; outputs are rounded to nearest even. */

@@ -219,6 +219,7 @@ SIGNATURES = {
                                              _i, _i, _i, _fp, _fp, _fp]),
     "ov_expand_prior_items_f32": (ctypes.c_int, [_fp, _fp, _i64, _i, _fp, _fp, _fp, _fp, _i64, _i, _fp, _fp, _fp, _fp,
                                                  _i, _i, _i, _i, _i, _fp, _fp]),
+    "ov_expand_prior_rows_f32": (ctypes.c_int, [_fp, _i, _i, _fp, _i64, _fp, _i64, _fp, _fp, _i64, _i64, _fp]),
 }
 
 _lib = None

@@ -276,6 +276,37 @@ class BaseSpeakerTTS(OpenVoiceBaseClass):
             return audio
         audio_io.write(output_path, audio, self.hps.data.sampling_rate)
 
+    # ---- streaming synthesis (tts_live.py) ---------------------------------------------------------------------------
+    def tts_live_pool(self, chunk_frames=60, max_streams_per_launch=32, generator="fp32", *, wavenet=None):
+        """A ``tts_live.TtsLivePool``: many sentences synthesised as streams in shared launches -- ``open(ids,
+        speaker_id, speed=1.0, noise_scale=0.667, noise_scale_w=0.6, sdp_ratio=0.2, seed=None)`` -> handle, ``step()``
+        -> ``{handle: new samples}``.  Each sentence equals its solo ``infer`` with the same ``(seed, stream)`` pair and
+        controls.  ``chunk_frames``: a positive multiple of 15; ``generator`` / ``wavenet``: as for
+        ``ToneColorConverter.live_pool``."""
+        from . import tts_live
+        return tts_live.TtsLivePool(self.model, chunk_frames=chunk_frames, max_streams_per_launch=max_streams_per_launch,
+                                    generator=generator, wavenet=wavenet)
+
+    def tts_stream_from_ids(self, id_sequences, speaker_id, speed=1.0, noise_scale=0.667, noise_scale_w=0.6, *,
+                            seed=None, chunk_frames=60, generator="fp32", wavenet=None):
+        """``tts_from_ids`` as a Python generator of device tensors: sentence 0's samples chunk by chunk as they leave
+        the generator, then ``clone.gap_samples(sr, speed)`` zeros, then sentence 1, and so on.  The first chunk leaves
+        after ``first_audio_frames`` (60 at the default chunk) of the sentence's frames have been through the flow,
+        not after the whole utterance.  Concatenated, the output is ``audio_numpy_concat`` of the per-sentence
+        (``batched=False``) ``tts_from_ids(..., seed=seed)`` outputs: sentence ``i`` runs on stream ``k + i`` of ``seed``
+        (``noise.per_item``; None: one seed drawn from torch's generator) -- bit for bit with direct kernels, within
+        1e-4 with the default ones.  ``chunk_frames`` / ``generator`` / ``wavenet``: as for ``tts_live_pool``."""
+        from . import tts_live
+        pool = tts_live.TtsLivePool(self.model, chunk_frames=chunk_frames, max_streams_per_launch=2,
+                                    generator=generator, wavenet=wavenet)
+        return tts_live.stream_sentences(pool, id_sequences, int(speaker_id), speed, noise_scale, noise_scale_w, seed,
+                                         self.hps.data.sampling_rate)
+
+    def tts_stream(self, text, speaker, language="English", speed=1.0, **kwargs):
+        """``tts_stream_from_ids`` of a text (``text_to_ids``: the text half of ``tts``)."""
+        return self.tts_stream_from_ids(self.text_to_ids(text, language), self.hps.speakers[speaker], speed=speed,
+                                        **kwargs)
+
 
 def intersperse(lst, item):
     """reference: openvoice/commons.py:22-25."""

@@ -345,6 +345,41 @@ class VoiceCloner:
                     for t, spk, s, g, lang, spd, r in zip(texts, *cols)]
         return self.speak_ids_many(requests, generator=generator, mixed=mixed, **kwargs)
 
+    def speak_stream_ids(self, id_sequences, speaker, src_se, tgt_se, speed=1.0, *, seed=None, tau=0.3, out_sr=None,
+                         chunk_frames=60, live_chunk_frames=15, generator="fp32", wavenet=None, noise_scale=0.667,
+                         noise_scale_w=0.6):
+        """``speak_ids`` as a Python generator of device tensors: every chunk of ``tts_stream_from_ids`` (gaps
+        included) is pushed into one stream of a converter ``LivePool`` (``sr_in`` = the TTS model's rate where the two
+        differ, ``sr_out=out_sr``) and what that stream returns is yielded; the stream is closed at the end.
+        Concatenated, the output equals ``converter.convert_long(joined, src_se, tgt_se, seed=seed, tau=tau, sr=the TTS
+        rate, out_sr=out_sr)`` of the concatenated ``tts_stream_from_ids(..., seed=seed)`` output (bit for bit with
+        direct kernels and equal rates; within the rates' bar otherwise).  ``seed``: the TTS sentences take streams
+        ``k + i`` of it, the converter's posterior noise stream ``k`` (purpose 0); None: nothing is reproducible.
+        ``chunk_frames`` / ``live_chunk_frames``: the chunk of the synthesis / of the conversion stream."""
+        conv = self.converter
+        chunks = self.tts.tts_stream_from_ids(id_sequences, self._speaker_id(speaker), speed=speed,
+                                              noise_scale=noise_scale, noise_scale_w=noise_scale_w, seed=seed,
+                                              chunk_frames=chunk_frames, generator=generator, wavenet=wavenet)
+        msr = int(conv.hps.data.sampling_rate)
+        pool = conv.live_pool(tau=tau, chunk_frames=live_chunk_frames, max_streams_per_launch=1, generator=generator,
+                              wavenet=wavenet)
+        from . import noise as noise_mod
+        h = pool.open(src_se, tgt_se, sr_in=None if self.tts_sr == msr else self.tts_sr, sr_out=out_sr,
+                      **noise_mod.kw(seed))
+        for chunk in chunks:
+            pool.push(h, chunk)
+            o = pool.step().get(h)
+            if o is not None and o.numel():
+                yield o
+        pool.close(h)
+        o = pool.step().get(h)
+        if o is not None and o.numel():
+            yield o
+
+    def speak_stream(self, text, speaker, src_se, tgt_se, language="English", speed=1.0, **kwargs):
+        """``speak_stream_ids`` of a text (``BaseSpeakerTTS.text_to_ids``)."""
+        return self.speak_stream_ids(self.tts.text_to_ids(text, language), speaker, src_se, tgt_se, speed=speed, **kwargs)
+
     def speak(self, text, speaker, src_se, tgt_se, language="English", speed=1.0, out_sr=None, output_path=None,
               noise_w=None, noise_z=None, noise=None, generator="fp32", **kwargs):
         """``speak_many`` of one text."""

@@ -12,47 +12,15 @@
 #include <cstdint>
 
 #include "openvoice_amd.h"
+#include "philox_normal.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using ovn::f32x4;
 
 constexpr int kThreads = 256;
 constexpr int64_t kMaxFrame = (int64_t)1 << 34;     // frames t < 2^34: the Philox block t / 4 is one 32-bit word
 constexpr int kMaxChunksPerRecord = 4096;           // grid.x bound; larger slabs take further passes
-
-__device__ inline void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                     uint32_t r[4]) {
-#pragma unroll
-  for (int round = 0; round < 10; ++round) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  r[0] = c0, r[1] = c1, r[2] = c2, r[3] = c3;
-}
-
-// Box-Muller on one pair of words.  u1 = (x + 0.5) 2^-24 with x = ra >> 8 is exact in fp32 for x < 2^23; for the upper
-// half 1 - u1 = ((2^24 - 1 - x) + 0.5) 2^-24 is, so the logarithm goes through log1p there (near u1 = 1, where the
-// radius is small, rounding u1 itself would lose all of it).  The angle is taken in half turns: 2 u2 is exact.
-__device__ inline void box_muller(uint32_t ra, uint32_t rb, float& even, float& odd) {
-  const uint32_t x = ra >> 8;
-  float ln;
-  if (x < (1u << 23))
-    ln = logf(((float)x + 0.5f) * 0x1p-24f);
-  else
-    ln = log1pf(-(((float)(0xFFFFFFu - x) + 0.5f) * 0x1p-24f));
-  const float radius = sqrtf(-2.f * ln);
-  float s, c;
-  sincospif((float)(rb >> 8) * 0x1p-23f, &s, &c);
-  even = radius * c;
-  odd = radius * s;
-}
 
 // Compute-light and store-bound: one thread owns one Philox block = four consecutive frames of one channel, lanes run
 // along frames (then channels, so that the few blocks of a live chunk still fill a workgroup).  The four values are
@@ -74,16 +42,7 @@ __global__ __launch_bounds__(kThreads) void normal_philox_kernel(const int64_t* 
   const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)((uint64_t)seed >> 32);
   for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < total; i += (uint64_t)gridDim.x * kThreads) {
     const uint64_t c = i / nblocks, q = q0 + (i - c * nblocks);
-    uint32_t r[4];
-    philox4x32_10((uint32_t)q, (uint32_t)c, (uint32_t)strm, (uint32_t)purpose, k0, k1, r);
-    f32x4 v;
-    {
-      float a, b;
-      box_muller(r[0], r[1], a, b);
-      v[0] = a, v[1] = b;
-      box_muller(r[2], r[3], a, b);
-      v[2] = a, v[3] = b;
-    }
+    const f32x4 v = ovn::normal_block((uint32_t)q, (uint32_t)c, (uint32_t)strm, (uint32_t)purpose, k0, k1);
     const int64_t rel = (int64_t)(q << 2) - f0;                    // slab column of the block's first frame (>= -3)
     const int64_t at = dst_off + (int64_t)c * dst_ld + rel;        // element of dst; used only where rel + e is in [0, nf)
     if (rel >= 0 && rel + 4 <= nf && (((reinterpret_cast<uintptr_t>(dst) >> 2) + (uint64_t)at) & 3) == 0) {

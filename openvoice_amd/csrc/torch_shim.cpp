@@ -496,6 +496,7 @@ TORCH_LIBRARY(openvoice_amd, m) {
   bind_device<&ov_expand_prior_f32>(m, "expand_prior_f32");
   bind_device<&ov_duration_items_f32>(m, "duration_items_f32");
   bind_device<&ov_expand_prior_items_f32>(m, "expand_prior_items_f32");
+  bind_device<&ov_expand_prior_rows_f32>(m, "expand_prior_rows_f32");
   bind_device<&ov_conv_post_tanh_bf16>(m, "conv_post_tanh_bf16");
   bind_device<&ov_split3_from_f32>(m, "split3_from_f32");
   bind_device<&ov_split3_to_f32>(m, "split3_to_f32");

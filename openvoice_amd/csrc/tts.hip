@@ -11,6 +11,7 @@
 #include <cstdint>
 
 #include "openvoice_amd.h"
+#include "prior_expand.h"
 
 namespace ovk {
 
@@ -422,15 +423,7 @@ __global__ __launch_bounds__(256) void expand_prior_kernel(const float* __restri
   if (t >= Ty) return;
   const int32_t* cb = cum + (int64_t)b * ldx;
   const int xl = (int)min((int64_t)Tx, x_len[b]);
-  int j = -1;
-  if (t < y_len[b] && xl > 0 && t < cb[xl - 1]) {
-    int lo = 0, hi = xl - 1;            // first j with cum[j] > t
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (cb[mid] > t) hi = mid; else lo = mid + 1;
-    }
-    j = lo;
-  }
+  const int j = t < y_len[b] ? ovp::token_of_frame(cb, xl, t) : -1;
   if (attn) {
     float* ar = attn + ((int64_t)b * Ty + t) * Tx;
     for (int i = 0; i < Tx; ++i) ar[i] = i == j ? 1.f : 0.f;
@@ -441,7 +434,7 @@ __global__ __launch_bounds__(256) void expand_prior_kernel(const float* __restri
     const float lg = j >= 0 ? logs_tok[(int64_t)b * tok_bstride + (int64_t)c * ldx + j] : 0.f;
     if (m_p) m_p[o] = m;
     if (logs_p) logs_p[o] = lg;
-    z_p[o] = m + noise[(int64_t)b * noise_bstride + (int64_t)c * ldn + t] * expf(lg) * noise_scale;
+    z_p[o] = ovp::prior_sample(m, noise[(int64_t)b * noise_bstride + (int64_t)c * ldn + t], lg, noise_scale);
   }
 }
 

@@ -263,53 +263,58 @@ class _Live:
         return None
 
 
-class LivePool:
-    """Many live streams stepped together (see the module docstring).  ``open(src_se, tgt_se, noise=None)`` -> handle;
-    ``push(h, samples)`` buffers; ``step()`` runs every stream with a ready chunk (and every closed stream's remaining
-    rounds) -> ``{handle: newly finished samples}`` (device tensors); ``close(h)`` marks the end of h's input.  Rounds:
-    every ready stream advances by one chunk per round, each unit runs its streams' buffers in launches of up to
-    ``max_streams_per_launch`` rows grouped by buffer width (steady-state streams share one width; a stream's first
-    rounds and its end run narrower), padded up to the ``launch_ladder`` sizes.  ``tau`` is the pool's default;
-    ``open(..., tau=)`` gives a stream its own, kept for life, and the rows of a posterior-encoder launch each carry
-    their stream's (``ov_conv1d_params.scale_b``; a launch whose rows agree is the scalar launch it always was).
-    Live units run eagerly, never from a captured graph.  ``generator``: ``"fp32"`` (default) or ``"bf16"`` -- the
-    kernels of the ``g`` units (module docstring); everything else, the latency and the state size included, is the
-    same for both.  ``wavenet``: None (follow ``ConverterEngine.use_bf16_wavenet``), ``"fp32"`` or ``"bf16"`` -- the
-    WaveNet layers of the ``q`` / ``f`` / ``r`` units on ``ov_wn_layer_bf16`` (bf16 matrix operands, fp32 state); the
-    layer's results do not depend on tile, row or batch, so a stream still equals the one-pass conversion with the same
-    keyword."""
+class UnitPool:
+    """What every pool of cascaded units shares, whatever feeds its first unit (``LivePool``: spectrogram frames of
+    pushed audio; ``tts_live.TtsLivePool``: the prior sample of a sentence): the unit table's memory layout (batch
+    slabs, one arena slot per stream with two state halves per unit), the record-driven carries, the launch ladder and
+    the unit launches themselves.  A stream object brings ``slot``, ``cas`` (its ``Cascade``), ``stored`` / ``s0`` /
+    ``half`` per unit and ``conds`` (the conditioning rows its units read).  ``units``: a slice of ``live_units``;
+    ``engine``: the ``ConverterEngine`` whose launches the units are."""
 
-    def __init__(self, model, tau=0.3, chunk_frames=DEFAULT_CHUNK_FRAMES,
-                 max_streams_per_launch=DEFAULT_LIVE_STREAMS_PER_LAUNCH, n_fft=1024, hop=256, model_sr=rates.MODEL_RATE,
-                 generator="fp32", wavenet=None):
-        self.model, self.tau = model, float(tau)
-        self._tau_rows = {}         # taus of a launch's rows -> their float32 device vector (uploaded once)
+    def __init__(self, engine, cfg, units, chunk_frames, max_streams_per_launch, generator="fp32", wavenet=None):
         self.generator = check_generator(generator)
         # the WaveNet layers' kernels of the q / f / r units: None follows the engine's use_bf16_wavenet switch
         self.wavenet = _lib.check_wavenet(wavenet, optional=True)
-        self.cfg = model.model_cfg
+        self.cfg = cfg
         self.chunk = check_chunk(self.cfg, chunk_frames)
-        eng = model.engine()
-        if getattr(eng, "_bf16_on", False) or getattr(eng, "_split3_on", False):
+        if getattr(engine, "_bf16_on", False) or getattr(engine, "_split3_on", False):
             raise ValueError("live streams run the fp32 generator only: turn use_bf16_generator / enable_split_bf16x3 off")
-        self.engine = eng
-        self.device = eng.device
-        self.n_fft, self.hop, self.pad = int(n_fft), int(hop), (int(n_fft) - int(hop)) // 2
-        self.bins = self.n_fft // 2 + 1
+        self.engine = engine
+        self.device = engine.device
         self.inter = self.cfg["inter_channels"]
         self.spf = samples_per_frame(self.cfg)
         self.ladder = launch_ladder(max_streams_per_launch)
         self.M = self.ladder[-1]
-        self.units = live_units(self.cfg)
-        self.latency_samples = live_latency_samples(self.cfg, self.chunk, self.n_fft, self.hop)
+        self.units = units
         self._layout()
-        self._streams, self._retired, self._next = {}, set(), 0
         self._free_slots, self._slots = [], 0
         self.mem = None
-        self.model_sr = int(model_sr)
-        self._rin, self._rout = rates.ResamplerBank(self.device), rates.ResamplerBank(self.device)
-        self._rin_owner = {}        # input resampler key -> stream
-        self._rout_ending = []      # output resampler keys of streams that finished in this step
+
+    def _take_slot(self):
+        """An arena slot for a new stream; the arena doubles when none is free (streams already open keep theirs)."""
+        if not self._free_slots:
+            grown = max(1, 2 * self._slots)
+            self._free_slots = list(range(grown - 1, self._slots - 1, -1)) + self._free_slots
+            self._slots = grown
+            self._ensure_mem()
+        return self._free_slots.pop()
+
+    def _run_units(self, plans):
+        """The units of one round after its feed: ``plans`` = [(handle, stream, pieces of ``Cascade.round``)] ->
+        ``{handle: the last unit's new output columns}``."""
+        outputs, acc = {}, 0
+        K = len(self.units)
+        for h, st, pieces in plans:
+            n = sum((e1 - e0) * self.units[k]["stride"] for k, _, _, e0, e1 in pieces if k == K - 1)
+            outputs[st] = [acc, 0, h]
+            acc += n
+        out = torch.empty(acc, dtype=torch.float32, device=self.device)
+        for k in range(K):
+            items = [(st, p) for h, st, pieces in plans for p in pieces if p[0] == k]
+            if not items:
+                continue
+            self._run_unit(k, items, outputs, out)
+        return {o[2]: out[o[0]:o[0] + o[1]] for st, o in outputs.items() if o[1]}
 
     # ---- memory layout --------------------------------------------------------------------------------------------
     def _layout(self):
@@ -354,15 +359,6 @@ class LivePool:
             so += 2 * self.rows[k] * self.cap[k]
         self.slot_elems = so
 
-    def state_bytes_per_stream(self):
-        """Device bytes one open stream adds: its arena slot (every unit's two state halves) and its conditioning rows
-        (the WaveNet gate biases of the posterior encoder and of both flow directions, the generator's cond bias).  Its
-        waveform buffer (>= 256 KiB, trimmed to the frames still to come) and an explicit noise tensor come on top.
-        5.6 MB at 15 frames for the released configurations."""
-        H, cfg = self.cfg["hidden_channels"], self.cfg
-        conds = 2 * H * ENC_Q_LAYERS + 2 * N_FLOWS * 2 * H * FLOW_LAYERS + cfg["upsample_initial_channel"]
-        return 4 * (self.slot_elems + conds)
-
     def _state(self, st, k, half):
         return self.arena_off + st.slot * self.slot_elems + self.state_off[k] + half * self.rows[k] * self.cap[k]
 
@@ -373,6 +369,149 @@ class LivePool:
             if self.mem is not None:
                 grown[:self.mem.numel()].copy_(self.mem)
             self.mem = grown
+
+    # ---- stepping -------------------------------------------------------------------------------------------------
+    def _carry(self, recs, dst=None):
+        if not recs:
+            return
+        dst = self.mem if dst is None else dst
+        table = torch.tensor(recs, dtype=torch.int64).to(self.device)
+        for i in range(0, len(recs), 65535):
+            _lib.call("ov_carry_rows_f32", table[i:i + 65535], min(65535, len(recs) - i), self.mem, self.mem.numel(),
+                      dst, dst.numel())
+
+    def _batches(self, items, key):
+        """Items grouped by ``key`` in order, in launches of up to M, each padded up to a ladder size."""
+        groups = {}
+        for it in items:
+            groups.setdefault(key(it), []).append(it)
+        for kv, its in groups.items():
+            for i in range(0, len(its), self.M):
+                chunk = its[i:i + self.M]
+                B = min(b for b in self.ladder if b >= len(chunk))
+                yield kv, chunk, B
+
+    def _run_unit(self, k, items, outputs, out):
+        """Unit k for ``items`` = [(stream, (k, b0, end, e0, e1))], per launch: one carry gathers the rows' buffers
+        (and shifts their kept history into the other state half), the unit runs, one carry scatters the kept output
+        columns into unit k + 1's state (the last unit's into ``out``) before the next launch reuses the slab."""
+        u = self.units[k]
+        for L, chunk, B in self._batches(items, key=lambda it: it[1][2] - it[1][1]):
+            rows = chunk + [chunk[-1]] * (B - len(chunk))
+            R, ldi = self.rows[k], self.ld_in[k]
+            gather, shift = [], []
+            for r, (st, (_, b0, end, e0, e1)) in enumerate(rows):
+                src = self._state(st, k, st.half[k])
+                gather.append((src + (b0 - st.s0[k]), self.in_off[k] + r * R * ldi, R, L, self.cap[k], ldi))
+                if r < len(chunk):
+                    nb = _start(u, e1)
+                    keep = st.stored[k] - nb
+                    if keep > 0:
+                        shift.append((src + (nb - st.s0[k]), self._state(st, k, 1 - st.half[k]), R, keep, self.cap[k],
+                                      self.cap[k]))
+            self._carry(gather + shift)
+            for st, (_, b0, end, e0, e1) in chunk:
+                st.s0[k] = _start(u, e1)
+                st.half[k] ^= 1
+            self._launch(k, rows, B, L)
+            recs = self._scatter(k, chunk, L, outputs)
+            if k == len(self.units) - 1:
+                self._carry(recs, dst=out)
+            else:
+                self._carry(recs)
+
+    def _launch(self, k, rows, B, L):
+        with self.engine.wavenet_scope(self.wavenet):
+            self._launch_unit(k, rows, B, L)
+
+    def _launch_unit(self, k, rows, B, L):
+        u, eng, mem = self.units[k], self.engine, self.mem
+        bf16 = u["kind"] == "g" and self.generator == "bf16"
+        ws = (eng.live_workspace_bf16 if bf16 else eng.live_workspace)((u["name"], self.width[k]), B, self.width[k],
+                                                                       stage=u["stage"])
+        R, ldi, ldo, C = self.rows[k], self.ld_in[k], self.ld_out[k], self.cout[k]
+        x = mem[self.in_off[k]:]
+        out = mem[self.out_off[k]:]
+        cat = lambda t: torch.cat([t_ for t_ in t])
+        if u["kind"] == "q":
+            self._launch_posterior(k, rows, B, L, ws)
+        elif u["kind"] in ("f", "r"):
+            key = "src" if u["kind"] == "f" else "tgt"
+            conds = [torch.cat([st.conds[key][f] for st, _ in rows]) for f in range(len(rows[0][0].conds[key]))]
+            eng.live_flow(x, out, B, L, conds, u["kind"] == "r", ws)
+        elif bf16:
+            cond = cat([st.conds["d16"] for st, _ in rows]) if u["stage"] == 0 else None
+            eng.live_generator_stage_bf16(u["stage"], x, ldi, R * ldi, out, B, L, ws, cond_d=cond)
+        else:
+            cond = cat([st.conds["d"] for st, _ in rows]) if u["stage"] == 0 else None
+            eng.live_generator_stage(u["stage"], x, ldi, R * ldi, out, B, L, ws, cond_d=cond)
+
+    def _scatter(self, k, chunk, L, outputs):
+        """Records moving unit k's kept output columns of a launch's rows into unit k + 1's state (or into the round's
+        output)."""
+        u = self.units[k]
+        s = u["stride"]
+        last = k == len(self.units) - 1
+        recs = []
+        C = self.cout[k]
+        ldo = L * s if u["kind"] == "g" else self.ld_out[k]
+        for r, (st, (_, b0, end, e0, e1)) in enumerate(chunk):
+            src = self.out_off[k] + r * C * ldo + (e0 - b0) * s
+            n = (e1 - e0) * s
+            if last:
+                o = outputs[st]
+                recs.append((src, o[0] + o[1], 1, n, ldo, n))
+                o[1] += n
+                continue
+            col = st.stored[k + 1] - st.s0[k + 1]
+            if col + n > self.cap[k + 1]:
+                raise RuntimeError(f"live stream state overflow (unit {self.units[k + 1]['name']})")
+            recs.append((src, self._state(st, k + 1, st.half[k + 1]) + col, C, n, ldo, self.cap[k + 1]))
+            st.stored[k + 1] += n
+        return recs
+
+
+class LivePool(UnitPool):
+    """Many live streams stepped together (see the module docstring).  ``open(src_se, tgt_se, noise=None)`` -> handle;
+    ``push(h, samples)`` buffers; ``step()`` runs every stream with a ready chunk (and every closed stream's remaining
+    rounds) -> ``{handle: newly finished samples}`` (device tensors); ``close(h)`` marks the end of h's input.  Rounds:
+    every ready stream advances by one chunk per round, each unit runs its streams' buffers in launches of up to
+    ``max_streams_per_launch`` rows grouped by buffer width (steady-state streams share one width; a stream's first
+    rounds and its end run narrower), padded up to the ``launch_ladder`` sizes.  ``tau`` is the pool's default;
+    ``open(..., tau=)`` gives a stream its own, kept for life, and the rows of a posterior-encoder launch each carry
+    their stream's (``ov_conv1d_params.scale_b``; a launch whose rows agree is the scalar launch it always was).
+    Live units run eagerly, never from a captured graph.  ``generator``: ``"fp32"`` (default) or ``"bf16"`` -- the
+    kernels of the ``g`` units (module docstring); everything else, the latency and the state size included, is the
+    same for both.  ``wavenet``: None (follow ``ConverterEngine.use_bf16_wavenet``), ``"fp32"`` or ``"bf16"`` -- the
+    WaveNet layers of the ``q`` / ``f`` / ``r`` units on ``ov_wn_layer_bf16`` (bf16 matrix operands, fp32 state); the
+    layer's results do not depend on tile, row or batch, so a stream still equals the one-pass conversion with the same
+    keyword."""
+
+    def __init__(self, model, tau=0.3, chunk_frames=DEFAULT_CHUNK_FRAMES,
+                 max_streams_per_launch=DEFAULT_LIVE_STREAMS_PER_LAUNCH, n_fft=1024, hop=256, model_sr=rates.MODEL_RATE,
+                 generator="fp32", wavenet=None):
+        self.model, self.tau = model, float(tau)
+        self._tau_rows = {}         # taus of a launch's rows -> their float32 device vector (uploaded once)
+        self.n_fft, self.hop, self.pad = int(n_fft), int(hop), (int(n_fft) - int(hop)) // 2
+        self.bins = self.n_fft // 2 + 1
+        check_generator(generator), _lib.check_wavenet(wavenet, optional=True), check_chunk(model.model_cfg, chunk_frames)
+        super().__init__(model.engine(), model.model_cfg, live_units(model.model_cfg), chunk_frames,
+                         max_streams_per_launch, generator=generator, wavenet=wavenet)
+        self.latency_samples = live_latency_samples(self.cfg, self.chunk, self.n_fft, self.hop)
+        self._streams, self._retired, self._next = {}, set(), 0
+        self.model_sr = int(model_sr)
+        self._rin, self._rout = rates.ResamplerBank(self.device), rates.ResamplerBank(self.device)
+        self._rin_owner = {}        # input resampler key -> stream
+        self._rout_ending = []      # output resampler keys of streams that finished in this step
+
+    def state_bytes_per_stream(self):
+        """Device bytes one open stream adds: its arena slot (every unit's two state halves) and its conditioning rows
+        (the WaveNet gate biases of the posterior encoder and of both flow directions, the generator's cond bias).  Its
+        waveform buffer (>= 256 KiB, trimmed to the frames still to come) and an explicit noise tensor come on top.
+        5.6 MB at 15 frames for the released configurations."""
+        H, cfg = self.cfg["hidden_channels"], self.cfg
+        conds = 2 * H * ENC_Q_LAYERS + 2 * N_FLOWS * 2 * H * FLOW_LAYERS + cfg["upsample_initial_channel"]
+        return 4 * (self.slot_elems + conds)
 
     # ---- streams --------------------------------------------------------------------------------------------------
     @property
@@ -391,12 +530,7 @@ class LivePool:
         if not isinstance(tau, float):
             raise _lib.OvError("LivePool.open: tau is one number per stream")
         sr_in, sr_out = rates.check_rate(sr_in, "sr_in"), rates.check_rate(sr_out, "sr_out")
-        if not self._free_slots:                 # the arena doubles: streams already open keep their slots
-            grown = max(1, 2 * self._slots)
-            self._free_slots = list(range(grown - 1, self._slots - 1, -1)) + self._free_slots
-            self._slots = grown
-            self._ensure_mem()
-        slot = self._free_slots.pop()
+        slot = self._take_slot()
         h = self._next
         self._next += 1
         st = _Live(self, slot, src_se, tgt_se, noise, seed=seed)
@@ -465,27 +599,6 @@ class LivePool:
             else:
                 self._rout.drop(st.rout)
 
-    # ---- stepping -------------------------------------------------------------------------------------------------
-    def _carry(self, recs, dst=None):
-        if not recs:
-            return
-        dst = self.mem if dst is None else dst
-        table = torch.tensor(recs, dtype=torch.int64).to(self.device)
-        for i in range(0, len(recs), 65535):
-            _lib.call("ov_carry_rows_f32", table[i:i + 65535], min(65535, len(recs) - i), self.mem, self.mem.numel(),
-                      dst, dst.numel())
-
-    def _batches(self, items, key):
-        """Items grouped by ``key`` in order, in launches of up to M, each padded up to a ladder size."""
-        groups = {}
-        for it in items:
-            groups.setdefault(key(it), []).append(it)
-        for kv, its in groups.items():
-            for i in range(0, len(its), self.M):
-                chunk = its[i:i + self.M]
-                B = min(b for b in self.ladder if b >= len(chunk))
-                yield kv, chunk, B
-
     def _feed(self, jobs):
         """New posterior-encoder frames of every ready stream: the spectrogram of frames [n_q, n_q + nf) of its
         waveform (bit-identical to the whole file's) and its noise into the staging rows, then carried onto the end of
@@ -529,62 +642,11 @@ class LivePool:
                 st.stored[k] += nf
             self._carry(carry)
 
-    def _run_unit(self, k, items, outputs, out):
-        """Unit k for ``items`` = [(stream, (k, b0, end, e0, e1))], per launch: one carry gathers the rows' buffers
-        (and shifts their kept history into the other state half), the unit runs, one carry scatters the kept output
-        columns into unit k + 1's state (the last unit's into ``out``) before the next launch reuses the slab."""
-        u = self.units[k]
-        for L, chunk, B in self._batches(items, key=lambda it: it[1][2] - it[1][1]):
-            rows = chunk + [chunk[-1]] * (B - len(chunk))
-            R, ldi = self.rows[k], self.ld_in[k]
-            gather, shift = [], []
-            for r, (st, (_, b0, end, e0, e1)) in enumerate(rows):
-                src = self._state(st, k, st.half[k])
-                gather.append((src + (b0 - st.s0[k]), self.in_off[k] + r * R * ldi, R, L, self.cap[k], ldi))
-                if r < len(chunk):
-                    nb = _start(u, e1)
-                    keep = st.stored[k] - nb
-                    if keep > 0:
-                        shift.append((src + (nb - st.s0[k]), self._state(st, k, 1 - st.half[k]), R, keep, self.cap[k],
-                                      self.cap[k]))
-            self._carry(gather + shift)
-            for st, (_, b0, end, e0, e1) in chunk:
-                st.s0[k] = _start(u, e1)
-                st.half[k] ^= 1
-            self._launch(k, rows, B, L)
-            recs = self._scatter(k, chunk, L, outputs)
-            if k == len(self.units) - 1:
-                self._carry(recs, dst=out)
-            else:
-                self._carry(recs)
-
-    def _launch(self, k, rows, B, L):
-        with self.engine.wavenet_scope(self.wavenet):
-            self._launch_unit(k, rows, B, L)
-
-    def _launch_unit(self, k, rows, B, L):
-        u, eng, mem = self.units[k], self.engine, self.mem
-        bf16 = u["kind"] == "g" and self.generator == "bf16"
-        ws = (eng.live_workspace_bf16 if bf16 else eng.live_workspace)((u["name"], self.width[k]), B, self.width[k],
-                                                                       stage=u["stage"])
-        R, ldi, ldo, C = self.rows[k], self.ld_in[k], self.ld_out[k], self.cout[k]
-        x = mem[self.in_off[k]:]
-        out = mem[self.out_off[k]:]
-        cat = lambda t: torch.cat([t_ for t_ in t])
-        if u["kind"] == "q":
-            cond = cat([st.conds["q"] for st, _ in rows])
-            eng.live_posterior(x, ldi, R * ldi, mem[self.in_off[k] + self.bins * ldi:], R * ldi, out, ldo, C * ldo, B,
-                               L, cond, self._launch_tau(rows), ws)
-        elif u["kind"] in ("f", "r"):
-            key = "src" if u["kind"] == "f" else "tgt"
-            conds = [torch.cat([st.conds[key][f] for st, _ in rows]) for f in range(len(rows[0][0].conds[key]))]
-            eng.live_flow(x, out, B, L, conds, u["kind"] == "r", ws)
-        elif bf16:
-            cond = cat([st.conds["d16"] for st, _ in rows]) if u["stage"] == 0 else None
-            eng.live_generator_stage_bf16(u["stage"], x, ldi, R * ldi, out, B, L, ws, cond_d=cond)
-        else:
-            cond = cat([st.conds["d"] for st, _ in rows]) if u["stage"] == 0 else None
-            eng.live_generator_stage(u["stage"], x, ldi, R * ldi, out, B, L, ws, cond_d=cond)
+    def _launch_posterior(self, k, rows, B, L, ws):
+        R, ldi, ldo, C, mem = self.rows[k], self.ld_in[k], self.ld_out[k], self.cout[k], self.mem
+        cond = torch.cat([st.conds["q"] for st, _ in rows])
+        self.engine.live_posterior(mem[self.in_off[k]:], ldi, R * ldi, mem[self.in_off[k] + self.bins * ldi:], R * ldi,
+                                   mem[self.out_off[k]:], ldo, C * ldo, B, L, cond, self._launch_tau(rows), ws)
 
     def _launch_tau(self, rows):
         """``tau`` of a posterior-encoder launch: the number when its rows agree, else their per-row device vector --
@@ -600,30 +662,6 @@ class LivePool:
             vec = self._tau_rows[key] = torch.tensor(tau, dtype=torch.float32).to(self.device)
         return vec
 
-    def _scatter(self, k, chunk, L, outputs):
-        """Records moving unit k's kept output columns of a launch's rows into unit k + 1's state (or into the round's
-        output)."""
-        u = self.units[k]
-        s = u["stride"]
-        last = k == len(self.units) - 1
-        recs = []
-        C = self.cout[k]
-        ldo = L * s if u["kind"] == "g" else self.ld_out[k]
-        for r, (st, (_, b0, end, e0, e1)) in enumerate(chunk):
-            src = self.out_off[k] + r * C * ldo + (e0 - b0) * s
-            n = (e1 - e0) * s
-            if last:
-                o = outputs[st]
-                recs.append((src, o[0] + o[1], 1, n, ldo, n))
-                o[1] += n
-                continue
-            col = st.stored[k + 1] - st.s0[k + 1]
-            if col + n > self.cap[k + 1]:
-                raise RuntimeError(f"live stream state overflow (unit {self.units[k + 1]['name']})")
-            recs.append((src, self._state(st, k + 1, st.half[k + 1]) + col, C, n, ldo, self.cap[k + 1]))
-            st.stored[k + 1] += n
-        return recs
-
     @torch.no_grad()
     def _round(self, streams):
         """One round: every stream in ``streams`` ([(h, st, new_frames)]) advances by one chunk (or its end)."""
@@ -636,19 +674,7 @@ class LivePool:
         for st, nf, f0 in jobs:
             if not st.closed:
                 st.trim()
-        total, outputs, acc = 0, {}, 0
-        K = len(self.units)
-        for h, st, pieces in plans:
-            n = sum((e1 - e0) * self.units[k]["stride"] for k, _, _, e0, e1 in pieces if k == K - 1)
-            outputs[st] = [acc, 0, h]
-            acc += n
-        out = torch.empty(acc, dtype=torch.float32, device=self.device)
-        for k in range(K):
-            items = [(st, p) for h, st, pieces in plans for p in pieces if p[0] == k]
-            if not items:
-                continue
-            self._run_unit(k, items, outputs, out)
-        return {o[2]: out[o[0]:o[0] + o[1]] for st, o in outputs.items() if o[1]}
+        return self._run_units(plans)
 
     @torch.no_grad()
     def step(self):

@@ -177,41 +177,28 @@ class TtsEngine:
     def _wavenet_cores(self):
         return (self.core,)
 
-    @wavenet_keyword
     @torch.no_grad()
     @on_own_device
-    def infer(self, tokens, lengths, sid, noise_scale=1.0, length_scale=1.0, noise_scale_w=1.0, sdp_ratio=0.2,
-              max_len=None, noise_w=None, noise_z=None, return_attn=True, skip_padding=False, *, seed=None,
-              generator="fp32"):
-        """Same contract as the reference (models.py:467-490): returns
-        ``(o [B,1,256*Ty'], attn [B,1,Ty,Tx], y_mask [B,1,Ty], (z, z_p, m_p, logs_p) [B,192,Ty])``.
-        ``noise_w`` [B,2,Tx] / ``noise_z`` [B,192,>=Ty] replace the reference's two RNG draws when given.
-        ``seed`` (instead of them): both draws counter-based (``noise.py``), row ``b`` of an int ``s`` on stream
-        ``(s, b)`` (or one seed / pair per row): ``noise_w`` is purpose 1 over the token positions ``[0, Tx)``,
-        ``noise_z`` purpose 2 over the frames ``[0, Ty)``, generated straight into the workspace rows once ``Ty`` is
-        known -- nobody has to guess a bound for it.
-        ``skip_padding``: the generator computes only ``y_length + core.limit_margin(B, Ty)`` frames (16-20) of each
-        utterance of a padded batch
-        (valid samples bit-identical, the padded tail of ``o`` zero; ``ConverterEngine.voice_conversion``).
-        ``generator``: ``"fp32"`` (default) or ``"bf16"`` -- the generator alone on the bf16 channels-last kernels
-        (``bf16.GeneratorBf16``, built on first use; ``use_bf16_generator`` is neither read nor set), everything before
-        it unchanged: ``attn``, ``y_mask`` and the four latents are the fp32 call's bits.  With ``skip_padding`` the
-        padded batch then runs as a few dense length groups (``GeneratorBf16.decode_groups``: valid samples the bits of
-        the padded bf16 run, the tail zero), without it as one padded ``GeneratorBf16.decode``.
-        ``noise_scale`` / ``length_scale`` / ``noise_scale_w`` / ``sdp_ratio``: each one number for the batch, or a
-        sequence / tensor with one value per item (``item_controls``).  Four plain numbers are the scalar launches
-        (``ov_duration_f32``, ``ov_expand_prior_f32``); otherwise all four become ``[B]`` device vectors and
-        ``ov_duration_items_f32`` / ``ov_expand_prior_items_f32`` run in their place: item ``b`` gets the durations,
-        alignment and prior that a call with item ``b``'s four numbers gives it, bit for bit; everything downstream
-        (flow, generator, ``skip_padding``, ``seed``) is per item already."""
-        _lib.check_generator(generator)
+    def front(self, tokens, lengths, sid, noise_scale=1.0, length_scale=1.0, noise_scale_w=1.0, sdp_ratio=0.2,
+              noise_w=None, *, seed=None):
+        """The token-rate front half of ``infer`` (models.py:468-479): text encoder, both duration predictors and the
+        duration arithmetic, for a padded batch.  Everything here runs at the token rate and nothing waits for the host;
+        the caller makes the one sync when it reads ``y_len``.  Arguments as for ``infer`` (``noise_scale`` is only
+        validated and uploaded with the other controls: the expansion applies it).  Returns a dict: ``stats``
+        ``[B, 2 * inter, Lx]`` (``m`` and ``logs`` of every token: the two halves), ``cum`` ``[B, Lx]`` int32 (inclusive
+        prefix sums of the durations), ``y_len`` ``[B]`` int64, ``logw`` ``[B, Lx]``, ``g`` ``[B, gin]`` (the speaker
+        embeddings), ``lengths``, ``B`` / ``Tx`` / ``Lx``, ``items`` (``item_controls``), ``noise_scale_b`` (its device
+        vector or None), ``streams`` (``noise.rows`` of ``seed`` or None) and ``zeros`` (the allocator).  ``infer`` is
+        this followed by the frame-rate back half."""
         dev = self.device
-        noise_mod.exclusive(seed, noise_w=noise_w, noise_z=noise_z)
+        noise_mod.exclusive(seed, noise_w=noise_w)
         check_token_count(tokens.shape[-1])
         items = item_controls(tokens.shape[0], noise_scale, length_scale, noise_scale_w, sdp_ratio)
         if items is not None:       # one host -> device copy: row i is control i of CONTROLS, one value per item
             ctl = torch.tensor([items[name] for name in CONTROLS], dtype=torch.float32).to(dev)
             noise_scale_b, length_scale_b, noise_scale_w_b, sdp_ratio_b = ctl[0], ctl[1], ctl[2], ctl[3]
+        else:
+            noise_scale_b = None
         tokens = tokens.to(dev, torch.int64).contiguous()
         lengths = lengths.to(dev, torch.int64).contiguous()
         sid = sid.to(dev, torch.int64).reshape(-1)
@@ -260,6 +247,7 @@ class TtsEngine:
         self._dds(self.sdp_convs, xs, t1, t2, mask, B, Fs, Tx, Lx)
         self._conv(self.sdp_proj, xs, Fs, t1, Fs, B, Tx, Lx, flags=F_MASK_V, mask=mask, mask_bs=Lx)
         xs, t1 = t1, xs                                                         # xs = conditioning of the flows
+        streams = None
         if seed is not None:
             streams = noise_mod.rows(seed, B)
             noise_w = torch.empty(B, 2, Tx, dtype=torch.float32, device=dev)
@@ -290,6 +278,44 @@ class TtsEngine:
         else:
             _lib.call("ov_duration_items_f32", zw, 2 * Lx, self.ea_m, self.ea_logs, dp_out, 32 * Lx, mask, logw, cum,
                       y_len, B, Tx, Lx, sdp_ratio_b, length_scale_b)
+        return dict(stats=stats, cum=cum, y_len=y_len, logw=logw, g=g, lengths=lengths, B=B, Tx=Tx, Lx=Lx, items=items,
+                    noise_scale_b=noise_scale_b, streams=streams, zeros=f)
+
+    @wavenet_keyword
+    @torch.no_grad()
+    @on_own_device
+    def infer(self, tokens, lengths, sid, noise_scale=1.0, length_scale=1.0, noise_scale_w=1.0, sdp_ratio=0.2,
+              max_len=None, noise_w=None, noise_z=None, return_attn=True, skip_padding=False, *, seed=None,
+              generator="fp32"):
+        """Same contract as the reference (models.py:467-490): returns
+        ``(o [B,1,256*Ty'], attn [B,1,Ty,Tx], y_mask [B,1,Ty], (z, z_p, m_p, logs_p) [B,192,Ty])``.
+        ``noise_w`` [B,2,Tx] / ``noise_z`` [B,192,>=Ty] replace the reference's two RNG draws when given.
+        ``seed`` (instead of them): both draws counter-based (``noise.py``), row ``b`` of an int ``s`` on stream
+        ``(s, b)`` (or one seed / pair per row): ``noise_w`` is purpose 1 over the token positions ``[0, Tx)``,
+        ``noise_z`` purpose 2 over the frames ``[0, Ty)``, generated straight into the workspace rows once ``Ty`` is
+        known -- nobody has to guess a bound for it.
+        ``skip_padding``: the generator computes only ``y_length + core.limit_margin(B, Ty)`` frames (16-20) of each
+        utterance of a padded batch
+        (valid samples bit-identical, the padded tail of ``o`` zero; ``ConverterEngine.voice_conversion``).
+        ``generator``: ``"fp32"`` (default) or ``"bf16"`` -- the generator alone on the bf16 channels-last kernels
+        (``bf16.GeneratorBf16``, built on first use; ``use_bf16_generator`` is neither read nor set), everything before
+        it unchanged: ``attn``, ``y_mask`` and the four latents are the fp32 call's bits.  With ``skip_padding`` the
+        padded batch then runs as a few dense length groups (``GeneratorBf16.decode_groups``: valid samples the bits of
+        the padded bf16 run, the tail zero), without it as one padded ``GeneratorBf16.decode``.
+        ``noise_scale`` / ``length_scale`` / ``noise_scale_w`` / ``sdp_ratio``: each one number for the batch, or a
+        sequence / tensor with one value per item (``item_controls``).  Four plain numbers are the scalar launches
+        (``ov_duration_f32``, ``ov_expand_prior_f32``); otherwise all four become ``[B]`` device vectors and
+        ``ov_duration_items_f32`` / ``ov_expand_prior_items_f32`` run in their place: item ``b`` gets the durations,
+        alignment and prior that a call with item ``b``'s four numbers gives it, bit for bit; everything downstream
+        (flow, generator, ``skip_padding``, ``seed``) is per item already."""
+        _lib.check_generator(generator)
+        noise_mod.exclusive(seed, noise_w=noise_w, noise_z=noise_z)
+        fh = self.front(tokens, lengths, sid, noise_scale=noise_scale, length_scale=length_scale,
+                        noise_scale_w=noise_scale_w, sdp_ratio=sdp_ratio, noise_w=noise_w, **noise_mod.kw(seed))
+        dev, f = self.device, fh["zeros"]
+        items, noise_scale_b, streams = fh["items"], fh["noise_scale_b"], fh["streams"]
+        lengths, stats, cum, y_len, logw, g = fh["lengths"], fh["stats"], fh["cum"], fh["y_len"], fh["logw"], fh["g"]
+        B, Tx, Lx, C = fh["B"], fh["Tx"], fh["Lx"], self.inter
         if generator == "bf16":       # the same one sync, carrying every length: decode_groups plans on the host
             y_host = y_len.cpu().tolist()
             Ty = max(y_host)
