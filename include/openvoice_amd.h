@@ -345,6 +345,24 @@ int ov_stitch_window_cores_f32(const float* o_hat, const int64_t* windows, int W
  * multiples of 4, as scalars otherwise; 64-bit offsets.  ABI 2.12. */
 int ov_carry_rows_f32(const int64_t* records, int n_records, const float* src_base, int64_t src_elems, float* dst_base,
                       int64_t dst_elems, ov_stream_t stream);
+/* The seam of a live stream with bounded look-ahead (openvoice_amd/live.py, lookahead_frames=): successive pieces come
+ * from different truncations of the input, so the first x samples of a piece are blended with the samples the previous
+ * round's preview computed for the same positions.  records is a DEVICE int64 [n_records][5] of
+ * (old_off, new_off, dst_off, n, x), in elements, old / new relative to src_base and dst relative to dst_base; w an
+ * fp32 DEVICE vector of w_elems fade-in weights (the host builds 0.5 - 0.5 cos(pi (i + 1) / (X + 1)) in float64 and
+ * rounds once).  For i < n:
+ *   dst[dst_off + i] = fmaf(w[i], src[new_off + i] - src[old_off + i], src[old_off + i])   for i < min(x, n),
+ *   dst[dst_off + i] = src[new_off + i]                                                      otherwise.
+ * One launch serves every stream of a pool's round; it replaces, per stream and round, torch's
+ * `torch.addcmul(old, w, new - old)` on the first x samples plus a slice copy of the rest (three launches and two
+ * temporaries each).  Source and destination regions of one launch must not overlap.  Host checks: null pointers,
+ * n_records in [1, 65535], extents > 0 (OV_E_BADARG).  The kernel checks every record: one with a negative or oversized
+ * (n, x > 2^31) field, n < 1, x > w_elems, or whose old span [old_off, old_off + min(x, n)), new span or destination
+ * leaves its buffer touches nothing.  A record moves as 16-byte vectors when all four bases are 16-byte aligned and its
+ * three offsets are multiples of 4, as scalars otherwise, with the same bits either way; 64-bit offsets.  Additive to
+ * ABI 2.12: found by name, like ov_normal_philox_f32. */
+int ov_crossfade_rows_f32(const int64_t* records, int n_records, const float* w, int64_t w_elems, const float* src_base,
+                          int64_t src_elems, float* dst_base, int64_t dst_elems, ov_stream_t stream);
 /* The two layout hand-overs of a live generator unit that runs the bf16 channels-last kernels (openvoice_amd/live.py,
  * generator="bf16"): the live arena and the carries stay fp32 channels-first, the bf16 generator reads and writes dense
  * channels-last bf16.  The fp32 side is B rows of `bs` elements, each [C][ld] with L valid columns; the bf16 side is a

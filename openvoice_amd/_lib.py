@@ -192,6 +192,7 @@ SIGNATURES = {
     "ov_frame_hops_multi_f32": (ctypes.c_int, [_fp, _i64, _fp, _i, _i, _i, _i, _i, _fp, _fp]),
     "ov_stitch_window_cores_f32": (ctypes.c_int, [_fp, _fp, _i, _i, _i, _fp, _i64, _i64, _fp]),
     "ov_carry_rows_f32": (ctypes.c_int, [_fp, _i, _fp, _i64, _fp, _i64, _fp]),
+    "ov_crossfade_rows_f32": (ctypes.c_int, [_fp, _i, _fp, _i64, _fp, _i64, _fp, _i64, _fp]),
     "ov_rows_f32_to_cl_bf16": (ctypes.c_int, [_fp, _i64, _i, _fp, _i, _i, _i, _fp]),
     "ov_cl_bf16_to_rows_f32": (ctypes.c_int, [_fp, _fp, _i64, _i, _i, _i, _i, _fp]),
     "ov_vad_frame_energy_f32": (ctypes.c_int, [_fp, _i64, _fp, _i, _i, _i, _fp, _fp]),

@@ -277,15 +277,17 @@ class BaseSpeakerTTS(OpenVoiceBaseClass):
         audio_io.write(output_path, audio, self.hps.data.sampling_rate)
 
     # ---- streaming synthesis (tts_live.py) ---------------------------------------------------------------------------
-    def tts_live_pool(self, chunk_frames=60, max_streams_per_launch=32, generator="fp32", *, wavenet=None):
+    def tts_live_pool(self, chunk_frames=60, max_streams_per_launch=32, generator="fp32", *, wavenet=None,
+                      lookahead_frames=None):
         """A ``tts_live.TtsLivePool``: many sentences synthesised as streams in shared launches -- ``open(ids,
         speaker_id, speed=1.0, noise_scale=0.667, noise_scale_w=0.6, sdp_ratio=0.2, seed=None)`` -> handle, ``step()``
         -> ``{handle: new samples}``.  Each sentence equals its solo ``infer`` with the same ``(seed, stream)`` pair and
         controls.  ``chunk_frames``: a positive multiple of 15; ``generator`` / ``wavenet``: as for
-        ``ToneColorConverter.live_pool``."""
+        ``ToneColorConverter.live_pool``.  ``lookahead_frames`` is the converter's keyword: anything but None raises
+        ``ValueError`` (streaming TTS emits committed samples only)."""
         from . import tts_live
         return tts_live.TtsLivePool(self.model, chunk_frames=chunk_frames, max_streams_per_launch=max_streams_per_launch,
-                                    generator=generator, wavenet=wavenet)
+                                    generator=generator, wavenet=wavenet, lookahead_frames=lookahead_frames)
 
     def tts_stream_from_ids(self, id_sequences, speaker_id, speed=1.0, noise_scale=0.667, noise_scale_w=0.6, *,
                             seed=None, chunk_frames=60, generator="fp32", wavenet=None):
@@ -701,7 +703,7 @@ class ToneColorConverter(OpenVoiceBaseClass):
 
     # ---- low-latency live streams ------------------------------------------------------------------------------------
     def live_stream(self, src_se, tgt_se, tau=0.3, chunk_frames=15, noise=None, sr_in=None, sr_out=None,
-                    generator="fp32", *, seed=None, wavenet=None):
+                    generator="fp32", *, seed=None, wavenet=None, lookahead_frames=None, crossfade_samples=None):
         """A ``live.LiveStream``: the conversion as a cascade of units that carry their recent input as state.
         ``push(samples)`` -> newly finished samples, ``close()`` -> the rest, ``latency_samples`` =
         ``live.live_latency_samples`` (1.45 s at 15 frames).  ``chunk_frames``: a positive multiple of 15 (the Winograd
@@ -715,14 +717,29 @@ class ToneColorConverter(OpenVoiceBaseClass):
         before and to ``sr_out`` after by ``audio_io.resample_on_device``), with ``generator="bf16"`` the one made with
         ``use_bf16_generator``.  ``seed`` (an int: stream ``(seed, 0)``, or a pair) does the same without a length: the
         noise of frames ``[f0, f0 + n)`` is generated when the chunk is fed, so the output does not depend on the push
-        sizes, equals ``convert_long(seed=...)``, and no noise tensor is held however long the call lasts."""
+        sizes, equals ``convert_long(seed=...)``, and no noise tensor is held however long the call lasts.
+
+        ``lookahead_frames`` (keyword only; None: all of the above, unchanged): an integer A >= 0 makes the stream emit
+        ``[0, hop * max(0, F - A))`` once it has taken F interior frames, instead of waiting for every sample's whole
+        receptive field (1.26 s): ``latency_samples`` becomes ``hop * (A + chunk_frames) + (n_fft - hop) / 2`` (0.19 s
+        at A = 0).  The piece a round emits is that piece of the one-pass conversion of the first F frames -- the input
+        so far, as if it ended there (same embeddings, ``tau`` and ``seed`` / ``noise``) -- not of the whole input;
+        samples whose receptive field had arrived are the same in both.  ``close()`` returns the rest from the exact
+        path.  With ``hop * A >= live.live_right_samples`` (A >= 109) nothing is approximated and nothing extra is
+        launched.  ``crossfade_samples`` = X: the first X samples of a piece are blended with what the previous round's
+        preview held for them (raised-cosine fade-in, ``ov_crossfade_rows_f32``); ``0 <= X <= min(hop * A, hop *
+        chunk_frames)``, default ``min(hop, hop * A)`` -- a default nobody has measured on a real voice.  X = 0 keeps
+        the contract above bit for bit."""
         from . import live
         d = self.hps.data
         return live.LiveStream(self.model, src_se, tgt_se, tau=tau, chunk_frames=chunk_frames, noise=noise,
                                n_fft=d.filter_length, hop=d.hop_length, sr_in=sr_in, sr_out=sr_out,
-                               model_sr=d.sampling_rate, generator=generator, wavenet=wavenet, **noise_mod.kw(seed))
+                               model_sr=d.sampling_rate, generator=generator, wavenet=wavenet,
+                               lookahead_frames=lookahead_frames, crossfade_samples=crossfade_samples,
+                               **noise_mod.kw(seed))
 
-    def live_pool(self, tau=0.3, chunk_frames=15, max_streams_per_launch=32, generator="fp32", *, wavenet=None):
+    def live_pool(self, tau=0.3, chunk_frames=15, max_streams_per_launch=32, generator="fp32", *, wavenet=None,
+                  lookahead_frames=None, crossfade_samples=None):
         """A ``live.LivePool``: many live streams (``open(src_se, tgt_se, noise=None, sr_in=None, sr_out=None,
         seed=None)`` /
         ``push`` / ``close``), every stream with a ready chunk converted by one ``step()`` in launches of up to
@@ -732,12 +749,13 @@ class ToneColorConverter(OpenVoiceBaseClass):
         launch row).  One ``generator`` (``"fp32"`` or
         ``"bf16"``) for the pool; pools of both kinds may be open on one converter at once.  ``wavenet`` (keyword only):
         the WaveNet layers' kernels of the pool's posterior-encoder and flow units, None (follow ``use_bf16_wavenet``),
-        ``"fp32"`` or ``"bf16"``."""
+        ``"fp32"`` or ``"bf16"``.  ``lookahead_frames`` / ``crossfade_samples`` (keyword only, pool-wide like
+        ``chunk_frames``): as for ``live_stream``; the streams' previews share launches like their committed rounds."""
         from . import live
         d = self.hps.data
         return live.LivePool(self.model, tau=tau, chunk_frames=chunk_frames, max_streams_per_launch=max_streams_per_launch,
                              n_fft=d.filter_length, hop=d.hop_length, model_sr=d.sampling_rate, generator=generator,
-                             wavenet=wavenet)
+                             wavenet=wavenet, lookahead_frames=lookahead_frames, crossfade_samples=crossfade_samples)
 
     @wavenet_keyword
     def convert_many(self, items, src_se, tgt_se, tau=0.3, window_frames=longform.DEFAULT_WINDOW_FRAMES,

@@ -347,7 +347,7 @@ class VoiceCloner:
 
     def speak_stream_ids(self, id_sequences, speaker, src_se, tgt_se, speed=1.0, *, seed=None, tau=0.3, out_sr=None,
                          chunk_frames=60, live_chunk_frames=15, generator="fp32", wavenet=None, noise_scale=0.667,
-                         noise_scale_w=0.6):
+                         noise_scale_w=0.6, lookahead_frames=None):
         """``speak_ids`` as a Python generator of device tensors: every chunk of ``tts_stream_from_ids`` (gaps
         included) is pushed into one stream of a converter ``LivePool`` (``sr_in`` = the TTS model's rate where the two
         differ, ``sr_out=out_sr``) and what that stream returns is yielded; the stream is closed at the end.
@@ -356,6 +356,14 @@ class VoiceCloner:
         direct kernels and equal rates; within the rates' bar otherwise).  ``seed``: the TTS sentences take streams
         ``k + i`` of it, the converter's posterior noise stream ``k`` (purpose 0); None: nothing is reproducible.
         ``chunk_frames`` / ``live_chunk_frames``: the chunk of the synthesis / of the conversion stream."""
+        if lookahead_frames is not None:          # at the call, not at the first next()
+            raise ValueError("lookahead_frames belongs to the converter's live streams (live_stream / live_pool): "
+                             "speak_stream* emits committed samples only")
+        return self._speak_stream_ids(id_sequences, speaker, src_se, tgt_se, speed, seed, tau, out_sr, chunk_frames,
+                                      live_chunk_frames, generator, wavenet, noise_scale, noise_scale_w)
+
+    def _speak_stream_ids(self, id_sequences, speaker, src_se, tgt_se, speed, seed, tau, out_sr, chunk_frames,
+                          live_chunk_frames, generator, wavenet, noise_scale, noise_scale_w):
         conv = self.converter
         chunks = self.tts.tts_stream_from_ids(id_sequences, self._speaker_id(speaker), speed=speed,
                                               noise_scale=noise_scale, noise_scale_w=noise_scale_w, seed=seed,

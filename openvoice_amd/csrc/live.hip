@@ -57,6 +57,53 @@ __global__ __launch_bounds__(256) void carry_rows_kernel(const int64_t* __restri
   }
 }
 
+// ---- the seam of a look-ahead stream ---------------------------------------------------------------------------------
+// Record r = (old_off, new_off, dst_off, n, x), all int64, in elements (old / new relative to src, dst to dst):
+//   dst[dst_off + i] = fmaf(w[i], new[i] - old[i], old[i])  for i < min(x, n),   = new[i]  for the rest of i < n.
+// One record is one stream's piece of a round, so one launch serves the pool.  Checked here like the carry's records: a
+// record with a negative or oversized field, x > w_elems, or whose old / new / dst span leaves its buffer touches
+// nothing.  Lanes run along samples; a record moves as 16-byte vectors when the four bases are 16-byte aligned and its
+// three offsets are multiples of 4 (the vector straddling x and the tail go element by element), as scalars otherwise.
+// Both forms apply the same two operations per element, so the bits do not depend on the form.
+constexpr int kFadeBlocks = 4;        // blocks per record; a piece is chunk x hop samples (3840 at the smallest chunk)
+
+__device__ inline float fade_one(float w, float o, float n) { return __builtin_fmaf(w, n - o, o); }
+
+__global__ __launch_bounds__(256) void crossfade_rows_kernel(const int64_t* __restrict__ records, const float* __restrict__ w,
+                                                             int64_t w_elems, const float* __restrict__ src,
+                                                             int64_t src_elems, float* __restrict__ dst, int64_t dst_elems,
+                                                             int bases_aligned) {
+  const int64_t* rec = records + 5 * (int64_t)blockIdx.y;
+  const int64_t oo = rec[0], no = rec[1], d_o = rec[2], n = rec[3], x = rec[4];
+  const int64_t kDim = int64_t(1) << 31, kOff = int64_t(1) << 61;
+  if (n <= 0 || x < 0 || oo < 0 || no < 0 || d_o < 0 || n > kDim || x > kDim || oo > kOff || no > kOff || d_o > kOff) return;
+  const int64_t xb = x < n ? x : n;                       // blended samples
+  if (x > w_elems || oo + xb > src_elems || no + n > src_elems || d_o + n > dst_elems) return;
+  const float* o = src + oo;
+  const float* p = src + no;
+  float* d = dst + d_o;
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (int64_t)gridDim.x * blockDim.x;
+  int64_t j0 = 0;
+  if (bases_aligned && ((oo | no | d_o) & 3) == 0) {
+    const int64_t nv = n >> 2;
+    for (int64_t v = t; v < nv; v += nt) {
+      const int64_t i = 4 * v;
+      f32x4 y = *reinterpret_cast<const f32x4*>(p + i);
+      if (i + 4 <= xb) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(o + i), c = *reinterpret_cast<const f32x4*>(w + i);
+        y = f32x4{fade_one(c[0], a[0], y[0]), fade_one(c[1], a[1], y[1]), fade_one(c[2], a[2], y[2]),
+                  fade_one(c[3], a[3], y[3])};
+      } else if (i < xb) {
+        for (int e = 0; e < 4; ++e)
+          if (i + e < xb) y[e] = fade_one(w[i + e], o[i + e], y[e]);
+      }
+      *reinterpret_cast<f32x4*>(d + i) = y;
+    }
+    j0 = nv << 2;
+  }
+  for (int64_t j = j0 + t; j < n; j += nt) d[j] = j < xb ? fade_one(w[j], o[j], p[j]) : p[j];
+}
+
 // ---- fp32 channels-first rows <-> dense bf16 channels-last ----------------------------------------------------------
 // One workgroup moves a tile of kTC channels x kTL columns of one batch row through LDS (fp32, [channel][column], rows
 // padded by one float).  Two lane maps, each coalesced on its side of the transpose:
@@ -201,6 +248,18 @@ int ov_carry_rows_f32(const int64_t* records, int n_records, const float* src_ba
   dim3 grid(16, n_records);
   hipLaunchKernelGGL(carry_rows_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), records, src_base,
                      src_elems, dst_base, dst_elems, aligned);
+  return hipGetLastError() == hipSuccess ? OV_OK : OV_E_LAUNCH;
+}
+
+int ov_crossfade_rows_f32(const int64_t* records, int n_records, const float* w, int64_t w_elems, const float* src_base,
+                          int64_t src_elems, float* dst_base, int64_t dst_elems, ov_stream_t stream) {
+  if (!records || !w || !src_base || !dst_base || n_records <= 0 || n_records > 65535 || w_elems <= 0 || src_elems <= 0 ||
+      dst_elems <= 0)
+    return OV_E_BADARG;
+  const int aligned = aligned16(w) && aligned16(src_base) && aligned16(dst_base);
+  dim3 grid(kFadeBlocks, n_records);
+  hipLaunchKernelGGL(crossfade_rows_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), records, w, w_elems,
+                     src_base, src_elems, dst_base, dst_elems, aligned);
   return hipGetLastError() == hipSuccess ? OV_OK : OV_E_LAUNCH;
 }
 

@@ -461,6 +461,7 @@ TORCH_LIBRARY(openvoice_amd, m) {
   bind_device<&ov_frame_hops_windows_f32>(m, "frame_hops_windows_f32");
   bind_device<&ov_frame_hops_multi_f32>(m, "frame_hops_multi_f32");
   bind_device<&ov_carry_rows_f32>(m, "carry_rows_f32");
+  bind_device<&ov_crossfade_rows_f32>(m, "crossfade_rows_f32");
   bind_device<&ov_rows_f32_to_cl_bf16>(m, "rows_f32_to_cl_bf16");
   bind_device<&ov_cl_bf16_to_rows_f32>(m, "cl_bf16_to_rows_f32");
   bind_device<&ov_vad_frame_energy_f32>(m, "vad_frame_energy_f32");

@@ -127,14 +127,59 @@ def check_chunk(cfg, chunk_frames):
     return chunk_frames
 
 
-def live_latency_samples(cfg, chunk_frames, n_fft=1024, hop=256):
+def check_lookahead(lookahead_frames):
+    """``lookahead_frames``: None (emit committed samples only) or an integer >= 0."""
+    A = lookahead_frames
+    if A is None:
+        return None
+    if isinstance(A, bool) or not isinstance(A, int) or A < 0:
+        raise ValueError(f"lookahead_frames must be None or an integer >= 0, got {A!r}")
+    return A
+
+
+def check_crossfade(crossfade_samples, lookahead_frames, chunk_frames, hop=256):
+    """``crossfade_samples`` of a look-ahead stream: None = ``min(hop, hop * A)``, else an integer in
+    ``[0, min(hop * A, hop * chunk_frames)]`` -- the previous preview reaches ``hop * A`` samples past the frontier, and a
+    piece is ``hop * chunk_frames`` samples long."""
+    A, X = lookahead_frames, crossfade_samples
+    if A is None:
+        if X is not None:
+            raise ValueError("crossfade_samples needs lookahead_frames")
+        return 0
+    top = min(hop * A, hop * chunk_frames)
+    if X is None:
+        return min(hop, top)
+    if isinstance(X, bool) or not isinstance(X, int) or not 0 <= X <= top:
+        raise ValueError(f"crossfade_samples must be an integer in [0, {top}] (min(hop * lookahead_frames, hop * "
+                         f"chunk_frames)), got {X!r}")
+    return X
+
+
+def crossfade_weights(X):
+    """The fade-in of the seam, ``w[i] = 0.5 - 0.5 cos(pi (i + 1) / (X + 1))`` for i < X: float64 on the host, rounded
+    once to float32 (one element, unused, when X = 0)."""
+    i = torch.arange(1, max(X, 1) + 1, dtype=torch.float64)
+    return (0.5 - 0.5 * torch.cos(math.pi * i / (X + 1))).to(torch.float32)
+
+
+def live_latency_samples(cfg, chunk_frames, n_fft=1024, hop=256, lookahead_frames=None):
     """The bound no output sample's delay exceeds: input samples that arrive after sample t before sample t of the
     output leaves.  Output sample t leaves once the posterior encoder has taken ``m = floor((t + R) / hop) + 1`` frames
     rounded up to the chunk, i.e. frames up to ``c * ceil(m / c)``; frame f is interior (no end reflect padding can
     reach it) from ``f * hop + n_fft - pad`` samples on.  The worst case over t is
     ``R + hop * chunk_frames + (n_fft - hop) / 2`` (R = ``live_right_samples``, hop = samples per frame): 32 060
-    samples (1.45 s at 22.05 kHz) at 15 frames for the released configurations."""
+    samples (1.45 s at 22.05 kHz) at 15 frames for the released configurations.
+
+    With ``lookahead_frames`` = A the stream emits ``[0, hop * max(0, F - A))`` once the posterior encoder has taken F
+    frames, whatever the units' reaches: sample t leaves once ``F >= floor(t / hop) + A + 1``, rounded up to the chunk,
+    i.e. at ``F <= floor(t / hop) + A + chunk_frames``, and frame F - 1 is interior from ``(F - 1) * hop + n_fft - pad``
+    samples on.  The worst case (t a multiple of hop whose frame count rounds up by a whole chunk less one) is
+    ``hop * (A + chunk_frames - 1) + n_fft - pad`` = ``hop * (A + chunk_frames) + (n_fft - hop) / 2``: 4 224 samples
+    (0.19 s) at A = 0 and 15 frames, 8 064 (0.37 s) at A = 15."""
     check_chunk(cfg, chunk_frames)
+    A = check_lookahead(lookahead_frames)
+    if A is not None:
+        return hop * (A + chunk_frames - 1) + n_fft - (n_fft - hop) // 2
     return live_right_samples(cfg) + hop * chunk_frames + (n_fft - hop) // 2
 
 
@@ -195,6 +240,84 @@ class Cascade:
             if k + 1 < len(self.units):
                 self.n[k + 1] += (e1 - e0) * u["stride"]
         return pieces
+
+
+def preview_plan(units, n, e, lo, hi):
+    """The pieces of a preview: the units run "as if the input ended now" on what a stream holds -- ``n[k]`` input
+    columns stored, ``e[k]`` of them emitted (a ``Cascade``'s ``n`` / ``e`` after a round) -- to produce the samples
+    ``[lo, hi)`` of the last unit's output, ``lo`` >= the committed end.  Back-propagated from the last unit the way
+    ``tts_live.first_audio_need`` goes: unit k must hand on its output columns ``[olo, ohi)``, i.e. emit the input
+    columns ``[olo // stride, ceil(ohi / stride))``; its buffer starts ``left`` columns before, down to the ``align``
+    grid (the committed buffers' tile phase), and ends ``right`` columns after or at the end of the input,
+    ``n[0] x rate``; what of that buffer lies past ``n[k]`` is unit k - 1's to hand on.  Returns
+    ``[(k, b0, end, olo, ohi)]`` in cascade order: unit k runs on input columns ``[b0, end)`` -- stored ones up to
+    ``n[k]``, then unit k - 1's -- and hands on its output columns ``[olo, ohi)``.  Units whose buffers lie inside the
+    stored input of their successor do not appear.  A buffer whose output rows would not be a whole number of 16-byte
+    vectors takes one column more (the fp32 MRF kernels of the stride-2 stages have vector instances only; committed
+    buffers there are even because chunk, ``align`` and the rates are)."""
+    pieces, olo, ohi = [], int(lo), int(hi)
+    for k in range(len(units) - 1, -1, -1):
+        if ohi <= olo:
+            break
+        u = units[k]
+        s, total = u["stride"], n[0] * u["rate"]
+        pe0, pe1 = olo // s, min(total, -(-ohi // s))
+        if pe0 < e[k] or pe1 <= pe0:
+            raise ValueError(f"preview range [{lo}, {hi}) reaches before the committed end of unit {u['name']}")
+        b0, end = _start(u, pe0), min(total, pe1 + u["right"])
+        if (end - b0) * s % 4 and end < total:      # dense output rows of whole 16-byte vectors, as a committed buffer's
+            end += 1
+        if u["kind"] == "g" and (end - b0) * s % 4:
+            # a buffer that ends with the input: whole vectors only if ``align`` and ``rate`` make it so (they do for the
+            # released configurations: both even on the stride-2 stages); the kernels have no scalar instance to fall to
+            raise ValueError(f"preview buffer of unit {u['name']} [{b0}, {end}) has no whole number of 16-byte output rows")
+        pieces.append((k, b0, end, olo, min(ohi, pe1 * s)))
+        olo, ohi = max(b0, n[k]), end
+    return pieces[::-1]
+
+
+def lookahead_schedule(units, chunk_frames, lookahead_frames, crossfade_samples, rounds, hop=256):
+    """The emission schedule of a look-ahead stream over ``rounds`` full chunks, from a ``Cascade`` run (host only):
+    per round ``dict(F, C, E0, E, lo, hi, plan)`` -- F frames taken, committed end C, the piece ``[E0, E)`` with
+    ``E = hop * max(0, F - A)``, and, when the piece leaves the committed samples, the preview range
+    ``[lo, hi) = [max(C, E0), E + X)`` with its ``preview_plan`` (else ``plan`` None)."""
+    cas, A, X = Cascade(units, chunk_frames), lookahead_frames, crossfade_samples
+    last, E0, C, out = len(units) - 1, 0, 0, []
+    for _ in range(rounds):
+        for k, _, _, e0, e1 in cas.round(chunk_frames):
+            if k == last:
+                C += (e1 - e0) * units[k]["stride"]
+        F = cas.n[0]
+        E = hop * max(0, F - A)
+        rec = dict(F=F, C=C, E0=E0, E=E, lo=None, hi=None, plan=None)
+        if E > max(C, E0):
+            rec["lo"], rec["hi"] = max(C, E0), min(E + X, hop * F)
+            rec["plan"] = preview_plan(units, cas.n, cas.e, rec["lo"], rec["hi"])
+        out.append(rec)
+        E0 = E
+    return out
+
+
+def preview_widths(units, chunk_frames, lookahead_frames, crossfade_samples, hop=256):
+    """Widest preview buffer of every unit, in input columns: the schedule repeats once every unit is in its steady
+    state (each round then moves every buffer by ``chunk x rate`` columns, a multiple of ``align``), so the maximum over
+    the rounds up to four chunks past the first committed sample and past frame A is the maximum for good."""
+    reach = -(-sum(u["right"] * hop // u["rate"] for u in units) // hop)
+    rounds = (reach + lookahead_frames) // chunk_frames + 5
+    widths = [0] * len(units)
+    for rec in lookahead_schedule(units, chunk_frames, lookahead_frames, crossfade_samples, rounds, hop):
+        for k, b0, end, _, _ in rec["plan"] or []:
+            widths[k] = max(widths[k], end - b0)
+    return widths
+
+
+class _Slabs:
+    """Batch slabs of M rows per unit (in / out) in one tensor ``mem``, for buffers of ``widths[k]`` columns: what a
+    unit launch reads its geometry from.  ``UnitPool`` is its own (committed) instance; the preview pass has a second."""
+
+    def __init__(self, pool, widths, tag):
+        self.tag, self.width, self.mem = tag, list(widths), None
+        self.ld_in, self.ld_out, self.in_off, self.out_off, self.elems = pool._slab_geometry(widths)
 
 
 class _Live:
@@ -317,41 +440,51 @@ class UnitPool:
         return {o[2]: out[o[0]:o[0] + o[1]] for st, o in outputs.items() if o[1]}
 
     # ---- memory layout --------------------------------------------------------------------------------------------
+    def _slab_geometry(self, widths):
+        """Row strides and offsets (elements) of the batch slabs of M rows per unit for buffers of ``widths[k]``
+        columns -> ``(ld_in, ld_out, in_off, out_off, total elements)``."""
+        pad4 = lambda n: (n + 3) // 4 * 4
+        from .engine import padded_frames
+        ld_in, ld_out = [], []
+        for u, W in zip(self.units, widths):
+            if u["kind"] == "g":
+                ld_in.append(pad4(W))
+                ld_out.append(W * u["stride"])                # dense per launch: ld = L * stride
+            else:
+                ld_in.append(padded_frames(W))                    # the frame units' workspace layout (ld = Tp)
+                ld_out.append(padded_frames(W))
+        off, M, in_off, out_off = 0, self.M, [], []
+        for k in range(len(self.units)):
+            in_off.append(off)
+            off += pad4(M * self.rows[k] * ld_in[k])
+            out_off.append(off)
+            off += pad4(M * self.cout[k] * ld_out[k])
+        return ld_in, ld_out, in_off, out_off, off
+
     def _layout(self):
         """Offsets (elements) in the one device tensor ``mem``: the batch slabs of M rows per unit (in / out) and the
         staging rows of new frames first, then one arena slot per stream (every unit's two state halves)."""
         pad4 = lambda n: (n + 3) // 4 * 4
-        from .engine import padded_frames
         cas = Cascade(self.units, self.chunk)
         stages = generator_stages(self.cfg)
-        self.rows, self.cap, self.width, self.ld_in, self.ld_out, self.cout = [], [], [], [], [], []
+        self.rows, self.cap, self.width, self.cout = [], [], [], []
         for k, u in enumerate(self.units):
-            W = cas.width(k)
-            self.width.append(W)
+            self.width.append(cas.width(k))
             self.cap.append(pad4(cas.capacity(k)))
             if u["kind"] == "g":
                 st = stages[u["stage"]]
                 cin = self.inter if st.index == 0 else st.cin
                 cout = 1 if st.last else st.ch
-                self.ld_in.append(pad4(W))
-                self.ld_out.append(W * u["stride"])           # dense per launch: ld = L * stride
             else:
                 cin = self.bins + self.inter if u["kind"] == "q" else self.inter
                 cout = self.inter
-                self.ld_in.append(padded_frames(W))               # the frame units' workspace layout (ld = Tp)
-                self.ld_out.append(padded_frames(W))
             self.rows.append(cin)
             self.cout.append(cout)
-        off, M = 0, self.M
-        self.in_off, self.out_off = [], []
-        for k in range(len(self.units)):
-            self.in_off.append(off)
-            off += pad4(M * self.rows[k] * self.ld_in[k])
-            self.out_off.append(off)
-            off += pad4(M * self.cout[k] * self.ld_out[k])
+        self.tag = None                                           # the committed slabs: this pool is its own ``_Slabs``
+        self.ld_in, self.ld_out, self.in_off, self.out_off, off = self._slab_geometry(self.width)
         self.stage_ld = pad4(self.chunk)                          # a round appends at most one chunk of frames
         self.stage_off = off
-        off += M * self.rows[0] * self.stage_ld
+        off += self.M * self.rows[0] * self.stage_ld
         self.arena_off = off
         self.state_off, so = [], 0
         for k in range(len(self.units)):
@@ -371,13 +504,14 @@ class UnitPool:
             self.mem = grown
 
     # ---- stepping -------------------------------------------------------------------------------------------------
-    def _carry(self, recs, dst=None):
+    def _carry(self, recs, dst=None, src=None):
         if not recs:
             return
         dst = self.mem if dst is None else dst
+        src = self.mem if src is None else src
         table = torch.tensor(recs, dtype=torch.int64).to(self.device)
         for i in range(0, len(recs), 65535):
-            _lib.call("ov_carry_rows_f32", table[i:i + 65535], min(65535, len(recs) - i), self.mem, self.mem.numel(),
+            _lib.call("ov_carry_rows_f32", table[i:i + 65535], min(65535, len(recs) - i), src, src.numel(),
                       dst, dst.numel())
 
     def _batches(self, items, key):
@@ -420,21 +554,23 @@ class UnitPool:
             else:
                 self._carry(recs)
 
-    def _launch(self, k, rows, B, L):
+    def _launch(self, k, rows, B, L, lay=None):
         with self.engine.wavenet_scope(self.wavenet):
-            self._launch_unit(k, rows, B, L)
+            self._launch_unit(k, rows, B, L, self if lay is None else lay)
 
-    def _launch_unit(self, k, rows, B, L):
-        u, eng, mem = self.units[k], self.engine, self.mem
+    def _launch_unit(self, k, rows, B, L, lay):
+        """Unit k on the first ``B`` rows of ``lay``'s slabs (``lay``: this pool for a committed round, the preview's
+        ``_Slabs`` for a preview), ``L`` columns each."""
+        u, eng, mem = self.units[k], self.engine, lay.mem
         bf16 = u["kind"] == "g" and self.generator == "bf16"
-        ws = (eng.live_workspace_bf16 if bf16 else eng.live_workspace)((u["name"], self.width[k]), B, self.width[k],
-                                                                       stage=u["stage"])
-        R, ldi, ldo, C = self.rows[k], self.ld_in[k], self.ld_out[k], self.cout[k]
-        x = mem[self.in_off[k]:]
-        out = mem[self.out_off[k]:]
+        key = (u["name"], lay.width[k]) if lay.tag is None else (u["name"], lay.tag, lay.width[k])
+        ws = (eng.live_workspace_bf16 if bf16 else eng.live_workspace)(key, B, lay.width[k], stage=u["stage"])
+        R, ldi = self.rows[k], lay.ld_in[k]
+        x = mem[lay.in_off[k]:]
+        out = mem[lay.out_off[k]:]
         cat = lambda t: torch.cat([t_ for t_ in t])
         if u["kind"] == "q":
-            self._launch_posterior(k, rows, B, L, ws)
+            self._launch_posterior(k, rows, B, L, ws, lay)
         elif u["kind"] in ("f", "r"):
             key = "src" if u["kind"] == "f" else "tgt"
             conds = [torch.cat([st.conds[key][f] for st, _ in rows]) for f in range(len(rows[0][0].conds[key]))]
@@ -485,19 +621,31 @@ class LivePool(UnitPool):
     same for both.  ``wavenet``: None (follow ``ConverterEngine.use_bf16_wavenet``), ``"fp32"`` or ``"bf16"`` -- the
     WaveNet layers of the ``q`` / ``f`` / ``r`` units on ``ov_wn_layer_bf16`` (bf16 matrix operands, fp32 state); the
     layer's results do not depend on tile, row or batch, so a stream still equals the one-pass conversion with the same
-    keyword."""
+    keyword.  ``lookahead_frames`` = A (None: all of the above, unchanged): the pool emits ``[0, hop * max(0, F - A))``
+    of every stream once it has taken F interior frames -- each round's piece is that piece of the one-pass conversion of
+    the first F frames, from a preview pass after the committed units (``_emit_ahead``, ``preview_plan``); committed
+    state is never built from previewed columns, and ``close`` is exact.  ``crossfade_samples`` = X blends the first X
+    samples of a piece with the previous preview's (``ov_crossfade_rows_f32``); the default, ``min(hop, hop * A)``, has
+    not been measured on a real voice.  Cost (chunk 15): a tick takes 1.6 - 1.9 x the plain one at
+    A = 0, 15 and 45 alike.  Streams of one pool that still fit a 100 ms tick on one GPU: 256 on fp32 at each A (90 ms
+    at A = 0, 96 - 97 ms at 15 and 45, measured: the practical limit; 52 ms plain), and 256 on bf16 with half the tick
+    to spare (51 - 54 ms; about 480 - 500 extrapolated from the cost per added stream, not run)."""
 
     def __init__(self, model, tau=0.3, chunk_frames=DEFAULT_CHUNK_FRAMES,
                  max_streams_per_launch=DEFAULT_LIVE_STREAMS_PER_LAUNCH, n_fft=1024, hop=256, model_sr=rates.MODEL_RATE,
-                 generator="fp32", wavenet=None):
+                 generator="fp32", wavenet=None, lookahead_frames=None, crossfade_samples=None):
         self.model, self.tau = model, float(tau)
+        self.lookahead = check_lookahead(lookahead_frames)
         self._tau_rows = {}         # taus of a launch's rows -> their float32 device vector (uploaded once)
         self.n_fft, self.hop, self.pad = int(n_fft), int(hop), (int(n_fft) - int(hop)) // 2
         self.bins = self.n_fft // 2 + 1
         check_generator(generator), _lib.check_wavenet(wavenet, optional=True), check_chunk(model.model_cfg, chunk_frames)
         super().__init__(model.engine(), model.model_cfg, live_units(model.model_cfg), chunk_frames,
                          max_streams_per_launch, generator=generator, wavenet=wavenet)
-        self.latency_samples = live_latency_samples(self.cfg, self.chunk, self.n_fft, self.hop)
+        self.latency_samples = live_latency_samples(self.cfg, self.chunk, self.n_fft, self.hop, self.lookahead)
+        self.crossfade = check_crossfade(crossfade_samples, self.lookahead, self.chunk, self.hop)
+        # look-ahead streams whose frontier stays inside the committed samples never run a preview
+        self._pv = self._fade = self._fade_w = None               # preview slabs, seam buffer, fade-in weights (lazy)
         self._streams, self._retired, self._next = {}, set(), 0
         self.model_sr = int(model_sr)
         self._rin, self._rout = rates.ResamplerBank(self.device), rates.ResamplerBank(self.device)
@@ -536,6 +684,9 @@ class LivePool(UnitPool):
         st = _Live(self, slot, src_se, tgt_se, noise, seed=seed)
         st.sr_in, st.sr_out, st.tau = sr_in, sr_out, tau
         st.rin = st.rout = None
+        st.E = st.C = 0             # look-ahead: samples emitted / committed so far
+        st.pend, st.pend_n = [], 0  # committed samples past the emitted ones, oldest first
+        st.has_tail = False         # the last preview's samples [E, E + X) are kept in this stream's seam slot
         if sr_in is not None and sr_in != self.model_sr:
             st.rin = self._rin.open(sr_in, self.model_sr)
             self._rin_owner[st.rin] = st
@@ -642,11 +793,11 @@ class LivePool(UnitPool):
                 st.stored[k] += nf
             self._carry(carry)
 
-    def _launch_posterior(self, k, rows, B, L, ws):
-        R, ldi, ldo, C, mem = self.rows[k], self.ld_in[k], self.ld_out[k], self.cout[k], self.mem
+    def _launch_posterior(self, k, rows, B, L, ws, lay):
+        R, ldi, ldo, C, mem = self.rows[k], lay.ld_in[k], lay.ld_out[k], self.cout[k], lay.mem
         cond = torch.cat([st.conds["q"] for st, _ in rows])
-        self.engine.live_posterior(mem[self.in_off[k]:], ldi, R * ldi, mem[self.in_off[k] + self.bins * ldi:], R * ldi,
-                                   mem[self.out_off[k]:], ldo, C * ldo, B, L, cond, self._launch_tau(rows), ws)
+        self.engine.live_posterior(mem[lay.in_off[k]:], ldi, R * ldi, mem[lay.in_off[k] + self.bins * ldi:], R * ldi,
+                                   mem[lay.out_off[k]:], ldo, C * ldo, B, L, cond, self._launch_tau(rows), ws)
 
     def _launch_tau(self, rows):
         """``tau`` of a posterior-encoder launch: the number when its rows agree, else their per-row device vector --
@@ -670,11 +821,142 @@ class LivePool(UnitPool):
             f0 = st.cas.n[0]
             plans.append((h, st, st.cas.round(nf, final=st.closed and f0 + nf == st.T)))
             jobs.append((st, nf, f0))
+        if self.lookahead is not None:       # a regular round: a whole chunk of interior frames, closed or not
+            for st, nf, f0 in jobs:
+                st.regular = nf == self.chunk and f0 + nf <= interior_frames(st.n, self.n_fft, self.hop)
         self._feed(jobs)
         for st, nf, f0 in jobs:
             if not st.closed:
                 st.trim()
-        return self._run_units(plans)
+        outs = self._run_units(plans)
+        return outs if self.lookahead is None else self._emit_ahead(streams, outs)
+
+    # ---- bounded look-ahead ---------------------------------------------------------------------------------------
+    def _seam_layout(self):
+        """One seam slot per arena slot in ``_fade``: ``[tail: X | piece area]``, the piece area holding a round's new
+        piece and the X samples after it (the next tail); the longest piece is the one at ``close``."""
+        X, pad4 = self.crossfade, lambda n: (n + 3) // 4 * 4
+        self.tail_ld = pad4(X)
+        self.seam_elems = self.tail_ld + pad4((self.lookahead + 2 * self.chunk + 8) * self.hop + X)
+        need = self._slots * self.seam_elems
+        if self._fade is None or self._fade.numel() < need:
+            grown = torch.zeros(need, dtype=torch.float32, device=self.device)
+            if self._fade is not None:
+                grown[:self._fade.numel()].copy_(self._fade)
+            self._fade = grown
+        if self._fade_w is None:
+            self._fade_w = crossfade_weights(X).to(self.device)
+
+    def _emit_ahead(self, streams, outs):
+        """What the streams of a round emit under ``lookahead_frames``: ``outs`` = the round's committed samples ->
+        ``{handle: the piece [E_{n-1}, E_n)}``.  Committed samples past the frontier wait in ``pend``; a piece takes them
+        first and the rest from a preview of what the stream holds (``_preview``); the first X samples of a piece that
+        begins past the committed samples, and of a closed stream's rest, are blended with the previous preview's
+        (``ov_crossfade_rows_f32``, one launch for the round).  A closed stream's last
+        rounds (reflect-padded frames) emit nothing until its cascade is done, then everything committed."""
+        A, X, hop = self.lookahead, self.crossfade, self.hop
+        res, jobs = {}, []
+        for h, st, nf in streams:
+            com = outs.get(h)
+            if com is not None:
+                k = max(0, st.E - st.C)                 # already emitted from previews
+                if k < com.numel():
+                    st.pend.append(com[k:])
+                    st.pend_n += com.numel() - k
+                st.C += com.numel()
+            if st.regular:
+                E = hop * max(0, st.cas.n[0] - A)
+            elif st.cas.done:
+                E = st.C
+            else:
+                continue
+            if E <= st.E:
+                continue
+            m = min(st.pend_n, E - st.E)
+            head = None
+            if m:
+                pend = st.pend[0] if len(st.pend) == 1 else torch.cat(st.pend)
+                head, rest = pend[:m], pend[m:]
+                st.pend, st.pend_n = ([rest] if rest.numel() else []), rest.numel()
+            # the seam: a piece that begins inside committed samples is exact there and is not blended (old = new);
+            # the rest of a closed stream is blended with the last preview's tail like any previewed piece
+            st.fade = st.has_tail and (m == 0 or not st.regular)
+            if st.E + m == E and not st.fade:           # committed samples only, no seam: no launch
+                st.has_tail = False
+                res[h], st.E = head, E
+                continue
+            jobs.append((h, st, E, head))
+        if not jobs:
+            return res
+        self._seam_layout()
+        total, recs, keep, previews = 0, [], [], []
+        for h, st, E, head in jobs:
+            base = st.slot * self.seam_elems
+            new, m, n = base + self.tail_ld, 0 if head is None else head.numel(), E - st.E
+            if n + X > self.seam_elems - self.tail_ld:
+                raise RuntimeError("live stream seam overflow")
+            if m:
+                self._fade[new:new + m].copy_(head)
+            lo = st.E + m
+            if lo < E:                                  # the piece leaves the committed samples: preview [lo, E + X)
+                hi = min(E + X, hop * st.cas.n[0])
+                previews.append((st, lo, hi, new + m))
+                if X and hi - E == X:
+                    keep.append((new + n, base, 1, X, X, X))
+            recs.append((base, new, total, n, X if st.fade else 0))
+            st.has_tail = lo < E and X > 0 and hi - E == X
+            st.E = E
+            total += n
+        self._preview(previews)
+        out = torch.empty(total, dtype=torch.float32, device=self.device)
+        table = torch.tensor(recs, dtype=torch.int64).to(self.device)
+        _lib.call("ov_crossfade_rows_f32", table, len(recs), self._fade_w, self._fade_w.numel(), self._fade,
+                  self._fade.numel(), out, total)
+        self._carry(keep, dst=self._fade, src=self._fade)          # the next tails, after this round's were read
+        for (h, st, E, head), r in zip(jobs, recs):
+            res[h] = out[r[2]:r[2] + r[3]]
+        return res
+
+    def _preview(self, jobs):
+        """``jobs`` = [(stream, lo, hi, dst)]: the samples ``[lo, hi)`` of each stream's conversion as if its input
+        ended with the frames it holds, written to ``_fade[dst:]``.  Every unit of its ``preview_plan`` runs through
+        ``_launch_unit`` on slabs of the preview's own (``_pv``): the stored part of a buffer is gathered from the arena
+        as it is -- no history shift, no write to the arena -- and the rest is what the unit before handed on.  Streams
+        whose plans have the same buffer widths share launches, on the pool's ladder."""
+        if not jobs:
+            return
+        if self._pv is None:
+            widths = preview_widths(self.units, self.chunk, self.lookahead, self.crossfade, self.hop)
+            self._pv = _Slabs(self, widths, "preview")
+            self._pv.mem = torch.zeros(self._pv.elems, dtype=torch.float32, device=self.device)
+        pv, K = self._pv, len(self.units)
+        plans = [(st, preview_plan(self.units, st.cas.n, st.cas.e, lo, hi), dst) for st, lo, hi, dst in jobs]
+        for sig, chunk, B in self._batches(plans, key=lambda p: tuple((k, end - b0) for k, b0, end, _, _ in p[1])):
+            rows = chunk + [chunk[-1]] * (B - len(chunk))
+            for i, (k, L) in enumerate(sig):
+                if L > pv.width[k]:
+                    raise RuntimeError(f"live preview wider than its slab (unit {self.units[k]['name']})")
+                R, ldi, C, s = self.rows[k], pv.ld_in[k], self.cout[k], self.units[k]["stride"]
+                gather = []
+                for r, (st, plan, _) in enumerate(rows):
+                    b0 = plan[i][1]
+                    n = min(plan[i][2], st.stored[k]) - b0
+                    if n > 0:
+                        gather.append((self._state(st, k, st.half[k]) + (b0 - st.s0[k]), pv.in_off[k] + r * R * ldi, R, n,
+                                       self.cap[k], ldi))
+                self._carry(gather, dst=pv.mem)
+                self._launch(k, [(st, None) for st, _, _ in rows], B, L, pv)
+                ldo = L * s if self.units[k]["kind"] == "g" else pv.ld_out[k]
+                hand = []
+                for r, (st, plan, dst) in enumerate(rows):
+                    _, b0, _, olo, ohi = plan[i]
+                    src = pv.out_off[k] + r * C * ldo + (olo - b0 * s)
+                    if k < K - 1:
+                        nb0, ldn = plan[i + 1][1], pv.ld_in[k + 1]
+                        hand.append((src, pv.in_off[k + 1] + r * C * ldn + (olo - nb0), C, ohi - olo, ldo, ldn))
+                    elif r < len(chunk):
+                        hand.append((src, dst, 1, ohi - olo, ldo, ohi - olo))
+                self._carry(hand, dst=pv.mem if k < K - 1 else self._fade, src=pv.mem)
 
     @torch.no_grad()
     def step(self):
@@ -717,10 +999,12 @@ class LiveStream:
     the model rate).  ``generator``: as for ``LivePool``."""
 
     def __init__(self, model, src_se, tgt_se, tau=0.3, chunk_frames=DEFAULT_CHUNK_FRAMES, noise=None, n_fft=1024,
-                 hop=256, sr_in=None, sr_out=None, model_sr=rates.MODEL_RATE, generator="fp32", seed=None, wavenet=None):
+                 hop=256, sr_in=None, sr_out=None, model_sr=rates.MODEL_RATE, generator="fp32", seed=None, wavenet=None,
+                 lookahead_frames=None, crossfade_samples=None):
         noise_mod.exclusive(seed, noise=noise)
         self._pool = LivePool(model, tau=tau, chunk_frames=chunk_frames, max_streams_per_launch=1, n_fft=n_fft, hop=hop,
-                              model_sr=model_sr, generator=generator, wavenet=wavenet)
+                              model_sr=model_sr, generator=generator, wavenet=wavenet, lookahead_frames=lookahead_frames,
+                              crossfade_samples=crossfade_samples)
         self._h = self._pool.open(src_se, tgt_se, noise=noise, sr_in=sr_in, sr_out=sr_out, **noise_mod.kw(seed))
         self.latency_seconds, self.latency_samples = self._pool.latency_of(self._h)
         self._closed = False

@@ -84,7 +84,10 @@ class TtsLivePool(UnitPool):
     ``front_batch=False`` runs the front half per sentence instead of as one padded batch."""
 
     def __init__(self, model, chunk_frames=DEFAULT_CHUNK_FRAMES, max_streams_per_launch=DEFAULT_LIVE_STREAMS_PER_LAUNCH,
-                 generator="fp32", wavenet=None, front_batch=True):
+                 generator="fp32", wavenet=None, front_batch=True, lookahead_frames=None):
+        if lookahead_frames is not None:
+            raise ValueError("lookahead_frames belongs to the converter's live streams (live_stream / live_pool): "
+                             "streaming TTS emits committed samples only")
         self.model = model
         self.tts = model.engine()
         cfg = model.model_cfg

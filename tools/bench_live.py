@@ -9,9 +9,12 @@ at that rate (openvoice_amd/rates.py: one resampler launch per direction and ste
 measured in the same run as the baseline.
 With ``--generator fp32 bf16`` every (chunk, N) row is measured once per generator, one after the other in the same run
 (``LivePool(generator=...)``: the kernels of the generator units; the records carry ``generator``).
+With ``--lookahead A [A ...]`` every (chunk, N, generator) row is measured first plain (``lookahead_frames`` None) and
+then once per A in the same run (``LivePool(lookahead_frames=A)``, default cross-fade); the records carry
+``lookahead_frames``, the latency bound of that A and ``x_plain`` = the row's ms per tick over its plain row's.
 Measurement tool: python tools/bench_live.py [--streams 1 8 32 128] [--chunks 15 30 60] [--max-streams-per-launch 32]
                                              [--min-ticks 20] [--sr-in HZ] [--sr-out HZ] [--generator fp32 bf16]
-                                             [--out FILE]"""
+                                             [--lookahead A [A ...]] [--out FILE]"""
 import argparse
 import json
 import math
@@ -25,13 +28,13 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tools.bench_streams import HOP, NFFT, SR, TICK, run as run_windowed, speechlike  # noqa: E402
 
 
-def run_live(model, chunk, N, M, min_ticks, dev, wave, ses, sr_in=None, sr_out=None, generator="fp32"):
+def run_live(model, chunk, N, M, min_ticks, dev, wave, ses, sr_in=None, sr_out=None, generator="fp32", lookahead=None):
     from openvoice_amd import live
     torch.cuda.empty_cache()
     torch.cuda.reset_peak_memory_stats(dev)
     pool = live.LivePool(model, tau=0.3, chunk_frames=chunk, max_streams_per_launch=M, n_fft=NFFT, hop=HOP,
-                         generator=generator)
-    latency = pool.latency_samples
+                         generator=generator, lookahead_frames=lookahead)
+    latency = live.live_latency_samples(model.model_cfg, chunk, NFFT, HOP)      # warm up past the plain bound in any case
     r_in, r_out = sr_in or SR, sr_out or SR
     push_n = r_in // 10                           # input samples per 100 ms push
     gen = torch.Generator().manual_seed(N * 7 + chunk)
@@ -60,6 +63,8 @@ def run_live(model, chunk, N, M, min_ticks, dev, wave, ses, sr_in=None, sr_out=N
            "ms_per_tick": round(ms, 2), "real_time_factor": round(N * 100.0 / ms, 2), "real_time": ms <= 100.0,
            "peak_gib": round(torch.cuda.max_memory_allocated(dev) / 2**30, 3), "latency_s": round(lat_s, 3),
            "state_mib_per_stream": round(pool.state_bytes_per_stream() / 2**20, 3)}
+    if lookahead is not None:
+        rec.update(lookahead_frames=lookahead, crossfade_samples=pool.crossfade)
     if sr_in or sr_out:
         rec.update(sr_in=r_in, sr_out=r_out, resampler_launches=pool._rin.launches + pool._rout.launches)
     return rec
@@ -76,6 +81,8 @@ def main():
     ap.add_argument("--sr-out", type=int, default=None, help="rate of the output (default: the model rate)")
     ap.add_argument("--generator", nargs="+", choices=["fp32", "bf16"], default=["fp32"],
                     help="the live pools' generator kernels; both: every row once per generator, in the same run")
+    ap.add_argument("--lookahead", type=int, nargs="+", default=[],
+                    help="lookahead_frames values; each row is measured plain first, then once per value")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
     from openvoice_amd.models import SynthesizerTrn
@@ -108,7 +115,13 @@ def main():
             for generator in args.generator:
                 if rated:                         # the model-rate row of the same run, then the resampled one
                     emit(run_live(model, chunk, N, M, args.min_ticks, dev, wave, ses, generator=generator))
-                emit(run_live(model, chunk, N, M, args.min_ticks, dev, wave_in, ses, args.sr_in, args.sr_out, generator))
+                plain = run_live(model, chunk, N, M, args.min_ticks, dev, wave_in, ses, args.sr_in, args.sr_out, generator)
+                emit(plain)
+                for A in args.lookahead:
+                    rec = run_live(model, chunk, N, M, args.min_ticks, dev, wave_in, ses, args.sr_in, args.sr_out,
+                                   generator, lookahead=A)
+                    rec["x_plain"] = round(rec["ms_per_tick"] / plain["ms_per_tick"], 2)
+                    emit(rec)
     if not args.no_windowed:
         eng._live_ws.clear()                       # the windowed rows' peak memory without the live workspaces
         eng._live_ws_bf16.clear()
