@@ -491,6 +491,29 @@ int ov_unpack_groups_f32(const float* src, int64_t src_len, const int64_t* recor
 int ov_normal_philox_f32(const int64_t* records, int R, int C, float* dst, int64_t dst_elems, int64_t max_frames,
                          ov_stream_t stream);
 
+/* The project's own keyed watermark (openvoice_amd/watermark.py) behind the converter's provenance hook, reference
+ * openvoice/api.py:162-201 (add_watermark / detect_watermark, which call the third-party wavmark network once per
+ * 16 000-sample window).  NOT wavmark-compatible: informed spread spectrum in the time domain.  A window x[0 .. L)
+ * carries 32 bits; bit j owns the samples S_j = {i : i % 32 == j}:
+ *   c[i]  = +1 / -1 for a set / clear bit (i % 32) of word (i % 128) / 32 of
+ *           Philox4x32-10(counter = (i / 128, 0, 0, 3), key = (key & 0xffffffff, key >> 32))   (ov_normal_philox_f32's core)
+ *   p_j   = (1 / |S_j|) sum_{i in S_j} c[i] x[i],      a = max(strength * sqrt(mean x^2), floor_level)
+ *   embed:  d_j = b_j max(a - b_j p_j, 0), b_j = +1 / -1 for payload bit j set / clear;  y[i] = x[i] + d_{i % 32} c[i]
+ *   detect: q_out[w][j] = p_j and level_out[w] = a of the window as it is; bit j reads as q_j >= 0.
+ * records is a DEVICE int64 [W][4] of (src_off, dst_off, L, bits), offsets in elements relative to src / dst, the payload
+ * in the low 32 bits of `bits` (bit j = (bits >> j) & 1); detect reads src_off and L only.  One launch serves every
+ * window, one 256-thread workgroup each.  dst may be src: a window's source and destination coincide or do not overlap,
+ * and the windows of one launch do not overlap each other.  Sums are added in a fixed order that depends on L alone, so
+ * what a window gets does not depend on W, on its place in the launch or on the alignment of its offsets.  Host checks
+ * (OV_E_BADARG): null pointers, extents <= 0, W outside [1, 65535], key < 0, strength outside [0, 1], floor_level outside
+ * (0, 1]; pointers 4-byte aligned (OV_E_ALIGN).  The kernel checks every record: one with L outside [512, 2^31], a
+ * negative offset, or whose window leaves [0, src_elems) (embed: or [0, dst_elems)) writes nothing.  Additive to ABI
+ * 2.12: found by name, like ov_normal_philox_f32. */
+int ov_wm_embed_windows_f32(const float* src, int64_t src_elems, float* dst, int64_t dst_elems, const int64_t* records,
+                            int W, int64_t key, float strength, float floor_level, ov_stream_t stream);
+int ov_wm_detect_windows_f32(const float* src, int64_t src_elems, const int64_t* records, int W, int64_t key,
+                             float strength, float floor_level, float* q_out, float* level_out, ov_stream_t stream);
+
 /* Rate conversion at the audio boundary, reference openvoice/api.py:123,144 (``librosa.load(path, sr=...)`` = resampy's
  * kaiser_best band-limited sinc interpolation): a polyphase FIR over a mono waveform,
  *   y[t] = sum_{j < 2 taps} h[t % P][j] * x[(t * Q) / P - taps + 1 + j]        (x = 0 outside [0, n_in))
@@ -925,7 +948,8 @@ int ov_conv1d_wino_pack_f32(const float* w, int Cout, int Cin, int K, float* dst
  * _pack_size, _pack_f32).  2.08: ov_conv1d_wino_f32 instances for Cout % 32 == 0 at K = 11 (one 32-row fragment per
  * workgroup; ov_conv1d_wino_chunk(11, 32) = 2 where 2.07 returned 0).  2.09: ov_conv1d_wino_params.out_slope (the field that
  * was `reserved0`: same size and offset, 0 = none).  2.10: ov_frame_hops_windows_f32, ov_stitch_window_cores_f32.  2.11: ov_frame_hops_multi_f32.  2.12: ov_carry_rows_f32 (and, added later within 2.12 without a version change, ov_polyphase_fir_rows_f32 and ov_vad_frame_energy_f32, ov_vad_segments_i32, ov_vad_compact_f32, ov_rows_f32_to_cl_bf16, ov_cl_bf16_to_rows_f32: additive symbols, which the Python binding looks up by name when it loads the library; likewise ov_wn_layer_wino_f32, ov_wn_layer_wino_tile, ov_wn_wino_pack_size and ov_wn_wino_pack_f32, and ov_join_segments_f32, and ov_pack_groups_cl_bf16 and ov_unpack_groups_f32, and ov_wn_layer_bf16, ov_wn_layer_bf16_supported,
- * ov_wn_layer_bf16_tile, ov_wn_bf16_pack_size and ov_wn_bf16_pack; and ov_conv1d_params.scale_b, one pointer appended
+ * ov_wn_layer_bf16_tile, ov_wn_bf16_pack_size and ov_wn_bf16_pack, and ov_wm_embed_windows_f32 and
+ * ov_wm_detect_windows_f32; and ov_conv1d_params.scale_b, one pointer appended
  * to the struct and read only under OV_F_SCALE_B, a flag no older caller sets: the version stays 212 and a caller built
  * against the shorter struct stays binary compatible).  The Python binding
  * refuses a library older than the entry points it calls (openvoice_amd/_lib.py MIN_VERSION). */

@@ -14,7 +14,8 @@ package at the repo root).  What differs, on purpose:
 * ``convert_batch`` (new) is the batched entry the benchmark configs use; ``convert`` is file I/O
   around ``convert_batch`` with B = 1;
 * audio decode / WAV write go through ``openvoice_amd.audio_io`` (librosa/soundfile when present);
-* the watermark (third-party ``wavmark``) stays an optional post-processing hook.
+* the watermark (third-party ``wavmark``) stays an optional post-processing hook; ``watermark="native"`` installs the
+  project's own device watermark (``openvoice_amd.watermark``, not wavmark-compatible) behind the same hook.
 """
 import os
 import re
@@ -25,6 +26,7 @@ import torch
 from . import _lib, audio_io, longform, rates, utils
 from .engine import item_tau, wavenet_keyword
 from . import noise as noise_mod
+from . import watermark as watermark_mod
 from .mel_processing import spectrogram_torch
 from .models import SynthesizerTrn
 
@@ -367,9 +369,15 @@ class ToneColorConverter(OpenVoiceBaseClass):
 
     def __init__(self, *args, **kwargs):
         enable_watermark = kwargs.pop("enable_watermark", True)
+        watermark, watermark_key = kwargs.pop("watermark", None), kwargs.pop("watermark_key", 0)
+        if watermark not in (None, "native"):
+            raise ValueError(f"watermark must be None (the wavmark hook, when installed) or 'native', got {watermark!r}")
         super().__init__(*args, **kwargs)
         self.watermark_model = None
-        if enable_watermark:
+        if enable_watermark and watermark == "native":
+            # the project's own keyed mark (openvoice_amd/watermark.py): on the device, NOT wavmark-compatible
+            self.watermark_model = watermark_mod.NativeWatermark(key=watermark_key).to(self.device)
+        elif enable_watermark:
             try:
                 import wavmark   # third-party, not part of the reference tree (requirements.txt:4)
                 self.watermark_model = wavmark.load_model().to(self.device)
@@ -618,8 +626,11 @@ class ToneColorConverter(OpenVoiceBaseClass):
                                      **noise_mod.kw(seed))
         o_hat, _ = self.convert_batch(y.unsqueeze(0), src_se, tgt_se, tau=tau,
                                       **noise_mod.kw(None if seed is None else [seed]))
+        if self._native_watermark():         # marked on the device, before the copy to the host
+            self.watermark_model.mark_many([o_hat[0, 0].data], message)
         audio = o_hat[0, 0].data.cpu().float().numpy()
-        audio = self.add_watermark(audio, message)
+        if not self._native_watermark():
+            audio = self.add_watermark(audio, message)
         if output_path is None:
             return audio
         audio_io.write(output_path, audio, hps.data.sampling_rate)
@@ -640,12 +651,31 @@ class ToneColorConverter(OpenVoiceBaseClass):
         y = torch.as_tensor(audio_or_path, dtype=torch.float32).reshape(-1).to(self.device)
         return y if sr is None or int(sr) == int(msr) else audio_io.resample_on_device(y, sr, msr)
 
+    def _native_watermark(self):
+        """True when the hook's model is the project's own (``watermark="native"``): the outputs are then marked on the
+        device by ``NativeWatermark.mark_many``, one launch per call, instead of the host loop of ``add_watermark``."""
+        return isinstance(self.watermark_model, watermark_mod.NativeWatermark)
+
+    def _finish_many(self, outs, message, out_srs):
+        """``_finish`` of many converted waveforms: without a model, or with the native one (which marks every carrier
+        window of every item in ONE launch first), the rate conversion is one launch for all items; any other model
+        keeps the per-item host loop."""
+        msr = self.hps.data.sampling_rate
+        if self.watermark_model is not None and not self._native_watermark():
+            return [self._finish(o, message, r) for o, r in zip(outs, out_srs)]
+        if self._native_watermark():
+            self.watermark_model.mark_many(outs, message)
+        outs = rates.resample_many(outs, [(msr, r) for r in out_srs], self.device)
+        return [o.cpu().numpy() for o in outs]
+
     def _finish(self, o, message, out_sr):
         """Converted device waveform at the model rate -> host audio at ``out_sr`` (None: the model rate).  The watermark
         hook runs at the model rate, before the rate conversion."""
         msr = self.hps.data.sampling_rate
         resample = out_sr is not None and int(out_sr) != int(msr)
-        if self.watermark_model is None:
+        if self._native_watermark():
+            self.watermark_model.mark_many([o], message)
+        if self.watermark_model is None or self._native_watermark():
             return (audio_io.resample_on_device(o, msr, out_sr) if resample else o).cpu().numpy()
         audio = self.add_watermark(o.cpu().numpy(), message)
         if resample:
@@ -798,11 +828,7 @@ class ToneColorConverter(OpenVoiceBaseClass):
         outs = self._windowed(window_frames, windows_per_launch).convert_many(waves, srcs, tgts, tau=tau, noises=noise,
                                                                               **noise_mod.kw(seed, "seeds"),
                                                                               **_lib.generator_kw(generator))
-        if self.watermark_model is None:
-            outs = rates.resample_many(outs, [(msr, r) for r in out_srs], self.device)
-            audios = [o.cpu().numpy() for o in outs]
-        else:
-            audios = [self._finish(o, message, r) for o, r in zip(outs, out_srs)]
+        audios = self._finish_many(outs, message, out_srs)
         if output_paths is None:
             return audios
         for path, audio, r in zip(output_paths, audios, out_srs):

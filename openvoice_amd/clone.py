@@ -308,11 +308,7 @@ class VoiceCloner:
             outs = conv._windowed(window_frames, windows_per_launch).convert_many(
                 waves, [r.src_se for r in reqs], [r.tgt_se for r in reqs], tau=tau, noises=noise, **gen_kw)
             out_srs = [r.out_sr for r in reqs]
-            if conv.watermark_model is None:
-                outs = rates.resample_many(outs, [(msr, r) for r in out_srs], self.device)
-                audios = [o.cpu().numpy() for o in outs]
-            else:
-                audios = [conv._finish(o, message, r) for o, r in zip(outs, out_srs)]
+            audios = conv._finish_many(outs, message, out_srs)
         if output_paths is not None:
             for path, audio, r in zip(output_paths, audios, out_srs):
                 audio_io.write(path, audio, msr if r is None else r)

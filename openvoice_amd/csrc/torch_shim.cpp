@@ -471,6 +471,8 @@ TORCH_LIBRARY(openvoice_amd, m) {
   bind_device<&ov_pack_groups_cl_bf16>(m, "pack_groups_cl_bf16");
   bind_device<&ov_unpack_groups_f32>(m, "unpack_groups_f32");
   bind_device<&ov_normal_philox_f32>(m, "normal_philox_f32");
+  bind_device<&ov_wm_embed_windows_f32>(m, "wm_embed_windows_f32");
+  bind_device<&ov_wm_detect_windows_f32>(m, "wm_detect_windows_f32");
   bind_device<&ov_stitch_window_cores_f32>(m, "stitch_window_cores_f32");
   bind_device<&ov_conv_post_tanh_f32>(m, "conv_post_tanh_f32");
   bind_device<&ov_conv_post_tanh_limited_f32>(m, "conv_post_tanh_limited_f32");

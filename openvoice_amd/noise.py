@@ -26,6 +26,7 @@ import numpy as np
 from . import _lib
 
 PURPOSE_POSTERIOR, PURPOSE_TTS_W, PURPOSE_TTS_Z = 0, 1, 2
+PURPOSE_WATERMARK = 3       # not a Gaussian draw: single bits of the same Philox core are watermark.py's chips
 RECORD_FIELDS = 7           # ov_normal_philox_f32's record: (seed, stream, purpose, f0, nf, dst_off, dst_ld)
 MAX_RECORDS = 65535
 SEED_LIMIT = 1 << 63
