@@ -45,10 +45,11 @@ import torch
 
 from . import _lib, rates
 from . import noise as noise_mod
-from .engine import item_tau, rows_tau
+from .engine import rows_tau
 from .generator import generator_stages, samples_per_frame
 from .longform import launch_ladder, stream_end_frames, winograd_grid_frames
 from .params import ENC_Q_KERNEL, ENC_Q_LAYERS, FLOW_KERNEL, FLOW_LAYERS, N_FLOWS
+from .streams import PushedPool, WaveBuffer
 
 DEFAULT_CHUNK_FRAMES = 15
 DEFAULT_LIVE_STREAMS_PER_LAUNCH = 32
@@ -321,18 +322,16 @@ class _Slabs:
 
 
 class _Live:
-    """One stream of a ``LivePool``: waveform buffer, noise, cascade bookkeeping and its arena slot."""
+    """One stream of a ``LivePool``: waveform buffer, noise, cascade bookkeeping and its arena slot (``slot``, given by
+    ``LivePool.open`` once the stream is known to be valid)."""
 
-    def __init__(self, pool, slot, src_se, tgt_se, noise, seed=None):
+    def __init__(self, pool, src_se, tgt_se, noise, seed=None):
         noise_mod.exclusive(seed, noise=noise)
-        self.pool, self.slot = pool, slot
+        self.pool, self.slot = pool, None
         self.seed = None if seed is None else noise_mod.check_seed(seed)      # (seed, stream): frames made on demand
         dev = pool.device
         self.cas = Cascade(pool.units, pool.chunk)
-        self.buf = torch.empty(0, dtype=torch.float32, device=dev)
-        self.len = 0                # valid samples in buf
-        self.base = 0               # file index of buf[0]; a multiple of hop
-        self.n = 0                  # samples received
+        self.wave = WaveBuffer(dev)
         self.noise = noise.to(dev, torch.float32) if noise is not None else None
         if self.noise is not None and (self.noise.dim() != 3 or self.noise.shape[:2] != (1, pool.inter)):
             raise ValueError(f"noise must be [1, {pool.inter}, >= T], got {tuple(self.noise.shape)}")
@@ -349,25 +348,6 @@ class _Live:
         self.closed = False
         self.T = None
 
-    def append(self, x):
-        n = x.numel()
-        if self.len + n > self.buf.numel():
-            grown = torch.empty(max(2 * self.buf.numel(), self.len + n, 1 << 16), dtype=torch.float32,
-                                device=self.buf.device)
-            grown[:self.len].copy_(self.buf[:self.len])
-            self.buf = grown
-        self.buf[self.len:self.len + n].copy_(x)
-        self.len += n
-        self.n += n
-
-    def trim(self):
-        """Drop samples no later frame reads (whole hops, from before the reflect padding of the next frame)."""
-        p = self.pool
-        base = max(0, self.cas.n[0] * p.hop - -(-p.pad // p.hop) * p.hop)
-        if base > self.base:
-            keep = self.buf[base - self.base:self.len].clone()
-            self.buf, self.len, self.base = keep, keep.numel(), base
-
     def noise_for(self, f0, nf):
         p = self.pool
         if self.noise is None:
@@ -381,7 +361,7 @@ class _Live:
         c = self.pool.chunk
         if self.closed:
             return None if self.cas.done else min(c, self.T - self.cas.n[0])
-        if interior_frames(self.n, self.pool.n_fft, self.pool.hop) >= self.cas.n[0] + c:
+        if interior_frames(self.wave.n, self.pool.n_fft, self.pool.hop) >= self.cas.n[0] + c:
             return c
         return None
 
@@ -607,7 +587,7 @@ class UnitPool:
         return recs
 
 
-class LivePool(UnitPool):
+class LivePool(UnitPool, PushedPool):
     """Many live streams stepped together (see the module docstring).  ``open(src_se, tgt_se, noise=None)`` -> handle;
     ``push(h, samples)`` buffers; ``step()`` runs every stream with a ready chunk (and every closed stream's remaining
     rounds) -> ``{handle: newly finished samples}`` (device tensors); ``close(h)`` marks the end of h's input.  Rounds:
@@ -646,11 +626,7 @@ class LivePool(UnitPool):
         self.crossfade = check_crossfade(crossfade_samples, self.lookahead, self.chunk, self.hop)
         # look-ahead streams whose frontier stays inside the committed samples never run a preview
         self._pv = self._fade = self._fade_w = None               # preview slabs, seam buffer, fade-in weights (lazy)
-        self._streams, self._retired, self._next = {}, set(), 0
-        self.model_sr = int(model_sr)
-        self._rin, self._rout = rates.ResamplerBank(self.device), rates.ResamplerBank(self.device)
-        self._rin_owner = {}        # input resampler key -> stream
-        self._rout_ending = []      # output resampler keys of streams that finished in this step
+        self._init_streams(self.device, model_sr)
 
     def state_bytes_per_stream(self):
         """Device bytes one open stream adds: its arena slot (every unit's two state halves) and its conditioning rows
@@ -662,10 +638,6 @@ class LivePool(UnitPool):
         return 4 * (self.slot_elems + conds)
 
     # ---- streams --------------------------------------------------------------------------------------------------
-    @property
-    def active(self):
-        return list(self._streams)
-
     def open(self, src_se, tgt_se, noise=None, sr_in=None, sr_out=None, *, seed=None, tau=None):
         """A new stream -> its handle.  ``tau``: None = the pool's, else this stream's own number, for life.
         ``sr_in`` / ``sr_out``: the rate of its pushes / of its output (None or the
@@ -674,26 +646,15 @@ class LivePool(UnitPool):
         the stream then equals ``convert_long(seed=...)`` of its whole input whatever the push sizes and whoever shares
         the pool, and holds no noise tensor; neither: drawn from torch's generator per chunk."""
         noise_mod.exclusive(seed, noise=noise)
-        tau = self.tau if tau is None else item_tau(1, tau)
-        if not isinstance(tau, float):
-            raise _lib.OvError("LivePool.open: tau is one number per stream")
+        tau = self._stream_tau(tau, "LivePool.open")
         sr_in, sr_out = rates.check_rate(sr_in, "sr_in"), rates.check_rate(sr_out, "sr_out")
-        slot = self._take_slot()
-        h = self._next
-        self._next += 1
-        st = _Live(self, slot, src_se, tgt_se, noise, seed=seed)
-        st.sr_in, st.sr_out, st.tau = sr_in, sr_out, tau
-        st.rin = st.rout = None
+        st = _Live(self, src_se, tgt_se, noise, seed=seed)
+        st.tau = tau
         st.E = st.C = 0             # look-ahead: samples emitted / committed so far
         st.pend, st.pend_n = [], 0  # committed samples past the emitted ones, oldest first
         st.has_tail = False         # the last preview's samples [E, E + X) are kept in this stream's seam slot
-        if sr_in is not None and sr_in != self.model_sr:
-            st.rin = self._rin.open(sr_in, self.model_sr)
-            self._rin_owner[st.rin] = st
-        if sr_out is not None and sr_out != self.model_sr:
-            st.rout = self._rout.open(self.model_sr, sr_out)
-        self._streams[h] = st
-        return h
+        st.slot = self._take_slot()         # nothing after this raises: a failed open leaves the pool as it was
+        return self._register(st, sr_in, sr_out)
 
     def latency_of(self, h):
         """``(seconds, samples)``: the latency bound of stream h at its own rates (``rates.stream_latency``; samples in
@@ -701,32 +662,10 @@ class LivePool(UnitPool):
         st = self._stream(h)
         return rates.stream_latency(self.latency_samples, self.model_sr, st.sr_in, st.sr_out)
 
-    def _stream(self, h):
-        st = self._streams.get(h)
-        if st is None:
-            raise RuntimeError(f"stream {h!r} is closed" if h in self._retired else f"no stream {h!r} in this pool")
-        return st
-
-    @torch.no_grad()
-    def push(self, h, samples):
-        st = self._stream(h)
-        if st.closed:
-            raise RuntimeError(f"push() after close() on stream {h!r}")
-        if st.rin is not None:                  # resampled to the model rate by the next step()
-            self._rin.push(st.rin, rates.owned_samples(samples, self.device))
-        else:
-            st.append(torch.as_tensor(samples, dtype=torch.float32).reshape(-1).to(self.device))
-
     def close(self, h):
         """End of h's input; too short an input raises ValueError here and retires h (the others are untouched)."""
-        st = self._stream(h)
-        if st.closed:
-            raise RuntimeError(f"close() called twice on stream {h!r}")
-        st.closed = True
-        n = st.n
-        if st.rin is not None:                  # the model-rate samples the input resampler has still to deliver
-            n += self._rin.final_count(st.rin) - self._rin.emitted(st.rin)
-            self._rin.end(st.rin)
+        n = self._end_input(h)
+        st = self._streams[h]
         try:
             st.T = stream_end_frames(n, self.n_fft, self.hop)
             if st.noise is not None and st.noise.shape[2] < st.T:
@@ -735,20 +674,8 @@ class LivePool(UnitPool):
             self._retire(h)
             raise
 
-    def _retire(self, h, finished=False):
-        """``finished``: h ran to its end, so its output resampler (if any) still delivers its tail in this step."""
-        st = self._streams.pop(h)
-        st.buf, st.len = st.buf[:0], 0
+    def _released(self, st):
         self._free_slots.append(st.slot)
-        self._retired.add(h)
-        if st.rin is not None:
-            self._rin.drop(st.rin)
-            self._rin_owner.pop(st.rin, None)
-        if st.rout is not None:
-            if finished:
-                self._rout_ending.append(st.rout)     # ended after this step's last output is queued
-            else:
-                self._rout.drop(st.rout)
 
     def _feed(self, jobs):
         """New posterior-encoder frames of every ready stream: the spectrogram of frames [n_q, n_q + nf) of its
@@ -760,10 +687,9 @@ class LivePool(UnitPool):
         for nf, chunk, _ in self._batches([j for j in jobs if j[1] > 0], key=lambda j: j[1]):
             srcs, recs, acc = [], [], 0
             for st, _, f0 in chunk:
-                wave = st.buf[:st.len]
-                srcs.append(wave)
-                recs.append((acc, st.len, f0 - st.base // self.hop))
-                acc += st.len
+                srcs.append(st.wave.valid())
+                recs.append((acc, st.wave.len, f0 - st.wave.base // self.hop))
+                acc += st.wave.len
             pool = srcs[0] if len(srcs) == 1 else torch.cat(srcs)
             rec_dev = torch.tensor(recs, dtype=torch.int64).to(self.device)
             spec = spec_eng.windows_multi(pool, rec_dev, nf)
@@ -823,11 +749,11 @@ class LivePool(UnitPool):
             jobs.append((st, nf, f0))
         if self.lookahead is not None:       # a regular round: a whole chunk of interior frames, closed or not
             for st, nf, f0 in jobs:
-                st.regular = nf == self.chunk and f0 + nf <= interior_frames(st.n, self.n_fft, self.hop)
+                st.regular = nf == self.chunk and f0 + nf <= interior_frames(st.wave.n, self.n_fft, self.hop)
         self._feed(jobs)
         for st, nf, f0 in jobs:
-            if not st.closed:
-                st.trim()
+            if not st.closed:           # no later frame reads before the reflect padding of the next one
+                st.wave.trim(st.cas.n[0], self.hop, self.pad)
         outs = self._run_units(plans)
         return outs if self.lookahead is None else self._emit_ahead(streams, outs)
 
@@ -963,12 +889,8 @@ class LivePool(UnitPool):
         """Rounds until no stream has a ready chunk; closed streams run to their end and are retired.  Streams with an
         input rate of their own first receive their new input at the model rate (one resampler launch for all of
         them); streams with an output rate of their own get theirs resampled after the rounds (one more launch)."""
-        for key, y in self._rin.step().items():
-            self._rin_owner[key].append(y)
-        res, routs = {}, {}
-        for h, st in self._streams.items():
-            if st.rout is not None:
-                routs[h] = st.rout
+        self._take_input()
+        res, routs = {}, self._output_rates()
         while True:
             ready = [(h, st, st.ready()) for h, st in self._streams.items()]
             ready = [r for r in ready if r[2] is not None]
@@ -980,16 +902,7 @@ class LivePool(UnitPool):
                 if st.closed and st.cas.done:
                     self._retire(h, finished=True)
         out = {h: (v[0] if len(v) == 1 else torch.cat(v)) for h, v in res.items()}
-        if routs:
-            for h, key in routs.items():
-                if h in out:
-                    self._rout.push(key, out.pop(h))
-            for key in self._rout_ending:
-                self._rout.end(key)
-            self._rout_ending.clear()
-            ys = self._rout.step()
-            out.update({h: ys[key] for h, key in routs.items() if key in ys})
-        return out
+        return self._deliver(out, routs)
 
 
 class LiveStream:

@@ -26,6 +26,7 @@ import torch
 from . import _lib, rates
 from .engine import item_tau, rows_tau, wavenet_keyword
 from . import noise as noise_mod
+from .streams import PushedPool, WaveBuffer
 from .generator import GENERATOR_MARGIN, generator_margin_frames, generator_stages, samples_per_frame
 from .params import ENC_Q_KERNEL, ENC_Q_LAYERS, FLOW_KERNEL, FLOW_LAYERS, N_FLOWS
 
@@ -379,22 +380,24 @@ class _StreamState:
         self.latency_seconds, self._latency = rates.stream_latency((self._Tw - 1) * c.hop + c.n_fft - c.pad, c.model_sr,
                                                                    self.sr_in, self.sr_out)
         self.rin = self.rout = None
-        self._buf = torch.empty(0, dtype=torch.float32, device=self.dev)
-        self._len = 0               # valid samples in _buf
-        self._base = 0              # file index of _buf[0]; a multiple of hop
-        self._n = 0                 # samples received
+        self.wave = WaveBuffer(self.dev)
         self._k = 0                 # next regular window
         self._emitted = 0           # frames of output handed out
         self._noise = noise.to(self.dev, torch.float32) if noise is not None else None
         # drawn noise, frames [_nz0, ..); a seeded stream keeps none
         self._nz = None if seed is not None else torch.empty(1, c.inter, 0, dtype=torch.float32, device=self.dev)
         self._nz0 = 0
-        self._closed = False
+        self.closed = False
         self._tail = None           # StreamPool: the end-of-input plan, taken by close()
 
     @property
     def latency_samples(self):
         return self._latency
+
+    @property
+    def _len(self):
+        """Samples buffered right now: what the tests of bounded memory read."""
+        return self.wave.len
 
     def _need(self, k):
         """Samples after which regular window k can run."""
@@ -425,24 +428,10 @@ class _StreamState:
 
     def _trim(self, keep_from_frame):
         """Drop buffered samples and noise no later window reads (whole hops, kept from before the reflect padding)."""
-        c = self.conv
-        base = max(0, keep_from_frame * c.hop - -(-c.pad // c.hop) * c.hop)
-        if base > self._base:
-            keep = self._buf[base - self._base:self._len].clone()
-            self._buf, self._len, self._base = keep, keep.numel(), base
+        self.wave.trim(keep_from_frame, self.conv.hop, self.conv.pad)
         if self._noise is None and self._seed is None and keep_from_frame > self._nz0:
             self._nz = self._nz[:, :, keep_from_frame - self._nz0:].clone()
             self._nz0 = keep_from_frame
-
-    def _append(self, x):
-        n = x.numel()
-        if self._len + n > self._buf.numel():          # grow geometrically: pushes of one sample stay O(1) amortised
-            grown = torch.empty(max(2 * self._buf.numel(), self._len + n, 1 << 16), dtype=torch.float32, device=self.dev)
-            grown[:self._len].copy_(self._buf[:self._len])
-            self._buf = grown
-        self._buf[self._len:self._len + n].copy_(x)
-        self._len += n
-        self._n += n
 
     def _tail_plan(self, n=None):
         """At the end of the input: ``[(record, Tw)]`` of the windows still to run -- the regular windows of the plan not
@@ -451,7 +440,7 @@ class _StreamState:
         padding or one frame, like ``spectrogram_torch``.  ``n``: the input's total length, when samples are still to
         be appended (an input resampler's tail); the samples received otherwise."""
         c = self.conv
-        T = stream_end_frames(self._n if n is None else n, c.n_fft, c.hop)
+        T = stream_end_frames(self.wave.n if n is None else n, c.n_fft, c.hop)
         plan, k, emitted = [], self._k, self._emitted
         if T > self._Tw:
             while k * self._core + self._Tw < T:
@@ -491,32 +480,32 @@ class ConversionStream(_StreamState):
             self.rout = rates.StreamResampler(conv.model_sr, self.sr_out, self.dev)
 
     def _run(self, rec, Tw):
-        """One window of the stream: its core samples as a fresh device tensor.  The buffer starts ``_base`` samples
+        """One window of the stream: its core samples as a fresh device tensor.  The buffer starts ``wave.base`` samples
         into the file (whole hops), so the window is framed at its first frame relative to the buffer; only a window
-        at the file's start (``_base`` 0) or end reads reflect padding, and the buffer holds that end."""
+        at the file's start (``wave.base`` 0) or end reads reflect padding, and the buffer holds that end."""
         c = self.conv
         f0, lo, hi = rec
-        rel = f0 - self._base // c.hop
-        assert self._base == 0 or rel * c.hop - c.pad >= 0, "stream buffer trimmed past a window's first sample"
+        rel = f0 - self.wave.base // c.hop
+        assert self.wave.base == 0 or rel * c.hop - c.pad >= 0, "stream buffer trimmed past a window's first sample"
         plan_dev = torch.tensor([(rel, rel + lo - f0, rel + hi - f0)], dtype=torch.int64).to(self.dev)
         out = torch.empty((hi - lo) * c.spf, dtype=torch.float32, device=self.dev)
         nz = self._noise_for(f0, Tw)
         seed = None
         if self._seed is not None:
             nz, seed = None, [nz]
-        c._launch(self._buf[:self._len], self._len, plan_dev, plan_dev[:, 0].contiguous(), Tw, self.src_se, self.tgt_se,
+        c._launch(self.wave.valid(), self.wave.len, plan_dev, plan_dev[:, 0].contiguous(), Tw, self.src_se, self.tgt_se,
                   self.tau, nz, out, rel + lo - f0, **noise_mod.kw(seed))
         self._emitted = hi
         return out
 
     @torch.no_grad()
     def push(self, samples):
-        if self._closed:
+        if self.closed:
             raise RuntimeError("push() after close()")
         x = torch.as_tensor(samples, dtype=torch.float32).reshape(-1).to(self.dev)
-        self._append(x if self.rin is None else self.rin.push(x))
+        self.wave.append(x if self.rin is None else self.rin.push(x))
         outs = []
-        while self._n >= self._need(self._k):
+        while self.wave.n >= self._need(self._k):
             rec = self._regular(self._k)
             outs.append(self._run(rec, self._Tw))
             self._k += 1
@@ -529,18 +518,18 @@ class ConversionStream(_StreamState):
 
     @torch.no_grad()
     def close(self):
-        if self._closed:
+        if self.closed:
             raise RuntimeError("close() called twice")
-        self._closed = True
+        self.closed = True
         if self.rin is not None:
-            self._append(self.rin.close())
+            self.wave.append(self.rin.close())
         outs = [self._run(rec, Tw) for rec, Tw in self._tail_plan()]
-        self._buf, self._len = self._buf[:0], 0
+        self.wave.release()
         y = outs[0] if len(outs) == 1 else torch.cat(outs)
         return y if self.rout is None else self.rout.close(y)
 
 
-class StreamPool:
+class StreamPool(PushedPool):
     """Many live streams on one window grid, their ready windows converted together: one ``step()`` runs every ready
     window of every open stream in ``ceil(R / max_windows_per_launch)`` launches (fewer per stream than one launch per
     window, which is what the solo ``ConversionStream`` costs).
@@ -571,22 +560,11 @@ class StreamPool:
             raise _lib.OvError("StreamPool: the pool's tau is one number; give a stream its own with open(tau=)")
         self.ladder = launch_ladder(max_windows_per_launch)
         self.max_windows_per_launch = self.ladder[-1]
-        self._streams = {}          # handle -> _StreamState, in handle order
-        self._next = 0
-        self._retired = set()
-        dev = conv._device()
-        self._rin, self._rout = rates.ResamplerBank(dev), rates.ResamplerBank(dev)
-        self._rin_owner = {}        # input resampler key -> stream
-        self._rout_ending = []      # output resampler keys of streams that finished in this step
+        self._init_streams(conv._device(), conv.model_sr)      # handle -> _StreamState
         engine = getattr(conv.model, "engine", None)
         if callable(engine):
             eng = engine()
             eng.resident_workspaces = max(eng.resident_workspaces, len(self.ladder) + 1)
-
-    @property
-    def active(self):
-        """Handles of the streams not yet retired (open, or closed with their tail still to run)."""
-        return list(self._streams)
 
     @property
     def latency_samples(self):
@@ -597,99 +575,51 @@ class StreamPool:
 
     def open(self, src_se, tgt_se, noise=None, sr_in=None, sr_out=None, *, seed=None, tau=None):
         """A new stream -> its handle.  ``tau``: None = the pool's, else this stream's own number, for life."""
-        tau = self.tau if tau is None else item_tau(1, tau)
-        if not isinstance(tau, float):
-            raise _lib.OvError("StreamPool.open: tau is one number per stream")
+        tau = self._stream_tau(tau, "StreamPool.open")
         st = _StreamState(self.conv, src_se, tgt_se, noise, sr_in=sr_in, sr_out=sr_out, seed=seed)
         st.tau = tau
-        msr = self.conv.model_sr
-        if st.sr_in is not None and st.sr_in != msr:
-            st.rin = self._rin.open(st.sr_in, msr)
-            self._rin_owner[st.rin] = st
-        if st.sr_out is not None and st.sr_out != msr:
-            st.rout = self._rout.open(msr, st.sr_out)
-        h = self._next
-        self._next += 1
-        self._streams[h] = st
-        return h
+        return self._register(st, st.sr_in, st.sr_out)
 
     def latency_of(self, h):
         """``(seconds, samples)``: stream h's latency bound at its own rates (samples in its output rate)."""
         st = self._stream(h)
         return st.latency_seconds, st.latency_samples
 
-    def _stream(self, h):
-        st = self._streams.get(h)
-        if st is None:
-            raise RuntimeError(f"stream {h!r} is closed" if h in self._retired else f"no stream {h!r} in this pool")
-        return st
-
-    @torch.no_grad()
-    def push(self, h, samples):
-        st = self._stream(h)
-        if st._closed:
-            raise RuntimeError(f"push() after close() on stream {h!r}")
-        if st.rin is not None:                  # resampled to the model rate by the next step()
-            self._rin.push(st.rin, rates.owned_samples(samples, st.dev))
-        else:
-            st._append(torch.as_tensor(samples, dtype=torch.float32).reshape(-1).to(st.dev))
-
     def close(self, h):
         """End of h's input.  Input shorter than the reflect padding or one frame raises ValueError here and retires h
         (the other streams are untouched)."""
-        st = self._stream(h)
-        if st._closed:
-            raise RuntimeError(f"close() called twice on stream {h!r}")
-        st._closed = True
-        n = None
-        if st.rin is not None:                  # the model-rate samples the input resampler has still to deliver
-            n = st._n + self._rin.final_count(st.rin) - self._rin.emitted(st.rin)
-            self._rin.end(st.rin)
+        n = self._end_input(h)
+        st = self._streams[h]
         try:
             st._tail = st._tail_plan(n)
         except ValueError:
             self._retire(h)
             raise
 
-    def _retire(self, h, finished=False):
-        """``finished``: h ran its tail, so its output resampler (if any) still delivers its own in this step."""
-        st = self._streams.pop(h)
-        st._buf, st._len = st._buf[:0], 0
-        self._retired.add(h)
-        if st.rin is not None:
-            self._rin.drop(st.rin)
-            self._rin_owner.pop(st.rin, None)
-        if st.rout is not None:
-            if finished:
-                self._rout_ending.append(st.rout)     # ended after this step's last output is queued
-            else:
-                self._rout.drop(st.rout)
-
     @torch.no_grad()
     def step(self):
         c = self.conv
-        for key, y in self._rin.step().items():
-            self._rin_owner[key]._append(y)
-        routs = {h: st.rout for h, st in self._streams.items() if st.rout is not None}
+        self._take_input()
+        routs = self._output_rates()
         sources, taus, jobs, spans, acc = [], [], [], {}, 0
         for h, st in self._streams.items():
-            if st._closed:
+            if st.closed:
                 recs = st._tail
             else:
                 recs = []
-                while st._n >= st._need(st._k):
+                while st.wave.n >= st._need(st._k):
                     recs.append((st._regular(st._k), st._Tw))
                     st._k += 1
             if not recs:
                 continue
             first = acc
-            sh = st._base // c.hop
+            sh = st.wave.base // c.hop
             for (f0, lo, hi), Tw in recs:
-                assert st._base == 0 or (f0 - sh) * c.hop - c.pad >= 0, "stream buffer trimmed past a window's first sample"
+                assert st.wave.base == 0 or (f0 - sh) * c.hop - c.pad >= 0, "stream buffer trimmed past a window's first sample"
                 jobs.append((len(sources), f0 - sh, lo - sh, hi - sh, Tw, st._noise_for(f0, Tw), st.src_se, st.tgt_se,
                              acc))
                 acc += hi - lo
-            sources.append(st._buf[:st._len])
+            sources.append(st.wave.valid())
             taus.append(st.tau)
             spans[h] = (first, acc, recs[-1][0])
         if not jobs:
@@ -703,17 +633,8 @@ class StreamPool:
             outs[h] = out[a * c.spf:b * c.spf]
             st = self._streams[h]
             st._emitted = hi
-            if st._closed:
+            if st.closed:
                 self._retire(h, finished=True)
             else:
                 st._trim(f0 + 1)        # every later window (regular or the last one) starts after this one
-        if routs:
-            for h, key in routs.items():
-                if h in outs:
-                    self._rout.push(key, outs.pop(h))
-            for key in self._rout_ending:
-                self._rout.end(key)
-            self._rout_ending.clear()
-            ys = self._rout.step()
-            outs.update({h: ys[key] for h, key in routs.items() if key in ys})
-        return outs
+        return self._deliver(outs, routs)

@@ -362,7 +362,7 @@ def test_seeded_streams_hold_no_noise_tensor(tcc):
         ls.push(wave[i * 9000:(i + 1) * 9000])
     live = ls._pool._streams[ls._h]
     assert live.cas.n[0] >= 15 and live.noise is None and live.seed == (SEED, 0)
-    tensors = [k for k, v in vars(live).items() if torch.is_tensor(v) and k != "buf"]
+    tensors = [k for k, v in {**vars(live), **vars(live.wave)}.items() if torch.is_tensor(v) and k != "buf"]
     assert tensors == [], tensors
 
 
