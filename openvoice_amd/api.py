@@ -499,7 +499,7 @@ class ToneColorConverter(OpenVoiceBaseClass):
         embs = []
         for lo, hi in plan:
             spec, frames = self._spec_ragged(pieces[lo:hi])                  # [n, 513, Tw], one launch pair
-            embs.append(engine.reference_encoder_ragged(spec, frames))       # [n, gin], one launch sequence
+            embs.append(engine.ref_enc.reference_encoder_ragged(spec, frames))  # [n, gin], one launch sequence
             self.last_extract_se_batches.append(hi - lo)
         g = torch.cat(embs) if len(embs) > 1 else embs[0]
         # per-voice mean: row P of gz is zero, and a voice with fewer pieces than the longest adds it (x + 0 = x)

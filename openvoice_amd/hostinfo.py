@@ -61,11 +61,12 @@ def _glob(*patterns):
 
 
 def kernel_source_digest():
-    """sha256 (16 hex digits) over the kernel sources, the C ABI header and the launch sequence (engine.py and the stage
-    geometry it reads from generator.py) -- what decides the HBM traffic of a conversion.  Measurement records
+    """sha256 (16 hex digits) over the kernel sources, the C ABI header and the launch sequence (engine.py, the fp32
+    generator of generator_fp32.py, the launchers of launch.py and the stage geometry of generator.py) -- what decides
+    the HBM traffic of a conversion.  Measurement records
     (profiles/pmc_traffic_latest.json) carry it, and bench.py only reports a PMC traffic figure whose digest equals the
     running tree's."""
-    files = _glob("csrc/*.hip", "csrc/*.h", "../include/*.h") + ["engine.py", "generator.py"]
+    files = _glob("csrc/*.hip", "csrc/*.h", "../include/*.h") + ["engine.py", "generator_fp32.py", "launch.py", "generator.py"]
     # the opt-in paths' kernels (bf16 generator: conv1d_bf16*; split-precision MRF: conv1d_split3*) launch nothing on
     # the fp32 path the record is about
     return _digest(f for f in files if not os.path.basename(f).startswith(("conv1d_bf16", "conv1d_split3")))

@@ -37,7 +37,7 @@ class _ReferenceEncoderHandle(nn.Module):
         object.__setattr__(self, "_root", weakref.ref(root))
 
     def forward(self, inputs, mask=None):
-        return self._root().engine().reference_encoder(inputs)
+        return self._root().engine().ref_enc(inputs)
 
 
 class SynthesizerTrn(nn.Module):

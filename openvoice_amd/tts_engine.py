@@ -8,7 +8,7 @@ inverse rational-quadratic spline of ConvFlow modules.py:485-516 / transforms.py
 duration arithmetic and the duration-driven expansion of the prior (models.py:474-487) -- runs on the
 kernels of csrc/tts.hip plus the MFMA conv kernel for every dense 1x1 / k3 conv.  The frame-rate back
 end (flow in reverse, HiFi-GAN generator: 98 % of the FLOPs) is the converter engine's
-(``engine.ConverterEngine._flow`` / ``.decode``), conditioned on the speaker-table embedding.
+(``engine.ConverterEngine._flow``, ``generator_fp32.GeneratorFp32.decode``), conditioned on the speaker-table embedding.
 
 Load-time transforms: the q, k, v projections of a layer are concatenated into one 576-row conv; the
 single-row ``dp.proj`` and the 29-row spline projections are zero-padded to 32 rows (the conv kernel
@@ -157,7 +157,7 @@ class TtsEngine:
     # ---- helpers ---------------------------------------------------------------------------------------
     def _conv(self, layer, x, xc, out, oc, B, T, ld, **kw):
         """Token-rate conv: x (B, xc, ld) -> out (B, oc, ld)."""
-        self.core._conv(layer, x, 0, xc * ld, out, 0, oc * ld, B, T, x_ld=ld, out_ld=ld, tag="tts", **kw)
+        self.core.launcher.conv(layer, x, 0, xc * ld, out, 0, oc * ld, B, T, x_ld=ld, out_ld=ld, tag="tts", **kw)
 
     def _ln(self, x, gamma, beta, out, B, C, T, ld, res=None, res2=None, mask=None, flags=0):
         _lib.call("ov_layernorm_ch_f32", x, res, gamma, beta, res2, mask, out, B, C, T, ld, LN_EPS, flags)
@@ -232,7 +232,7 @@ class TtsEngine:
         # ---- duration predictor (models.py:86-100) --------------------------------------------------------
         Fd = self.dp_filter
         xd, d1, d2, dp_out = f(B, H, Lx), f(B, Fd, Lx), f(B, Fd, Lx), f(B, 32, Lx)
-        cg = self.core._linear(g, self.dp_cond_w, self.dp_cond_b)
+        cg = self.core.launcher.linear(g, self.dp_cond_w, self.dp_cond_b)
         _lib.call("ov_add_bias_mask_f32", x, cg, mask, xd, B, H, Tx, Lx)
         self._conv(self.dp_c1, xd, H, d1, Fd, B, Tx, Lx)
         self._ln(d1, *self.dp_n[0], d1, B, Fd, Tx, Lx, mask=mask, flags=LN_PRE_RELU)
@@ -242,7 +242,7 @@ class TtsEngine:
         # ---- stochastic duration predictor, reverse (models.py:129-138, :171-180) -------------------------
         Fs = self.sdp_filter
         xs, t1, t2, hflow, hp = f(B, Fs, Lx), f(B, Fs, Lx), f(B, Fs, Lx), f(B, Fs, Lx), f(B, 32, Lx)
-        cs = self.core._linear(g, self.sdp_cond_w, self.sdp_cond_b)
+        cs = self.core.launcher.linear(g, self.sdp_cond_w, self.sdp_cond_b)
         self._conv(self.sdp_pre, x, H, xs, Fs, B, Tx, Lx, bias_b=cs, bias_b_bs=Fs)
         self._dds(self.sdp_convs, xs, t1, t2, mask, B, Fs, Tx, Lx)
         self._conv(self.sdp_proj, xs, Fs, t1, Fs, B, Tx, Lx, flags=F_MASK_V, mask=mask, mask_bs=Lx)
@@ -294,7 +294,7 @@ class TtsEngine:
         ``(s, b)`` (or one seed / pair per row): ``noise_w`` is purpose 1 over the token positions ``[0, Tx)``,
         ``noise_z`` purpose 2 over the frames ``[0, Ty)``, generated straight into the workspace rows once ``Ty`` is
         known -- nobody has to guess a bound for it.
-        ``skip_padding``: the generator computes only ``y_length + core.limit_margin(B, Ty)`` frames (16-20) of each
+        ``skip_padding``: the generator computes only ``y_length + core.generator.limit_margin(B, Ty)`` frames (16-20) of each
         utterance of a padded batch
         (valid samples bit-identical, the padded tail of ``o`` zero; ``ConverterEngine.voice_conversion``).
         ``generator``: ``"fp32"`` (default) or ``"bf16"`` -- the generator alone on the bf16 channels-last kernels
@@ -343,7 +343,7 @@ class TtsEngine:
                       ws["noise"], C * Ly, Ly, z_p, m_p, logs_p, attn, B, C, Tx, Ty, Ly, noise_scale_b)
         cond_flow = [core._wn_cond(cp["wn"], g) for cp in core.couplings]
         core._flow(z_p, z, ws, B, Ty, cond_flow, mask_y, reverse=True)      # z_p -> z, no copy
-        cond_d = core._linear(g, core.dec_cond_w, core.dec_cond_b)
+        cond_d = core.generator.cond(g)
         Td = Ty if max_len is None else min(Ty, int(max_len))
         if generator == "bf16":
             gen = core.bf16_generator()
@@ -352,7 +352,8 @@ class TtsEngine:
             else:
                 o = gen.decode(z[:, :, :Td], g.unsqueeze(-1))
         else:
-            o = core.decode(z, cond_d, ws, T=Td, limits=core.frame_limits(y_len, Td) if skip_padding else None)
+            gen = core.generator
+            o = gen.decode(z, cond_d, ws, T=Td, limits=gen.frame_limits(y_len, Td) if skip_padding else None)
         outs = tuple(t[:, :, :Ty].contiguous() for t in (z, z_p, m_p, logs_p))
         self.last_logw = logw[:, :Tx]
         return (o, attn.unsqueeze(1) if attn is not None else None, mask_y[:, :Ty].unsqueeze(1).contiguous(), outs)

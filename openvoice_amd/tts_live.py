@@ -179,7 +179,7 @@ class TtsLivePool(UnitPool):
             st.T = self.frames[h] = int(y_len[b])
             g = fh["g"][b:b + 1].contiguous()                # the launches of a solo infer: one row each
             st.conds = dict(tgt=[core._wn_cond(cp["wn"], g) for cp in core.couplings],
-                            d=core._linear(g, core.dec_cond_w, core.dec_cond_b))
+                            d=core.generator.cond(g))
             if self.generator == "bf16":
                 st.conds["d16"] = core.live_cond_bf16(g)
 

@@ -99,7 +99,7 @@ def main():
         del src, dst
     if not args.no_fp32:
         eng = ConverterEngine(sd, CFG, 513, dev, zero_g=False)
-        cond = eng._linear(g.reshape(1, -1), eng.dec_cond_w, eng.dec_cond_b)
+        cond = eng.generator.cond(g.reshape(1, -1))
         dt32, o32 = timeit(lambda: eng.decode(z, cond))
         err = (o16 - o32).abs()
         out["fp32_generator_ms_per_batch"] = round(dt32 * 1e3, 3)
