@@ -555,7 +555,11 @@ int ov_conv_post_tanh_f32(const float* x, const float* w, float* out, int B, int
 /* The same with a length-aware tail: samples t >= col_limit[b] * col_limit_scale of utterance b are written as 0
  * without reading x there (the generator launches before it left those columns unwritten, see
  * ov_conv1d_params.col_limit).  col_limit NULL = ov_conv_post_tanh_f32.  (A col_limit_scale that is not a multiple
- * of 4 takes the per-sample kernel: the 16-byte path decides per 4 consecutive samples.) */
+ * of 4 takes the per-sample kernel: the 16-byte path decides per 4 consecutive samples.)
+ * Read reach: with n = min(L, col_limit[b] * col_limit_scale), the samples t < n are those of the unlimited launch bit
+ * for bit and depend on x[b][c][0 .. n + (K - 1) / 2) only: the conv of a sample below the limit reaches (K - 1) / 2
+ * (= 3 at K = 7) columns past it, which the generator must have written; nothing from column n + (K - 1) / 2 on enters a
+ * result (the 16-byte path may load the rest of that 4-sample group, it never uses it). */
 int ov_conv_post_tanh_limited_f32(const float* x, const float* w, float* out, int B, int C, int L, int K,
                                   float in_slope, const int32_t* col_limit, int col_limit_scale, ov_stream_t stream);
 /* limits[b] = min(T, max(0, lengths[b]) + margin): the frames of utterance b the generator has to produce so that

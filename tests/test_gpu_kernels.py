@@ -8,6 +8,9 @@ The frame-rate epilogues (GATE, RESSKIP, COUPLE, POSTERIOR, CONVT, MAGNITUDE, fr
 instance and element by element, to float64 mirrors in tests/test_gpu_frame_kernels.py (oracle/fp32_ref.py).
 The sample-rate ResBlock (MRF) LINEAR instances -- every X(...) line of conv1d_inst_a.hip .. conv1d_inst_f.hip with tile, chunk
 and loader count forced -- are held the same way in tests/test_gpu_mrf_kernels.py; the norm-wise bars below stay, they are weaker.
+The waveform-edge entry points (conv_post + tanh and its limited form, ov_linear_f32, the sequence mask, the frame limits, the
+unpad, the window stitch and the three framing gathers) are held element by element, or bit for bit, in
+tests/test_gpu_edge_kernels.py (oracle/edge_ref.py).
 """
 import ctypes
 
