@@ -513,6 +513,28 @@ int ov_wm_embed_windows_f32(const float* src, int64_t src_elems, float* dst, int
                             int W, int64_t key, float strength, float floor_level, ov_stream_t stream);
 int ov_wm_detect_windows_f32(const float* src, int64_t src_elems, const int64_t* records, int W, int64_t key,
                              float strength, float floor_level, float* q_out, float* level_out, ov_stream_t stream);
+/* The block-wise form of the same mark, for streams (openvoice_amd/watermark.py, "streams"): a carrier window of 16 000
+ * samples is cut into 16 000 / H blocks of H samples, H (the hold) one of 16000, 8000, 4000, 3200, 1600, 800, 640, and
+ * per window and bit one float R_j >= 0, the surplus of the blocks so far, is carried.  For a block x with p_j and
+ * a_m = max(strength * sqrt(mean_block x^2), floor_level) of the block alone, chips counted from the window's start:
+ *   u_j = b_j p_j + R_j,   d_j = b_j max(a_m - u_j, 0),   y[i] = x[i] + d_{i % 32} c[i],   R_j <- max(u_j - a_m, 0)
+ * so that b_j p_j(y) >= mean_m a_m >= floor_level over the whole window: ov_wm_detect_windows_f32 reads every bit.
+ * records is a DEVICE int64 [R][8] of (src_off, dst_off, H, blocks, bits, chip_off, state_row, reset): a run of `blocks`
+ * consecutive blocks of one window, the first one chip_off samples (a multiple of H) after the window's start, source
+ * and destination offsets in elements of src / dst (dst may be src), the payload in the low 32 bits of `bits`.  state
+ * is DEVICE float [state_rows][32]: the record's workgroup (256 threads, one per record) starts from row state_row, or
+ * from zero when reset = 1, walks its blocks in order and writes the row back at the end.  No two records of one launch
+ * may name the same row, and their destinations must not overlap.  A block is reduced in the order
+ * ov_wm_embed_windows_f32 reduces a window, so H = 16 000 gives that entry point's samples bit for bit, and what a run
+ * gets depends on its samples, payload, parameters and incoming row alone.  Host checks (OV_E_BADARG): null pointers,
+ * extents <= 0, R outside [1, 65535], state_rows <= 0, key < 0, strength outside [0, 1], floor_level outside (0, 1];
+ * pointers 4-byte aligned (OV_E_ALIGN).  The kernel checks every record: one whose H is not in the list, with blocks
+ * < 1, chip_off negative or no multiple of H, chip_off + blocks H > 16 000, state_row outside [0, state_rows), reset
+ * other than 0 / 1, a negative offset, or whose run leaves [0, src_elems) or [0, dst_elems) writes nothing, neither
+ * samples nor state.  Additive to ABI 2.12: found by name. */
+int ov_wm_embed_blocks_f32(const float* src, int64_t src_elems, float* dst, int64_t dst_elems, const int64_t* records,
+                           int R, float* state, int64_t state_rows, int64_t key, float strength, float floor_level,
+                           ov_stream_t stream);
 
 /* Rate conversion at the audio boundary, reference openvoice/api.py:123,144 (``librosa.load(path, sr=...)`` = resampy's
  * kaiser_best band-limited sinc interpolation): a polyphase FIR over a mono waveform,
@@ -953,7 +975,7 @@ int ov_conv1d_wino_pack_f32(const float* w, int Cout, int Cin, int K, float* dst
  * workgroup; ov_conv1d_wino_chunk(11, 32) = 2 where 2.07 returned 0).  2.09: ov_conv1d_wino_params.out_slope (the field that
  * was `reserved0`: same size and offset, 0 = none).  2.10: ov_frame_hops_windows_f32, ov_stitch_window_cores_f32.  2.11: ov_frame_hops_multi_f32.  2.12: ov_carry_rows_f32 (and, added later within 2.12 without a version change, ov_polyphase_fir_rows_f32 and ov_vad_frame_energy_f32, ov_vad_segments_i32, ov_vad_compact_f32, ov_rows_f32_to_cl_bf16, ov_cl_bf16_to_rows_f32: additive symbols, which the Python binding looks up by name when it loads the library; likewise ov_wn_layer_wino_f32, ov_wn_layer_wino_tile, ov_wn_wino_pack_size and ov_wn_wino_pack_f32, and ov_join_segments_f32, and ov_pack_groups_cl_bf16 and ov_unpack_groups_f32, and ov_wn_layer_bf16, ov_wn_layer_bf16_supported,
  * ov_wn_layer_bf16_tile, ov_wn_bf16_pack_size and ov_wn_bf16_pack, and ov_wm_embed_windows_f32 and
- * ov_wm_detect_windows_f32; and ov_conv1d_params.scale_b, one pointer appended
+ * ov_wm_detect_windows_f32, and ov_wm_embed_blocks_f32; and ov_conv1d_params.scale_b, one pointer appended
  * to the struct and read only under OV_F_SCALE_B, a flag no older caller sets: the version stays 212 and a caller built
  * against the shorter struct stays binary compatible).  The Python binding
  * refuses a library older than the entry points it calls (openvoice_amd/_lib.py MIN_VERSION). */

@@ -640,7 +640,8 @@ class ToneColorConverter(OpenVoiceBaseClass):
         d = self.hps.data
         return longform.WindowedConverter(self.model, n_fft=d.filter_length, hop=d.hop_length, window_frames=window_frames,
                                           windows_per_launch=windows_per_launch, graph=self.use_graphs,
-                                          model_sr=d.sampling_rate, wavenet=wavenet)
+                                          model_sr=d.sampling_rate, wavenet=wavenet,
+                                          watermark_model=self.watermark_model)
 
     def _to_model_rate(self, audio_or_path, sr):
         """(device waveform at the model rate, its rate before resampling or None): a path is decoded and resampled on
@@ -706,7 +707,8 @@ class ToneColorConverter(OpenVoiceBaseClass):
         audio_io.write(output_path, audio, self.hps.data.sampling_rate if out_sr is None else out_sr)
 
     def stream(self, src_se, tgt_se, tau=0.3, window_frames=longform.DEFAULT_STREAM_WINDOW_FRAMES, noise=None, sr_in=None,
-               sr_out=None, *, seed=None, wavenet=None):
+               sr_out=None, *, seed=None, wavenet=None, message=None, watermark_hold=watermark_mod.DEFAULT_HOLD,
+               message_repeat=False):
         """A ``longform.ConversionStream``: ``push(samples)`` -> newly finished converted samples (device tensor, maybe
         empty), ``close()`` -> the rest, ``latency_samples`` = ``(window_frames - 1) * hop + n_fft - (n_fft - hop) / 2``
         at the model rate.  ``sr_in`` / ``sr_out``: the rate of the pushes / of the output (None: the model rate); the
@@ -715,15 +717,26 @@ class ToneColorConverter(OpenVoiceBaseClass):
         and so does
         ``seed`` (stream ``(seed, 0)``, or a pair), which needs no length and keeps no noise tensor.  The
         output equals ``convert_long(..., windows_per_launch=1)`` of the whole input, bit for bit -- with rates, of the
-        input resampled to the model rate, and resampled to ``sr_out`` after (``audio_io.resample_on_device``)."""
+        input resampled to the model rate, and resampled to ``sr_out`` after (``audio_io.resample_on_device``).
+
+        ``message`` (keyword only; None: the stream is not marked, all of the above unchanged): with
+        ``watermark="native"`` the output carries the block-wise form of the native watermark (``watermark.py``,
+        "streams"), made at the model rate before the output resampler and read by ``detect_watermark``.
+        ``watermark_hold`` = H, one of 16000, 8000, 4000, 3200, 1600, 800, 640: a sample leaves once its block of H
+        samples is whole, at most H - 1 samples later than unmarked (``latency_samples`` says so); at 16000 the output
+        is the unmarked stream's passed through ``mark_many``, bit for bit; a shorter hold costs signal-to-mark ratio
+        (DESIGN.md section 27).  ``message_repeat``: window n carries group n % G for the stream's life, instead of the
+        first G windows only.  The samples of a block unfinished at ``close()`` leave unmarked.  ValueError, at the
+        call, for a message without the native watermark and for a hold outside the list."""
         return self._windowed(window_frames, 1, wavenet).stream(src_se, tgt_se, tau=tau, noise=noise, sr_in=sr_in, sr_out=sr_out,
-                                                       **noise_mod.kw(seed))
+                                                       message=message, watermark_hold=watermark_hold,
+                                                       message_repeat=message_repeat, **noise_mod.kw(seed))
 
     # ---- many streams and recordings in shared launches -------------------------------------------------------------
     def stream_pool(self, tau=0.3, window_frames=longform.DEFAULT_STREAM_WINDOW_FRAMES,
                     max_windows_per_launch=longform.DEFAULT_POOL_WINDOWS_PER_LAUNCH, *, wavenet=None):
         """A ``longform.StreamPool``: many live streams (``open(src_se, tgt_se, noise=None, sr_in=None, sr_out=None,
-        seed=None)`` ->
+        seed=None, tau=None, message=None, watermark_hold=16000, message_repeat=False)`` ->
         handle, ``push(h, samples)``, ``close(h)``), whose ready windows one ``step()`` converts together, up to
         ``max_windows_per_launch`` per launch -> ``{handle: newly finished samples}``; streams at rates of their own are
         resampled in one launch per direction and step.  Each stream's output equals a ``stream(...)`` fed the same
@@ -733,7 +746,8 @@ class ToneColorConverter(OpenVoiceBaseClass):
 
     # ---- low-latency live streams ------------------------------------------------------------------------------------
     def live_stream(self, src_se, tgt_se, tau=0.3, chunk_frames=15, noise=None, sr_in=None, sr_out=None,
-                    generator="fp32", *, seed=None, wavenet=None, lookahead_frames=None, crossfade_samples=None):
+                    generator="fp32", *, seed=None, wavenet=None, lookahead_frames=None, crossfade_samples=None,
+                    message=None, watermark_hold=watermark_mod.DEFAULT_HOLD, message_repeat=False):
         """A ``live.LiveStream``: the conversion as a cascade of units that carry their recent input as state.
         ``push(samples)`` -> newly finished samples, ``close()`` -> the rest, ``latency_samples`` =
         ``live.live_latency_samples`` (1.45 s at 15 frames).  ``chunk_frames``: a positive multiple of 15 (the Winograd
@@ -759,19 +773,24 @@ class ToneColorConverter(OpenVoiceBaseClass):
         launched.  ``crossfade_samples`` = X: the first X samples of a piece are blended with what the previous round's
         preview held for them (raised-cosine fade-in, ``ov_crossfade_rows_f32``); ``0 <= X <= min(hop * A, hop *
         chunk_frames)``, default ``min(hop, hop * A)`` -- a default nobody has measured on a real voice.  X = 0 keeps
-        the contract above bit for bit."""
+        the contract above bit for bit.
+
+        ``message`` / ``watermark_hold`` / ``message_repeat`` (keyword only): as for ``stream`` -- the block-wise native
+        watermark of what the stream emits (emitted samples are final; the crossfade runs before the mark), at most
+        ``watermark_hold - 1`` samples later, which ``latency_samples`` includes."""
         from . import live
         d = self.hps.data
         return live.LiveStream(self.model, src_se, tgt_se, tau=tau, chunk_frames=chunk_frames, noise=noise,
                                n_fft=d.filter_length, hop=d.hop_length, sr_in=sr_in, sr_out=sr_out,
                                model_sr=d.sampling_rate, generator=generator, wavenet=wavenet,
                                lookahead_frames=lookahead_frames, crossfade_samples=crossfade_samples,
-                               **noise_mod.kw(seed))
+                               watermark_model=self.watermark_model, message=message, watermark_hold=watermark_hold,
+                               message_repeat=message_repeat, **noise_mod.kw(seed))
 
     def live_pool(self, tau=0.3, chunk_frames=15, max_streams_per_launch=32, generator="fp32", *, wavenet=None,
                   lookahead_frames=None, crossfade_samples=None):
         """A ``live.LivePool``: many live streams (``open(src_se, tgt_se, noise=None, sr_in=None, sr_out=None,
-        seed=None)`` /
+        seed=None, tau=None, message=None, watermark_hold=16000, message_repeat=False)`` /
         ``push`` / ``close``), every stream with a ready chunk converted by one ``step()`` in launches of up to
         ``max_streams_per_launch`` rows per unit; streams at rates of their own are resampled in one launch per direction
         and step.  Each stream equals its solo ``live_stream``.  ``tau`` is the pool's default: ``open(..., tau=None)``
@@ -785,7 +804,8 @@ class ToneColorConverter(OpenVoiceBaseClass):
         d = self.hps.data
         return live.LivePool(self.model, tau=tau, chunk_frames=chunk_frames, max_streams_per_launch=max_streams_per_launch,
                              n_fft=d.filter_length, hop=d.hop_length, model_sr=d.sampling_rate, generator=generator,
-                             wavenet=wavenet, lookahead_frames=lookahead_frames, crossfade_samples=crossfade_samples)
+                             wavenet=wavenet, lookahead_frames=lookahead_frames, crossfade_samples=crossfade_samples,
+                             watermark_model=self.watermark_model)
 
     @wavenet_keyword
     def convert_many(self, items, src_se, tgt_se, tau=0.3, window_frames=longform.DEFAULT_WINDOW_FRAMES,

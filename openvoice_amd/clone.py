@@ -343,7 +343,8 @@ class VoiceCloner:
 
     def speak_stream_ids(self, id_sequences, speaker, src_se, tgt_se, speed=1.0, *, seed=None, tau=0.3, out_sr=None,
                          chunk_frames=60, live_chunk_frames=15, generator="fp32", wavenet=None, noise_scale=0.667,
-                         noise_scale_w=0.6, lookahead_frames=None):
+                         noise_scale_w=0.6, lookahead_frames=None, message=None, watermark_hold=16000,
+                         message_repeat=False):
         """``speak_ids`` as a Python generator of device tensors: every chunk of ``tts_stream_from_ids`` (gaps
         included) is pushed into one stream of a converter ``LivePool`` (``sr_in`` = the TTS model's rate where the two
         differ, ``sr_out=out_sr``) and what that stream returns is yielded; the stream is closed at the end.
@@ -351,15 +352,20 @@ class VoiceCloner:
         rate, out_sr=out_sr)`` of the concatenated ``tts_stream_from_ids(..., seed=seed)`` output (bit for bit with
         direct kernels and equal rates; within the rates' bar otherwise).  ``seed``: the TTS sentences take streams
         ``k + i`` of it, the converter's posterior noise stream ``k`` (purpose 0); None: nothing is reproducible.
-        ``chunk_frames`` / ``live_chunk_frames``: the chunk of the synthesis / of the conversion stream."""
+        ``chunk_frames`` / ``live_chunk_frames``: the chunk of the synthesis / of the conversion stream.
+        ``message`` / ``watermark_hold`` / ``message_repeat``: the conversion stream's block-wise native watermark, as
+        for ``ToneColorConverter.live_stream`` (checked at the call; ``tts_live_pool`` speech itself is never marked)."""
         if lookahead_frames is not None:          # at the call, not at the first next()
             raise ValueError("lookahead_frames belongs to the converter's live streams (live_stream / live_pool): "
                              "speak_stream* emits committed samples only")
+        from . import watermark as watermark_mod
+        watermark_mod.stream_mark(self.converter.watermark_model, message, watermark_hold, message_repeat)
         return self._speak_stream_ids(id_sequences, speaker, src_se, tgt_se, speed, seed, tau, out_sr, chunk_frames,
-                                      live_chunk_frames, generator, wavenet, noise_scale, noise_scale_w)
+                                      live_chunk_frames, generator, wavenet, noise_scale, noise_scale_w,
+                                      dict(message=message, watermark_hold=watermark_hold, message_repeat=message_repeat))
 
     def _speak_stream_ids(self, id_sequences, speaker, src_se, tgt_se, speed, seed, tau, out_sr, chunk_frames,
-                          live_chunk_frames, generator, wavenet, noise_scale, noise_scale_w):
+                          live_chunk_frames, generator, wavenet, noise_scale, noise_scale_w, mark_kw):
         conv = self.converter
         chunks = self.tts.tts_stream_from_ids(id_sequences, self._speaker_id(speaker), speed=speed,
                                               noise_scale=noise_scale, noise_scale_w=noise_scale_w, seed=seed,
@@ -369,7 +375,7 @@ class VoiceCloner:
                               wavenet=wavenet)
         from . import noise as noise_mod
         h = pool.open(src_se, tgt_se, sr_in=None if self.tts_sr == msr else self.tts_sr, sr_out=out_sr,
-                      **noise_mod.kw(seed))
+                      **mark_kw, **noise_mod.kw(seed))
         for chunk in chunks:
             pool.push(h, chunk)
             o = pool.step().get(h)

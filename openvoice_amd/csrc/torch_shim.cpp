@@ -473,6 +473,7 @@ TORCH_LIBRARY(openvoice_amd, m) {
   bind_device<&ov_normal_philox_f32>(m, "normal_philox_f32");
   bind_device<&ov_wm_embed_windows_f32>(m, "wm_embed_windows_f32");
   bind_device<&ov_wm_detect_windows_f32>(m, "wm_detect_windows_f32");
+  bind_device<&ov_wm_embed_blocks_f32>(m, "wm_embed_blocks_f32");
   bind_device<&ov_stitch_window_cores_f32>(m, "stitch_window_cores_f32");
   bind_device<&ov_conv_post_tanh_f32>(m, "conv_post_tanh_f32");
   bind_device<&ov_conv_post_tanh_limited_f32>(m, "conv_post_tanh_limited_f32");

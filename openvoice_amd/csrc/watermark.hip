@@ -32,20 +32,25 @@ constexpr int64_t kMaxL = (int64_t)1 << 31;         // the Philox block i / 128 
 constexpr int64_t kMaxOff = (int64_t)1 << 61;
 constexpr uint32_t kPurposeWatermark = 3;           // noise.py: purposes 0 .. 2 are the Gaussian draws
 
-// Calls f(i, negative) for this thread's samples i = t + 256 k < L, k ascending; negative: c[i] = -1.  Chips are made in
-// registers, one Philox block = 128 signs: a 256-sample step k needs the blocks 2 k and 2 k + 1, threads 0 .. 127 the
-// first and 128 .. 255 the second, and a wave reads two of a block's four words.  Lane l of a wave therefore computes
-// the block of step kc + l, and the 64 steps kc .. kc + 63 each fetch their two words from that lane (v_readlane: the
-// step is wave-uniform).  Every lane runs every step; only the call of f is predicated.
-template <typename F> __device__ inline void for_chips(int64_t L, uint32_t k0, uint32_t k1, F f) {
+// Calls f(i, negative) for this thread's samples i = t + 256 k < L, k ascending; negative: c[base + i] = -1.  `base` is the
+// chip index of sample 0: 0 for a whole window, a multiple of 32 for a block inside one (so that sample i still belongs
+// to bit t % 32).  Chips are made in registers, one Philox block = 128 signs = four 32-sample groups.  In step k a wave
+// (threads 64 w .. 64 w + 63) needs the two groups G = base / 32 + 2 w + 8 k and G + 1: words G % 4 and (G + 1) % 4 of
+// the blocks G / 4 and (G + 1) / 4, which differ only when G % 4 == 3 (an odd base / 32; wave-uniform).  Lane l of a wave
+// therefore computes the block(s) of step kc + l, and the 64 steps kc .. kc + 63 each fetch their two words from that
+// lane (v_readlane: the step is wave-uniform).  Every lane runs every step; only the call of f is predicated.
+template <typename F> __device__ inline void for_chips(int64_t L, int64_t base, uint32_t k0, uint32_t k1, F f) {
   const int t = threadIdx.x, lane = t & 63;
   const int64_t steps = (L + kThreads - 1) / kThreads;
-  const uint32_t half = (uint32_t)(t >> 7);
-  const bool upper_words = (t & 64) != 0;            // wave-uniform: this wave reads words 2, 3 (else 0, 1)
+  const int64_t g0 = base / kBits + 2 * (t >> 6);    // this wave's first group in step 0
+  const int word0 = (int)(g0 & 3);                   // wave-uniform
   for (int64_t kc = 0; kc < steps; kc += 64) {
-    uint32_t r[4];
-    ovn::philox4x32_10((uint32_t)(2 * (kc + lane)) + half, 0u, 0u, kPurposeWatermark, k0, k1, r);
-    const int w_lo = (int)(upper_words ? r[2] : r[0]), w_hi = (int)(upper_words ? r[3] : r[1]);
+    uint32_t r[4], r2[4] = {0u, 0u, 0u, 0u};
+    const uint32_t block = (uint32_t)(g0 / 4 + 2 * (kc + lane));
+    ovn::philox4x32_10(block, 0u, 0u, kPurposeWatermark, k0, k1, r);
+    if (word0 == 3) ovn::philox4x32_10(block + 1u, 0u, 0u, kPurposeWatermark, k0, k1, r2);
+    const int w_lo = (int)(word0 == 0 ? r[0] : word0 == 1 ? r[1] : word0 == 2 ? r[2] : r[3]);
+    const int w_hi = (int)(word0 == 0 ? r[1] : word0 == 1 ? r[2] : word0 == 2 ? r[3] : r2[0]);
     const int n = (int)(steps - kc < 64 ? steps - kc : 64);
     for (int kk = 0; kk < n; ++kk) {
       const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane(w_lo, kk), hi = (uint32_t)__builtin_amdgcn_readlane(w_hi, kk);
@@ -63,11 +68,11 @@ struct Stats {
 };
 
 // Pass 1 and the fixed-order reduction.  sp / se: 256 floats of LDS each.
-__device__ inline Stats window_stats(const float* x, int64_t L, uint32_t k0, uint32_t k1, float strength,
+__device__ inline Stats window_stats(const float* x, int64_t L, int64_t base, uint32_t k0, uint32_t k1, float strength,
                                      float floor_level, float* sp, float* se) {
   const int t = threadIdx.x;
   float p = 0.f, e = 0.f;
-  for_chips(L, k0, k1, [&](int64_t i, bool negative) {
+  for_chips(L, base, k0, k1, [&](int64_t i, bool negative) {
     const float v = x[i];
     p += negative ? -v : v;
     e = __builtin_fmaf(v, v, e);
@@ -99,7 +104,7 @@ __global__ __launch_bounds__(kThreads) void wm_embed_kernel(const float* src, in
   const int64_t so = rec[0], d_o = rec[1], L = rec[2], bits = rec[3];
   if (L < kMinL || L > kMaxL || !span_ok(so, L, src_elems) || !span_ok(d_o, L, dst_elems)) return;     // (block-uniform)
   const float* x = src + so;            // (src and dst carry no __restrict__: a window may be marked in place)
-  const Stats st = window_stats(x, L, k0, k1, strength, floor_level, sp, se);
+  const Stats st = window_stats(x, L, 0, k0, k1, strength, floor_level, sp, se);
   const int t = threadIdx.x;
   if (t < kBits) {
     const float b = ((uint64_t)bits >> t) & 1u ? 1.f : -1.f;
@@ -108,7 +113,7 @@ __global__ __launch_bounds__(kThreads) void wm_embed_kernel(const float* src, in
   __syncthreads();
   const float d = sd[t & (kBits - 1)];
   float* y = dst + d_o;
-  for_chips(L, k0, k1, [&](int64_t i, bool negative) {
+  for_chips(L, 0, k0, k1, [&](int64_t i, bool negative) {
     const float v = x[i];
     y[i] = negative ? v - d : v + d;
   });
@@ -122,10 +127,62 @@ __global__ __launch_bounds__(kThreads) void wm_detect_kernel(const float* __rest
   const int64_t* rec = records + 4 * (int64_t)blockIdx.x;
   const int64_t so = rec[0], L = rec[2];
   if (L < kMinL || L > kMaxL || !span_ok(so, L, src_elems)) return;
-  const Stats st = window_stats(src + so, L, k0, k1, strength, floor_level, sp, se);
+  const Stats st = window_stats(src + so, L, 0, k0, k1, strength, floor_level, sp, se);
   const int t = threadIdx.x;
   if (t < kBits) q_out[(int64_t)blockIdx.x * kBits + t] = st.p;
   if (t == 0) level_out[blockIdx.x] = st.level;
+}
+
+// The block-wise form for streams (watermark.py, "streams"): a carrier window of 16 000 samples is cut into blocks of H
+// samples, and per window and bit one float R_j >= 0 -- the surplus of the blocks so far -- is carried in a state row:
+//   u_j = b_j p_j + R_j,   d_j = b_j max(a_m - u_j, 0),   R_j <- max(u_j - a_m, 0)       (p_j, a_m: of the block alone)
+// A record is one run of consecutive blocks of one window of one stream; its workgroup walks the blocks in order with
+// R_j in a register of thread j, reads the state row first unless `reset` and writes it last.  A block is reduced by
+// window_stats, so with H = 16 000 (R = 0, u = b p exactly) the samples are ov_wm_embed_windows_f32's bit for bit.
+constexpr int64_t kWindow = 16000;
+constexpr int kBlockFields = 8;                     // (src_off, dst_off, H, blocks, bits, chip_off, state_row, reset)
+
+__device__ inline bool hold_ok(int64_t H) {
+  return H == 16000 || H == 8000 || H == 4000 || H == 3200 || H == 1600 || H == 800 || H == 640;
+}
+
+__global__ __launch_bounds__(kThreads) void wm_embed_blocks_kernel(const float* src, int64_t src_elems, float* dst,
+                                                                   int64_t dst_elems, const int64_t* __restrict__ records,
+                                                                   float* state, int64_t state_rows, uint32_t k0,
+                                                                   uint32_t k1, float strength, float floor_level) {
+  __shared__ float sp[kThreads], se[kThreads], sd[kBits];
+  const int64_t* rec = records + kBlockFields * (int64_t)blockIdx.x;
+  const int64_t so = rec[0], d_o = rec[1], H = rec[2], blocks = rec[3], bits = rec[4], chip_off = rec[5], row = rec[6],
+                reset = rec[7];
+  // (block-uniform; hold_ok bounds H, so blocks * H cannot overflow once blocks <= 25)
+  if (!hold_ok(H) || blocks < 1 || blocks > kWindow / H || chip_off < 0 || chip_off % H != 0 ||
+      chip_off + blocks * H > kWindow || row < 0 || row >= state_rows || (reset != 0 && reset != 1) ||
+      !span_ok(so, blocks * H, src_elems) || !span_ok(d_o, blocks * H, dst_elems))
+    return;
+  const int t = threadIdx.x;
+  float* srow = state + row * kBits;
+  const float b = ((uint64_t)bits >> (t & (kBits - 1))) & 1u ? 1.f : -1.f;
+  float surplus = 0.f;                                // R_t, threads 0 .. 31
+  if (t < kBits && !reset) surplus = srow[t];
+  for (int64_t m = 0; m < blocks; ++m) {
+    const float* x = src + so + m * H;                // (no __restrict__: a block may be marked in place)
+    float* y = dst + d_o + m * H;
+    const int64_t base = chip_off + m * H;
+    const Stats st = window_stats(x, H, base, k0, k1, strength, floor_level, sp, se);
+    if (t < kBits) {
+      const float u = b * st.p + surplus;
+      sd[t] = b * fmaxf(st.level - u, 0.f);
+      surplus = fmaxf(u - st.level, 0.f);
+    }
+    __syncthreads();
+    const float d = sd[t & (kBits - 1)];
+    for_chips(H, base, k0, k1, [&](int64_t i, bool negative) {
+      const float v = x[i];
+      y[i] = negative ? v - d : v + d;
+    });
+    // (the next block's window_stats passes a barrier between this read of sd and the next write of it)
+  }
+  if (t < kBits) srow[t] = surplus;
 }
 
 bool launch_args_ok(const void* src, int64_t src_elems, const void* records, int W, int64_t key, float strength,
@@ -145,6 +202,20 @@ int ov_wm_embed_windows_f32(const float* src, int64_t src_elems, float* dst, int
   if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 3) return OV_E_ALIGN;
   hipLaunchKernelGGL(wm_embed_kernel, dim3((unsigned)W), dim3(kThreads), 0, static_cast<hipStream_t>(stream), src, src_elems,
                      dst, dst_elems, records, (uint32_t)key, (uint32_t)((uint64_t)key >> 32), strength, floor_level);
+  return hipGetLastError() == hipSuccess ? OV_OK : OV_E_LAUNCH;
+}
+
+int ov_wm_embed_blocks_f32(const float* src, int64_t src_elems, float* dst, int64_t dst_elems, const int64_t* records, int R,
+                           float* state, int64_t state_rows, int64_t key, float strength, float floor_level,
+                           ov_stream_t stream) {
+  if (!launch_args_ok(src, src_elems, records, R, key, strength, floor_level) || !dst || dst_elems <= 0 || !state ||
+      state_rows <= 0 || state_rows > kMaxOff / kBits)
+    return OV_E_BADARG;
+  if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(state)) & 3)
+    return OV_E_ALIGN;
+  hipLaunchKernelGGL(wm_embed_blocks_kernel, dim3((unsigned)R), dim3(kThreads), 0, static_cast<hipStream_t>(stream), src,
+                     src_elems, dst, dst_elems, records, state, state_rows, (uint32_t)key, (uint32_t)((uint64_t)key >> 32),
+                     strength, floor_level);
   return hipGetLastError() == hipSuccess ? OV_OK : OV_E_LAUNCH;
 }
 

@@ -45,6 +45,7 @@ import torch
 
 from . import _lib, rates
 from . import noise as noise_mod
+from . import watermark as watermark_mod
 from .engine import rows_tau
 from .generator import generator_stages, samples_per_frame
 from .longform import launch_ladder, stream_end_frames, winograd_grid_frames
@@ -613,8 +614,9 @@ class LivePool(UnitPool, PushedPool):
 
     def __init__(self, model, tau=0.3, chunk_frames=DEFAULT_CHUNK_FRAMES,
                  max_streams_per_launch=DEFAULT_LIVE_STREAMS_PER_LAUNCH, n_fft=1024, hop=256, model_sr=rates.MODEL_RATE,
-                 generator="fp32", wavenet=None, lookahead_frames=None, crossfade_samples=None):
+                 generator="fp32", wavenet=None, lookahead_frames=None, crossfade_samples=None, watermark_model=None):
         self.model, self.tau = model, float(tau)
+        self.watermark_model = watermark_model      # the converter's: what open(message=) marks with
         self.lookahead = check_lookahead(lookahead_frames)
         self._tau_rows = {}         # taus of a launch's rows -> their float32 device vector (uploaded once)
         self.n_fft, self.hop, self.pad = int(n_fft), int(hop), (int(n_fft) - int(hop)) // 2
@@ -622,11 +624,17 @@ class LivePool(UnitPool, PushedPool):
         check_generator(generator), _lib.check_wavenet(wavenet, optional=True), check_chunk(model.model_cfg, chunk_frames)
         super().__init__(model.engine(), model.model_cfg, live_units(model.model_cfg), chunk_frames,
                          max_streams_per_launch, generator=generator, wavenet=wavenet)
-        self.latency_samples = live_latency_samples(self.cfg, self.chunk, self.n_fft, self.hop, self.lookahead)
+        self._core_latency = live_latency_samples(self.cfg, self.chunk, self.n_fft, self.hop, self.lookahead)
         self.crossfade = check_crossfade(crossfade_samples, self.lookahead, self.chunk, self.hop)
         # look-ahead streams whose frontier stays inside the committed samples never run a preview
         self._pv = self._fade = self._fade_w = None               # preview slabs, seam buffer, fade-in weights (lazy)
         self._init_streams(self.device, model_sr)
+
+    @property
+    def latency_samples(self):
+        """The bound at the model rate: ``live_latency_samples``, plus ``H - 1`` samples of the longest hold among the
+        open streams that carry a message (``latency_of(h)`` is stream h's own)."""
+        return self._core_latency + self._hold_wait()
 
     def state_bytes_per_stream(self):
         """Device bytes one open stream adds: its arena slot (every unit's two state halves) and its conditioning rows
@@ -638,8 +646,14 @@ class LivePool(UnitPool, PushedPool):
         return 4 * (self.slot_elems + conds)
 
     # ---- streams --------------------------------------------------------------------------------------------------
-    def open(self, src_se, tgt_se, noise=None, sr_in=None, sr_out=None, *, seed=None, tau=None):
+    def open(self, src_se, tgt_se, noise=None, sr_in=None, sr_out=None, *, seed=None, tau=None, message=None,
+             watermark_hold=watermark_mod.DEFAULT_HOLD, message_repeat=False):
         """A new stream -> its handle.  ``tau``: None = the pool's, else this stream's own number, for life.
+        ``message`` (None: unmarked, today's path): the stream's output carries the block-wise native watermark of it
+        (``watermark.py``, "streams"), made at the model rate after the crossfade and before the output resampler, all
+        marked streams of a step in one launch; ``watermark_hold`` = H, one of ``watermark.HOLDS``: a sample leaves at
+        most H - 1 samples later; ``message_repeat``: window n carries group n % G for the stream's life instead of
+        the first G windows only.  ValueError for a message on a pool whose converter has no native watermark.
         ``sr_in`` / ``sr_out``: the rate of its pushes / of its output (None or the
         model rate: no resampler in that direction).  ``noise`` ``[1, inter, >= T]``, or ``seed`` (an int: stream
         ``(seed, 0)``, or a pair): counter-based noise (``noise.py``) generated chunk by chunk into the staging rows --
@@ -647,9 +661,10 @@ class LivePool(UnitPool, PushedPool):
         the pool, and holds no noise tensor; neither: drawn from torch's generator per chunk."""
         noise_mod.exclusive(seed, noise=noise)
         tau = self._stream_tau(tau, "LivePool.open")
+        mark = watermark_mod.stream_mark(self.watermark_model, message, watermark_hold, message_repeat)
         sr_in, sr_out = rates.check_rate(sr_in, "sr_in"), rates.check_rate(sr_out, "sr_out")
         st = _Live(self, src_se, tgt_se, noise, seed=seed)
-        st.tau = tau
+        st.tau, st.mark = tau, mark
         st.E = st.C = 0             # look-ahead: samples emitted / committed so far
         st.pend, st.pend_n = [], 0  # committed samples past the emitted ones, oldest first
         st.has_tail = False         # the last preview's samples [E, E + X) are kept in this stream's seam slot
@@ -660,7 +675,8 @@ class LivePool(UnitPool, PushedPool):
         """``(seconds, samples)``: the latency bound of stream h at its own rates (``rates.stream_latency``; samples in
         its output rate, ``latency_samples`` when it resamples nothing)."""
         st = self._stream(h)
-        return rates.stream_latency(self.latency_samples, self.model_sr, st.sr_in, st.sr_out)
+        return rates.stream_latency(self._core_latency, self.model_sr, st.sr_in, st.sr_out,
+                                    hold_samples=watermark_mod.hold_wait(st.mark))
 
     def close(self, h):
         """End of h's input; too short an input raises ValueError here and retires h (the others are untouched)."""
@@ -909,16 +925,19 @@ class LiveStream:
     """One live stream (a ``LivePool`` of one): ``push(samples)`` -> newly finished samples (device tensor, possibly
     empty), ``close()`` -> the rest, ``latency_samples`` the bound no output sample's delay exceeds (in output samples;
     ``latency_seconds`` the same bound in seconds).  ``sr_in`` / ``sr_out``: rates of the pushes / of the output (None:
-    the model rate).  ``generator``: as for ``LivePool``."""
+    the model rate).  ``generator``: as for ``LivePool``.  ``message`` / ``watermark_hold`` / ``message_repeat``: as for
+    ``LivePool.open``, marked with ``watermark_model``; the latency figures include the hold."""
 
     def __init__(self, model, src_se, tgt_se, tau=0.3, chunk_frames=DEFAULT_CHUNK_FRAMES, noise=None, n_fft=1024,
                  hop=256, sr_in=None, sr_out=None, model_sr=rates.MODEL_RATE, generator="fp32", seed=None, wavenet=None,
-                 lookahead_frames=None, crossfade_samples=None):
+                 lookahead_frames=None, crossfade_samples=None, watermark_model=None, message=None,
+                 watermark_hold=watermark_mod.DEFAULT_HOLD, message_repeat=False):
         noise_mod.exclusive(seed, noise=noise)
         self._pool = LivePool(model, tau=tau, chunk_frames=chunk_frames, max_streams_per_launch=1, n_fft=n_fft, hop=hop,
                               model_sr=model_sr, generator=generator, wavenet=wavenet, lookahead_frames=lookahead_frames,
-                              crossfade_samples=crossfade_samples)
-        self._h = self._pool.open(src_se, tgt_se, noise=noise, sr_in=sr_in, sr_out=sr_out, **noise_mod.kw(seed))
+                              crossfade_samples=crossfade_samples, watermark_model=watermark_model)
+        self._h = self._pool.open(src_se, tgt_se, noise=noise, sr_in=sr_in, sr_out=sr_out, message=message,
+                                  watermark_hold=watermark_hold, message_repeat=message_repeat, **noise_mod.kw(seed))
         self.latency_seconds, self.latency_samples = self._pool.latency_of(self._h)
         self._closed = False
 

@@ -27,6 +27,7 @@ from . import _lib, rates
 from .engine import item_tau, rows_tau, wavenet_keyword
 from . import noise as noise_mod
 from .streams import PushedPool, WaveBuffer
+from . import watermark as watermark_mod
 from .generator import GENERATOR_MARGIN, generator_margin_frames, generator_stages, samples_per_frame
 from .params import ENC_Q_KERNEL, ENC_Q_LAYERS, FLOW_KERNEL, FLOW_LAYERS, N_FLOWS
 
@@ -160,8 +161,10 @@ class WindowedConverter:
     captures at most three shapes: full batches, the last partial batch, and the single-window case)."""
 
     def __init__(self, model, n_fft=1024, hop=256, window_frames=DEFAULT_WINDOW_FRAMES,
-                 windows_per_launch=DEFAULT_WINDOWS_PER_LAUNCH, graph=False, model_sr=rates.MODEL_RATE, wavenet=None):
+                 windows_per_launch=DEFAULT_WINDOWS_PER_LAUNCH, graph=False, model_sr=rates.MODEL_RATE, wavenet=None,
+                 watermark_model=None):
         self.model = model
+        self.watermark_model = watermark_model      # the converter's: what a stream opened with message= marks with
         # the WaveNet layers' kernels of every launch of THIS converter (its streams and pools included): None follows
         # the engine's use_bf16_wavenet switch or the running call's wavenet=
         self.wavenet = _lib.check_wavenet(wavenet, optional=True)
@@ -354,9 +357,10 @@ class WindowedConverter:
                          **noise_mod.kw(rows))
         return out
 
-    def stream(self, src_se, tgt_se, tau=0.3, noise=None, sr_in=None, sr_out=None, *, seed=None):
-        return ConversionStream(self, src_se, tgt_se, tau=tau, noise=noise, sr_in=sr_in, sr_out=sr_out,
-                                **noise_mod.kw(seed))
+    def stream(self, src_se, tgt_se, tau=0.3, noise=None, sr_in=None, sr_out=None, *, seed=None, message=None,
+               watermark_hold=watermark_mod.DEFAULT_HOLD, message_repeat=False):
+        return ConversionStream(self, src_se, tgt_se, tau=tau, noise=noise, sr_in=sr_in, sr_out=sr_out, message=message,
+                                watermark_hold=watermark_hold, message_repeat=message_repeat, **noise_mod.kw(seed))
 
     def stream_pool(self, tau=0.3, max_windows_per_launch=DEFAULT_POOL_WINDOWS_PER_LAUNCH):
         return StreamPool(self, tau=tau, max_windows_per_launch=max_windows_per_launch)
@@ -368,17 +372,22 @@ class _StreamState:
     rule, the end-of-input plan, the noise, and the rates of the input / output (``sr_in`` / ``sr_out``, None: the
     model rate)."""
 
-    def __init__(self, conv, src_se, tgt_se, noise=None, sr_in=None, sr_out=None, seed=None):
+    def __init__(self, conv, src_se, tgt_se, noise=None, sr_in=None, sr_out=None, seed=None, message=None,
+                 watermark_hold=watermark_mod.DEFAULT_HOLD, message_repeat=False):
         noise_mod.exclusive(seed, noise=noise)
+        # message=: the block-wise native watermark of the output (watermark.py, "streams"); None: unmarked
+        self.mark = watermark_mod.stream_mark(conv.watermark_model, message, watermark_hold, message_repeat)
         self.conv, self.src_se, self.tgt_se = conv, src_se, tgt_se
         self._seed = None if seed is None else noise_mod.check_seed(seed)     # (seed, stream): frames made on demand
         self.dev = conv._device()
         c = conv
         self._Tw, self._core, self._ctx = c.window_frames, c.core, c.context
         self.sr_in, self.sr_out = rates.check_rate(sr_in, "sr_in"), rates.check_rate(sr_out, "sr_out")
-        # (Tw - 1) * hop + n_fft - pad at the model rate; the resamplers' waits on top (rates.stream_latency)
+        # (Tw - 1) * hop + n_fft - pad at the model rate; the resamplers' waits and a message's hold on top
+        # (rates.stream_latency)
         self.latency_seconds, self._latency = rates.stream_latency((self._Tw - 1) * c.hop + c.n_fft - c.pad, c.model_sr,
-                                                                   self.sr_in, self.sr_out)
+                                                                   self.sr_in, self.sr_out,
+                                                                   hold_samples=watermark_mod.hold_wait(self.mark))
         self.rin = self.rout = None
         self.wave = WaveBuffer(self.dev)
         self._k = 0                 # next regular window
@@ -469,11 +478,19 @@ class ConversionStream(_StreamState):
 
     ``sr_in`` / ``sr_out``: the rate of the pushes / of the output (None: the model rate).  Pushes then pass through a
     ``rates.StreamResampler`` to the model rate and the output through another one, one launch each per push;
-    ``latency_samples`` (in output samples) and ``latency_seconds`` include their waits (``rates.stream_latency``)."""
+    ``latency_samples`` (in output samples) and ``latency_seconds`` include their waits (``rates.stream_latency``).
 
-    def __init__(self, conv, src_se, tgt_se, tau=0.3, noise=None, sr_in=None, sr_out=None, seed=None):
-        super().__init__(conv, src_se, tgt_se, noise, sr_in=sr_in, sr_out=sr_out, seed=seed)
+    ``message`` (None: unmarked, today's path): the output carries the block-wise native watermark of it, made at the
+    model rate before the output resampler (``watermark.StreamMarker``, one launch per push with output);
+    ``watermark_hold`` = H: a sample leaves at most H - 1 samples later, which the latency figures include;
+    ``message_repeat``: window n carries group n % G for the stream's life."""
+
+    def __init__(self, conv, src_se, tgt_se, tau=0.3, noise=None, sr_in=None, sr_out=None, seed=None, message=None,
+                 watermark_hold=watermark_mod.DEFAULT_HOLD, message_repeat=False):
+        super().__init__(conv, src_se, tgt_se, noise, sr_in=sr_in, sr_out=sr_out, seed=seed, message=message,
+                         watermark_hold=watermark_hold, message_repeat=message_repeat)
         self.tau = tau
+        self._marker = None if self.mark is None else watermark_mod.StreamMarker(self.mark, self.dev)
         if self.sr_in is not None and self.sr_in != conv.model_sr:
             self.rin = rates.StreamResampler(self.sr_in, conv.model_sr, self.dev)
         if self.sr_out is not None and self.sr_out != conv.model_sr:
@@ -514,6 +531,8 @@ class ConversionStream(_StreamState):
             y = torch.empty(0, dtype=torch.float32, device=self.dev)
         else:
             y = outs[0] if len(outs) == 1 else torch.cat(outs)
+        if self._marker is not None:
+            y = self._marker.push(y)
         return y if self.rout is None else self.rout.push(y)
 
     @torch.no_grad()
@@ -526,6 +545,8 @@ class ConversionStream(_StreamState):
         outs = [self._run(rec, Tw) for rec, Tw in self._tail_plan()]
         self.wave.release()
         y = outs[0] if len(outs) == 1 else torch.cat(outs)
+        if self._marker is not None:
+            y = self._marker.close(y)
         return y if self.rout is None else self.rout.close(y)
 
 
@@ -569,14 +590,18 @@ class StreamPool(PushedPool):
     @property
     def latency_samples(self):
         """As ``ConversionStream.latency_samples``: ``(Tw - 1) * hop + n_fft - pad`` (plus the wait for the next
-        ``step()``)."""
+        ``step()``), plus ``H - 1`` samples of the longest hold among the open streams that carry a message."""
         c = self.conv
-        return (c.window_frames - 1) * c.hop + c.n_fft - c.pad
+        return (c.window_frames - 1) * c.hop + c.n_fft - c.pad + self._hold_wait()
 
-    def open(self, src_se, tgt_se, noise=None, sr_in=None, sr_out=None, *, seed=None, tau=None):
-        """A new stream -> its handle.  ``tau``: None = the pool's, else this stream's own number, for life."""
+    def open(self, src_se, tgt_se, noise=None, sr_in=None, sr_out=None, *, seed=None, tau=None, message=None,
+             watermark_hold=watermark_mod.DEFAULT_HOLD, message_repeat=False):
+        """A new stream -> its handle.  ``tau``: None = the pool's, else this stream's own number, for life.
+        ``message`` / ``watermark_hold`` / ``message_repeat``: as for ``ConversionStream``; the marked streams of a step
+        share one launch (``watermark.MarkBank``)."""
         tau = self._stream_tau(tau, "StreamPool.open")
-        st = _StreamState(self.conv, src_se, tgt_se, noise, sr_in=sr_in, sr_out=sr_out, seed=seed)
+        st = _StreamState(self.conv, src_se, tgt_se, noise, sr_in=sr_in, sr_out=sr_out, seed=seed, message=message,
+                          watermark_hold=watermark_hold, message_repeat=message_repeat)
         st.tau = tau
         return self._register(st, st.sr_in, st.sr_out)
 

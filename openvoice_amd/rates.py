@@ -62,12 +62,15 @@ def latency_seconds(sr_in, sr_out):
     return Fraction(pair(sr_in, sr_out)[2], int(sr_in))
 
 
-def stream_latency(core_samples, model_sr=MODEL_RATE, sr_in=None, sr_out=None):
+def stream_latency(core_samples, model_sr=MODEL_RATE, sr_in=None, sr_out=None, hold_samples=0):
     """``(seconds, samples)``: the latency bound of a stream whose conversion at the model rate waits at most
     ``core_samples`` and whose input / output are resampled from ``sr_in`` / to ``sr_out`` (None: the model rate).
-    ``seconds = taps_in / sr_in + (core_samples + taps_out) / model_sr`` (the output resampler waits ``taps_out`` model-rate
-    samples), ``samples = ceil(seconds * output rate)``: ``core_samples`` itself when neither rate is given."""
-    sec = latency_seconds(sr_in, model_sr) + Fraction(int(core_samples), int(model_sr))
+    ``hold_samples``: what a stream with a message waits on top at the model rate, ``watermark_hold - 1`` (a sample
+    leaves once its watermark block is whole; ``watermark.hold_wait``).
+    ``seconds = taps_in / sr_in + (core_samples + hold_samples + taps_out) / model_sr`` (the output resampler waits
+    ``taps_out`` model-rate samples), ``samples = ceil(seconds * output rate)``: ``core_samples + hold_samples`` itself
+    when neither rate is given."""
+    sec = latency_seconds(sr_in, model_sr) + Fraction(int(core_samples) + int(hold_samples), int(model_sr))
     if sr_out is not None and int(sr_out) != int(model_sr):
         sec += Fraction(pair(model_sr, sr_out)[2], int(model_sr))
     rate = int(model_sr) if sr_out is None else int(sr_out)

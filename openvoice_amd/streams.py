@@ -1,11 +1,13 @@
 """What ``longform.StreamPool`` and ``live.LivePool`` do to a pushed stream before and after their conversion launches:
 the growing waveform buffer (``WaveBuffer``) and the handle table with its per-stream resamplers (``PushedPool``).
 Nothing here knows of windows, units, rounds or noise.  A stream object brings ``wave`` (its ``WaveBuffer``), ``closed``
-and ``tau``; ``_register`` gives it ``sr_in`` / ``sr_out`` and its resampler keys ``rin`` / ``rout`` (None: the model
-rate)."""
+and ``tau``, and ``mark`` when it was opened with a message (``watermark.stream_mark``'s answer); ``_register`` gives it
+``sr_in`` / ``sr_out``, its resampler keys ``rin`` / ``rout`` (None: the model rate) and, with a ``mark``, its place in
+the pool's ``watermark.MarkBank``."""
 import torch
 
 from . import _lib, rates
+from . import watermark as watermark_mod
 from .engine import item_tau
 
 
@@ -54,6 +56,8 @@ class PushedPool:
         self._rin, self._rout = rates.ResamplerBank(device), rates.ResamplerBank(device)
         self._rin_owner = {}        # input resampler key -> stream
         self._rout_ending = []      # output resampler keys of streams that finished in this step
+        # streams opened with message=: their block-wise watermark (watermark.MarkBank), made on first use
+        self._mark, self._mark_keys, self._mark_ending = None, {}, []       # handle -> mark key; keys ending this step
 
     @property
     def active(self):
@@ -76,6 +80,7 @@ class PushedPool:
     def _register(self, st, sr_in, sr_out):
         """The last step of ``open``, after everything that can raise: ``st``'s resampler keys and its handle."""
         st.sr_in, st.sr_out, st.rin, st.rout = sr_in, sr_out, None, None
+        mark = getattr(st, "mark", None)        # watermark.stream_mark's answer, checked by open() before this
         if sr_in is not None and sr_in != self.model_sr:
             st.rin = self._rin.open(sr_in, self.model_sr)
             self._rin_owner[st.rin] = st
@@ -84,7 +89,15 @@ class PushedPool:
         h = self._next
         self._next += 1
         self._streams[h] = st
+        if mark is not None:
+            if self._mark is None:
+                self._mark = watermark_mod.MarkBank(self._rin.device)
+            self._mark_keys[h] = self._mark.open(mark)
         return h
+
+    def _hold_wait(self):
+        """The longest wait a message adds to a stream open in this pool, in model-rate samples (``H - 1``)."""
+        return max((watermark_mod.hold_wait(getattr(st, "mark", None)) for st in self._streams.values()), default=0)
 
     @torch.no_grad()
     def push(self, h, samples):
@@ -121,6 +134,11 @@ class PushedPool:
                 self._rout_ending.append(st.rout)     # ended after this step's last output is queued
             else:
                 self._rout.drop(st.rout)
+        if h in self._mark_keys:
+            if finished:
+                self._mark_ending.append(self._mark_keys[h])      # flushed by this step's _deliver
+            else:
+                self._mark.drop(self._mark_keys.pop(h))
         self._released(st)
 
     def _released(self, st):
@@ -136,7 +154,20 @@ class PushedPool:
         return {h: st.rout for h, st in self._streams.items() if st.rout is not None}
 
     def _deliver(self, outs, routs):
-        """Last in a ``step()``: ``outs`` with the output of the streams in ``routs`` at their own rates (one launch)."""
+        """Last in a ``step()``: ``outs`` with the output of the streams that carry a message marked (one launch, at
+        the model rate; a sample leaves once its block is whole, a finished stream's rest at once), then with the output
+        of the streams in ``routs`` at their own rates (one launch).  A pool without a marked stream runs no mark code."""
+        if self._mark_keys:
+            for h, key in self._mark_keys.items():
+                if h in outs:
+                    self._mark.push(key, outs.pop(h))
+            for key in self._mark_ending:
+                self._mark.end(key)
+            ys = self._mark.step()
+            outs.update({h: ys[key] for h, key in self._mark_keys.items() if key in ys})
+            if self._mark_ending:
+                self._mark_keys = {h: k for h, k in self._mark_keys.items() if k not in self._mark_ending}
+                self._mark_ending = []
         if routs:
             for h, key in routs.items():
                 if h in outs:

@@ -30,6 +30,35 @@ returns arbitrary characters), and robustness to resampling, MP3 coding or a tim
 ``ov_wm_detect_windows_f32``, record-driven, one workgroup per window, ONE launch for all windows); ``encode_host`` /
 ``decode_host`` restate the definition in float64 numpy (the pattern of ``noise.normal_host``): it is what tools and the
 CPU tests use.  There is no CPU fallback.
+
+Streams (``stream``, ``live_stream``, the pools, ``VoiceCloner.speak_stream*`` with ``message=``) carry a block-wise form
+of the same mark, because a window's ``d_j`` needs the whole window and a live stream cannot wait 0.73 s for it.  The
+carrier windows stay the hook's: window ``n`` is the stream's model-rate output samples ``[32 000 n, 32 000 n + 16 000)``
+and carries one 32-bit group; chips and bit ownership are those above, ``i`` counted from the window's start.  A window
+is cut into ``M = 16 000 / H`` blocks of ``H`` samples, ``H`` (the hold) one of ``HOLDS`` -- the divisors of 16 000 that
+are multiples of 32 and at least ``MIN_WINDOW`` -- so every bit owns exactly ``H / 32`` samples of every block.  Per
+window and bit the stream carries one float ``R_j >= 0``, the surplus of the blocks so far in projection units, zero at
+the window's start.  For block ``m`` with samples ``x``::
+
+    p_j = mean_{i in block, i % 32 == j} c[i] x[i]
+    a_m = max(strength * sqrt(mean_block x^2), floor)
+    u_j = b_j p_j + R_j
+    d_j = b_j max(a_m - u_j, 0)
+    y[i] = x[i] + d_{i % 32} c[i]
+    R_j <- max(u_j - a_m, 0)
+
+Block ``m`` moves ``b_j p_j`` of the block to ``b_j p_j + max(a_m - u_j, 0)``, and ``R`` after it is the sum of those
+values over the blocks so far minus the sum of their ``a_m``, never below zero: by induction ``sum_m b_j p_j(y_m) >=
+sum_m a_m``, and a window's projection is the mean of its blocks', so ``b_j p_j(y) >= mean_m a_m >= floor`` for the
+whole window and the unchanged reader returns every bit -- exact by construction, like the file mark.  A block the host
+audio (or an earlier block's surplus) already carries is left alone.  With ``H = 16 000`` there is one block, ``R = 0``
+and ``u = b p`` exactly: the formulas and, on the device, the bits are the file's (``ov_wm_embed_blocks_f32`` reduces a
+block in the order ``ov_wm_embed_windows_f32`` reduces a window).  The block grid is fixed to the stream's sample index,
+not to pushes, so the marked stream is a pure function of the unmarked samples, message, key, strength, floor and ``H``:
+it does not depend on chunking, on the pool or on the launch.  A sample leaves once its block is complete, at most
+``H - 1`` samples later than without a message; samples outside carrier windows pass through in order, behind a held
+block; at the end of the stream the samples of an unfinished block leave unmarked.  ``plan_blocks`` is the schedule,
+``mark_stream_host`` the float64 mirror of a whole stream, ``MarkBank`` the device side for many streams in one launch.
 """
 import numpy as np
 
@@ -46,6 +75,10 @@ DEFAULT_FLOOR = 2.0 ** -12
 # the carrier windows of the converter's hook (ToneColorConverter.WATERMARK_*): group n in the 16 000 samples from 32 000 n
 WINDOW = 16000
 STRIDE = 2 * WINDOW
+# the holds of a marked stream: the divisors of WINDOW that are multiples of BITS and at least MIN_WINDOW
+HOLDS = tuple(h for h in range(WINDOW, MIN_WINDOW - 1, -1) if WINDOW % h == 0 and h % BITS == 0)
+DEFAULT_HOLD = WINDOW
+BLOCK_RECORD_FIELDS = 8     # (src_off, dst_off, H, blocks, bits, chip_off, state_row, reset)
 
 
 def _is_int(v):
@@ -94,7 +127,12 @@ def read_host(carrier, key=0, strength=DEFAULT_STRENGTH, floor=DEFAULT_FLOOR):
     key, strength, floor = check_params(key, strength, floor)
     x = np.atleast_2d(np.asarray(carrier, dtype=np.float64))
     _check_window(x.shape[1])
-    cx = x * chips_host(key, x.shape[1])[None, :]
+    return _read(x, chips_host(key, x.shape[1]), strength, floor)
+
+
+def _read(x, chips, strength, floor):
+    """``read_host`` of rows ``x [B, L]`` with their chips given (a stream's block takes them from inside a window)."""
+    cx = x * chips[None, :]
     q = np.stack([cx[:, j::BITS].mean(axis=1) for j in range(BITS)], axis=1)
     a = np.maximum(strength * np.sqrt(np.mean(x * x, axis=1)), floor)
     return q, a
@@ -116,6 +154,89 @@ def decode_host(carrier, key=0, strength=DEFAULT_STRENGTH, floor=DEFAULT_FLOOR):
     """Scores ``[B, 32]`` in float64: ``0.5 + 0.5 tanh(q / a)``."""
     q, a = read_host(carrier, key, strength, floor)
     return 0.5 + 0.5 * np.tanh(q / a[:, None])
+
+
+# ---- streams: the schedule and the float64 mirror ---------------------------------------------------------------------
+def check_hold(hold):
+    """``hold`` as an int of ``HOLDS``; ValueError otherwise."""
+    if not _is_int(hold) or int(hold) not in HOLDS:
+        raise ValueError(f"watermark_hold must be one of {HOLDS}, got {hold!r}")
+    return int(hold)
+
+
+def groups_of(message):
+    """The payload words of ``message`` (padded / cut to 8 latin-1 characters): one per 32-bit group, in order."""
+    from .api import string_to_bits
+    payload = string_to_bits(message).reshape(-1)
+    return [pack_bits(payload[i:i + BITS]) for i in range(0, len(payload) - BITS + 1, BITS)]
+
+
+def _group_of(n, groups, repeat):
+    """The message group window ``n`` carries, or None: ``n`` itself below ``groups``, ``n % groups`` with ``repeat``."""
+    if groups < 1 or (n >= groups and not repeat):
+        return None
+    return n % groups
+
+
+def plan_blocks(pos, n_new, closing, H, groups, repeat):
+    """The schedule of a marked stream, a pure function.  ``pos``: the stream's samples that have left; ``n_new``: the
+    samples at hand from ``pos`` on (the held ones, then the new ones); ``closing``: they are the stream's last;
+    ``groups``: the message's group count; ``repeat``: ``message_repeat``.  Returns ``(n_out, records)``: the first
+    ``n_out`` of the samples at hand leave now -- all of them, except the samples of an unfinished block of a carrier
+    window (which leave too, unmarked, when ``closing``) -- and ``records`` = ``[(off, blocks, window, group, chip_off,
+    reset)]``: the run of ``blocks`` whole blocks that starts ``off`` samples after ``pos`` belongs to carrier window
+    ``window``, carries message group ``group``, begins ``chip_off`` samples after the window's start, and starts the
+    window's state afresh (``reset``) or continues it.  At most one record per window.  ``pos`` is where an earlier call
+    left it: outside the carrier windows, or on a block boundary."""
+    pos, n_new, H = int(pos), int(n_new), check_hold(H)
+    if pos < 0 or n_new < 0:
+        raise ValueError(f"plan_blocks: pos {pos}, n_new {n_new}")
+    end, records, n_out = pos + n_new, [], n_new
+    n = pos // STRIDE
+    while n * STRIDE < end:
+        group = _group_of(n, groups, repeat)
+        if group is None:
+            if not repeat:
+                break                                    # no later window carries anything
+            n += 1
+            continue
+        w0 = n * STRIDE
+        lo, hi = max(pos, w0), min(end, w0 + WINDOW)
+        if lo < w0 + WINDOW:
+            if (lo - w0) % H:
+                raise ValueError(f"plan_blocks: pos {pos} lies inside a block of window {n}")
+            m0, m1 = (lo - w0) // H, (hi - w0) // H
+            if m1 > m0:
+                records.append((lo - pos, m1 - m0, n, group, m0 * H, m0 == 0))
+            if hi < w0 + WINDOW and not closing:         # the stream ends inside this window, for now
+                n_out = w0 + m1 * H - pos
+        n += 1
+    return n_out, records
+
+
+def mark_stream_host(x, message, key=0, strength=DEFAULT_STRENGTH, floor=DEFAULT_FLOOR, hold=DEFAULT_HOLD, repeat=False):
+    """The float64 mirror of a whole marked stream: ``x`` (1-D, the stream's unmarked model-rate output from its start
+    to its end) -> the samples the stream emits with ``message=message, watermark_hold=hold, message_repeat=repeat``.
+    Every whole block of a carrier window inside ``x`` is marked, the samples of an unfinished block are not."""
+    key, strength, floor = check_params(key, strength, floor)
+    H, words = check_hold(hold), groups_of(message)
+    y = np.array(x, dtype=np.float64).reshape(-1)
+    c = chips_host(key, WINDOW)
+    _, records = plan_blocks(0, y.size, True, H, len(words), repeat)
+    for off, blocks, _, group, chip_off, reset in records:
+        assert reset and chip_off == 0                   # one call: every window from its start
+        b = np.array([1.0 if (words[group] >> j) & 1 else -1.0 for j in range(BITS)])
+        R = np.zeros(BITS)
+        for m in range(blocks):
+            blk = y[off + m * H:off + (m + 1) * H]       # a view: marked in place
+            cm = c[m * H:(m + 1) * H]
+            p, a = _read(blk[None, :], cm, strength, floor)          # as read_host adds a window
+            p, a = p[0], a[0]
+            u = b * p + R
+            d = b * np.maximum(a - u, 0.0)
+            R = np.maximum(u - a, 0.0)
+            blk += np.tile(d, H // BITS) * cm
+    return y
 
 
 # ---- the device side ------------------------------------------------------------------------------------------------
@@ -172,6 +293,185 @@ def detect_windows(src, records, key=0, strength=DEFAULT_STRENGTH, floor=DEFAULT
         _lib.call("ov_wm_detect_windows_f32", src, src.numel(), recs, len(part), key, strength, floor, q[i:i + len(part)],
                   level[i:i + len(part)])
     return q, level
+
+
+def embed_blocks(src, dst, records, state, key=0, strength=DEFAULT_STRENGTH, floor=DEFAULT_FLOOR):
+    """``ov_wm_embed_blocks_f32`` on host rows ``(src_off, dst_off, H, blocks, bits, chip_off, state_row, reset)``
+    (``state``: float32 ``[rows, 32]`` on the device), uploaded in one copy, ONE launch (per 65535 records).  The rows go
+    to the kernel as they are: it checks every one and a bad one writes nothing."""
+    import torch
+    key, strength, floor = check_params(key, strength, floor)
+    _check_buffer(src, "src")
+    _check_buffer(dst, "dst")
+    _check_buffer(state, "state")
+    if state.dim() != 2 or state.shape[1] != BITS:
+        raise ValueError(f"state must be [rows, {BITS}]")
+    table = [tuple(int(v) for v in rec) for rec in records]
+    if any(len(rec) != BLOCK_RECORD_FIELDS for rec in table):
+        raise ValueError("a block record is (src_off, dst_off, H, blocks, bits, chip_off, state_row, reset)")
+    for i in range(0, len(table), MAX_RECORDS):
+        part = table[i:i + MAX_RECORDS]
+        recs = torch.tensor(part, dtype=torch.int64).to(src.device)
+        _lib.call("ov_wm_embed_blocks_f32", src, src.numel(), dst, dst.numel(), recs, len(part), state, state.shape[0], key,
+                  strength, floor)
+
+
+def stream_mark(model, message, hold=DEFAULT_HOLD, repeat=False):
+    """The ``message=`` / ``watermark_hold=`` / ``message_repeat=`` keywords of the stream entry points, checked at the
+    call: None without a message, else ``(model, payload words, H, repeat)``.  ValueError for a hold outside ``HOLDS``
+    and for a message on a converter whose ``watermark_model`` is not a ``NativeWatermark``."""
+    H = check_hold(hold)
+    if message is None:
+        return None
+    if not isinstance(message, str):
+        raise ValueError(f"message must be a string or None, got {message!r}")
+    if not isinstance(model, NativeWatermark):
+        raise ValueError('message= on a stream needs the native watermark: ToneColorConverter(..., watermark="native")')
+    return model, groups_of(message), H, bool(repeat)
+
+
+def hold_wait(mark):
+    """Samples a marked stream's output waits at most behind the unmarked one: ``H - 1`` (0 without a mark)."""
+    return 0 if mark is None else mark[2] - 1
+
+
+class _Marked:
+    def __init__(self, mark, slot, dev):
+        import torch
+        self.model, self.words, self.H, self.repeat = mark
+        self.slot = slot                # state rows 2 slot and 2 slot + 1
+        self.pos = 0                    # samples that have left
+        self.held = torch.empty(0, dtype=torch.float32, device=dev)      # samples [pos, ..) of an unfinished block
+        self.pending, self.ending = [], False
+        self.cur = 0                    # the state row of the window left open
+        self.whole = set()              # message groups that got a whole carrier window
+
+
+class MarkBank:
+    """The block-wise marks of many streams, stepped together (module docstring, "streams"); the interface of
+    ``rates.ResamplerBank``.  ``open(mark)`` (``mark``: what ``stream_mark`` returned) -> key; ``push(key, x)`` queues
+    this round's model-rate output of a stream; ``end(key)`` marks the end of it; ``step()`` -> ``{key: the samples that
+    may leave}`` (views of one packed tensor) after ONE launch of ``ov_wm_embed_blocks_f32`` per model in use for every
+    whole block at hand.  Per stream the bank holds the position, the held samples of an unfinished block (fewer than
+    ``H``) and two state rows.  A piece that spans several windows has a record per window, and no two records of a
+    launch share a row: the window a piece continues keeps the stream's current row, a window it leaves open takes the
+    other one (which becomes the current one), and a window that begins and ends inside the piece, whose row nobody
+    reads again, takes a scratch row of the launch.  An ended key leaves the bank with its ``step()``, which prints the
+    upstream notice if some group of its message never got a whole window."""
+
+    def __init__(self, device):
+        import torch
+        self.device = torch.device(device)
+        self._ms, self._next = {}, 0
+        self._free, self._slots, self._state = [], 0, None
+        self.launches = 0
+
+    def __contains__(self, key):
+        return key in self._ms
+
+    def __len__(self):
+        return len(self._ms)
+
+    def open(self, mark):
+        import torch
+        if not self._free:
+            grown = max(1, 2 * self._slots)
+            state = torch.zeros(2 * grown, BITS, dtype=torch.float32, device=self.device)
+            if self._state is not None:
+                state[:2 * self._slots].copy_(self._state[:2 * self._slots])
+            self._free, self._slots, self._state = list(range(grown - 1, self._slots - 1, -1)), grown, state
+        k = self._next
+        self._next += 1
+        self._ms[k] = _Marked(mark, self._free.pop(), self.device)
+        return k
+
+    def push(self, key, x):
+        m = self._ms[key]
+        if m.ending:
+            raise RuntimeError("push() after end()")
+        if x.numel():
+            m.pending.append(x.reshape(-1))
+
+    def end(self, key):
+        self._ms[key].ending = True
+
+    def drop(self, key):
+        m = self._ms.pop(key, None)
+        if m is not None:
+            self._free.append(m.slot)
+
+    def step(self):
+        import torch
+        work = [(k, m) for k, m in self._ms.items() if m.pending or m.ending]
+        if not work:
+            return {}
+        pieces, spans, recs, acc, n_scratch = [], [], {}, 0, 0
+        for k, m in work:
+            pieces += [m.held] + m.pending
+            n = m.held.numel() + sum(p.numel() for p in m.pending)
+            n_out, plan = plan_blocks(m.pos, n, m.ending, m.H, len(m.words), m.repeat)
+            for off, blocks, window, group, chip_off, reset in plan:
+                whole = chip_off + blocks * m.H == WINDOW
+                if not reset:                            # continues the window the last step left open
+                    row = 2 * m.slot + m.cur
+                elif whole:                              # begins and ends here: nobody reads its row again
+                    row, n_scratch = ("scratch", n_scratch), n_scratch + 1
+                else:                                    # left open: the stream's other row becomes its current one
+                    m.cur ^= 1
+                    row = 2 * m.slot + m.cur
+                recs.setdefault(m.model, []).append([acc + off, acc + off, m.H, blocks, m.words[group], chip_off, row,
+                                                     int(reset)])
+                if whole:
+                    m.whole.add(group)
+            spans.append((k, m, acc, n_out, n))
+            m.pos, m.pending = m.pos + n_out, []
+            acc += n
+        pieces = [p for p in pieces if p.numel()]
+        # always a fresh tensor: marked in place, and the held samples below are views of it
+        arena = torch.cat(pieces) if pieces else torch.empty(0, dtype=torch.float32, device=self.device)
+        rows = 2 * self._slots
+        if self._state.shape[0] < rows + n_scratch:       # the streams' rows first, this launch's scratch rows behind
+            grown = torch.zeros(rows + 2 * n_scratch, BITS, dtype=torch.float32, device=self.device)
+            grown[:rows].copy_(self._state[:rows])
+            self._state = grown
+        for model, table in recs.items():
+            for rec in table:
+                if type(rec[6]) is tuple:
+                    rec[6] = rows + rec[6][1]
+            embed_blocks(arena, arena, table, self._state, model.key, model.strength, model.floor)
+            n_launch = (len(table) + MAX_RECORDS - 1) // MAX_RECORDS
+            self.launches += n_launch
+            model.launches += n_launch
+        res = {}
+        for k, m, a, n_out, n in spans:
+            if n_out:
+                res[k] = arena[a:a + n_out]
+            m.held = arena[a + n_out:a + n]
+            if m.ending:
+                if len(m.whole) < len(m.words):
+                    print("Audio too short, fail to add watermark")
+                self.drop(k)
+        return res
+
+
+class StreamMarker:
+    """One stream's mark (a bank of one): ``push(x)`` -> the samples that may leave, ``close(x=None)`` -> the rest."""
+
+    def __init__(self, mark, device):
+        import torch
+        self.bank = MarkBank(device)
+        self.key = self.bank.open(mark)
+        self._none = torch.empty(0, dtype=torch.float32, device=self.bank.device)
+
+    def push(self, x):
+        self.bank.push(self.key, x)
+        return self.bank.step().get(self.key, self._none)
+
+    def close(self, x=None):
+        if x is not None:
+            self.bank.push(self.key, x)
+        self.bank.end(self.key)
+        return self.bank.step().get(self.key, self._none)
 
 
 class NativeWatermark:
@@ -244,9 +544,7 @@ class NativeWatermark:
     @staticmethod
     def groups_of(message):
         """The payload words of ``message`` (padded / cut to 8 latin-1 characters): one per 32-bit group, in order."""
-        from .api import string_to_bits
-        payload = string_to_bits(message).reshape(-1)
-        return [pack_bits(payload[i:i + BITS]) for i in range(0, len(payload) - BITS + 1, BITS)]
+        return groups_of(message)
 
     def mark_many(self, waves, messages):
         """Mark, in place and in ONE launch, every carrier window of every waveform of ``waves`` (1-D float32 device
