@@ -302,6 +302,33 @@ int ov_wn_layer_bf16_tile(int B, int T, int width);
 int ov_frame_hops_f32(const float* wave, float* hops, int B, int N, int hop, int pad, int U, int ld,
                       ov_stream_t stream);
 
+/* General linear-magnitude STFT, the reference's spectrogram_torch (openvoice/mel_processing.py:40-75) at any supported
+ * shape -- ov_frame_hops_f32 + the framing conv cover n_fft == 4 * hop only:
+ *   out[b][f][t] = sqrt(re^2 + im^2 + 1e-6),  (re, im)[f][t] = sum_n hann_pad[n] (cos, -sin)(2 pi f n / n_fft) ypad[t * hop + n]
+ * for f <= n_fft / 2 and t < T = (Np - n_fft) / hop + 1.  ypad (Np samples) is y [B][N] reflect-padded by
+ * (n_fft - hop) / 2 (:54-58) and, when `center`, that result reflect-padded AGAIN by n_fft / 2 (torch.stft at :61-72): two
+ * reflections in sequence, indexed in place.  hann_pad is the periodic Hann window of `win` samples with (n_fft - win) / 2
+ * zeros to its left, as torch.stft pads it; it reaches the kernel only through `wpack`, which the host builds in float64
+ * and rounds once to fp32 (openvoice_amd/mel_processing.py stft_weights): float4 record ((bt * 2 + c) * G + g), lane l,
+ * element u = W_c[32 bt + (l & 31)][8 g + 2 u + (l >> 5)], c = 0 re / 1 im, G = ceil(n_fft / 8), zeros beyond bins and n_fft;
+ * 16-byte aligned.  out is [B][n_fft / 2 + 1][ld] with ld == T rounded up to 4; columns [T, ld) are written as 0.
+ * Supported: 16 <= n_fft <= 2048 and even, 1 <= hop <= n_fft, 1 <= win <= n_fft (else OV_E_UNSUPPORTED); N larger than
+ * each pad it reflects, N <= 2^30, B <= 65535 (else OV_E_BADARG).  Nothing is launched when a check fails.  (Added within
+ * 2.12: an additive symbol.) */
+int ov_stft_mag_f32(const float* y, const float* wpack, float* out, int B, int N, int n_fft, int hop, int win, int center,
+                    int ld, ov_stream_t stream);
+/* Frames one workgroup of ov_stft_mag_f32 and ov_mel_log_f32 owns (tests size their shapes by it). */
+int ov_stft_tile_frames(void);
+/* Mel projection with dynamic-range compression, the reference's spec_to_mel_torch (openvoice/mel_processing.py:122-133:
+ * torch.matmul(mel_basis, spec) at :131, spectral_normalize_torch at :132 = log(clamp(x, min = 1e-5)), :8-14), and with
+ * ov_stft_mag_f32 in front of it mel_spectrogram_torch (:136-183):
+ *   out[b][m][t] = logf(max(sum_f mel[m][f] * spec[b][f][t], clip))
+ * spec rows are spec_ld >= T apart and items spec_bstride apart; mel is DEVICE [num_mels][bins] fp32; out is
+ * [B][num_mels][out_ld] with out_ld == T rounded up to 4, columns [T, out_ld) written as 0.  num_mels <= 256 and
+ * bins <= 1025 (else OV_E_UNSUPPORTED); clip > 0.  (Added within 2.12: an additive symbol.) */
+int ov_mel_log_f32(const float* spec, const float* mel, float* out, int B, int num_mels, int bins, int T, int spec_ld,
+                   int64_t spec_bstride, int out_ld, float clip, ov_stream_t stream);
+
 /* Windowed framing for long recordings (openvoice_amd/longform.py), replacing for each window the reflect pad + framing of
  * the reference's one-pass spectrogram_torch (openvoice/mel_processing.py:54-72, called at openvoice/api.py:145):
  *   hops[w][c][u] = ypad[hop * (first_frame[w] + u) + c],  u < U,
@@ -975,7 +1002,8 @@ int ov_conv1d_wino_pack_f32(const float* w, int Cout, int Cin, int K, float* dst
  * workgroup; ov_conv1d_wino_chunk(11, 32) = 2 where 2.07 returned 0).  2.09: ov_conv1d_wino_params.out_slope (the field that
  * was `reserved0`: same size and offset, 0 = none).  2.10: ov_frame_hops_windows_f32, ov_stitch_window_cores_f32.  2.11: ov_frame_hops_multi_f32.  2.12: ov_carry_rows_f32 (and, added later within 2.12 without a version change, ov_polyphase_fir_rows_f32 and ov_vad_frame_energy_f32, ov_vad_segments_i32, ov_vad_compact_f32, ov_rows_f32_to_cl_bf16, ov_cl_bf16_to_rows_f32: additive symbols, which the Python binding looks up by name when it loads the library; likewise ov_wn_layer_wino_f32, ov_wn_layer_wino_tile, ov_wn_wino_pack_size and ov_wn_wino_pack_f32, and ov_join_segments_f32, and ov_pack_groups_cl_bf16 and ov_unpack_groups_f32, and ov_wn_layer_bf16, ov_wn_layer_bf16_supported,
  * ov_wn_layer_bf16_tile, ov_wn_bf16_pack_size and ov_wn_bf16_pack, and ov_wm_embed_windows_f32 and
- * ov_wm_detect_windows_f32, and ov_wm_embed_blocks_f32; and ov_conv1d_params.scale_b, one pointer appended
+ * ov_wm_detect_windows_f32, and ov_wm_embed_blocks_f32, and ov_stft_mag_f32,
+ * ov_stft_tile_frames and ov_mel_log_f32; and ov_conv1d_params.scale_b, one pointer appended
  * to the struct and read only under OV_F_SCALE_B, a flag no older caller sets: the version stays 212 and a caller built
  * against the shorter struct stays binary compatible).  The Python binding
  * refuses a library older than the entry points it calls (openvoice_amd/_lib.py MIN_VERSION). */
