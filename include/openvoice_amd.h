@@ -562,6 +562,41 @@ int ov_wm_detect_windows_f32(const float* src, int64_t src_elems, const int64_t*
 int ov_wm_embed_blocks_f32(const float* src, int64_t src_elems, float* dst, int64_t dst_elems, const int64_t* records,
                            int R, float* state, int64_t state_rows, int64_t key, float strength, float floor_level,
                            ov_stream_t stream);
+/* The same reader at EVERY offset of a waveform, for audio whose start was cut, shifted or is unknown
+ * (openvoice_amd/watermark.py, "the scan").  records is a DEVICE int64 [R][3] of (src_off, n, out_off): for every
+ * s in [0, n - 16 000] of the waveform src[src_off .. src_off + n), with p_j(s) and a(s) the projections and the level
+ * of the window x[s .. s + 16 000) as defined above, at index out_off + s
+ *   words[.] = the 32 bits (bit j set iff p_j(s) >= 0),   pmin[.] = min_j |p_j(s)|,   level[.] = a(s)
+ * and, when p_out is not NULL (a [out_elems][32] array: tests and soft decisions), p_out[.][j] = p_j(s).  The
+ * projections run on the fp32 matrix pipe: with C[m][j] = c[32 m + j] (500 x 32) and t = s + j,
+ *   Q[t][j] = sum_{m < 500} x[t + 32 m] C[m][j],   p_j(s) = Q[s + j][j] / 500
+ * 32 consecutive t at a time, the chips made from their Philox words on the device.  The energy is sum_j W[s + j] with
+ * W[t] = sum_m x[t + 32 m]^2.  Every sum runs in an order that does not depend on s, on the tile or on the record:
+ * what offset s gets is a function of its 16 000 samples, key, strength and floor_level alone.  One launch serves every
+ * record: ov_wm_scan_tile() = 896 offsets per 256-thread workgroup, a grid of ceil((max_n - 15 999) / 896) x R with
+ * max_n the largest n of the call.  The output ranges of the records must not overlap.  Host checks (OV_E_BADARG): null
+ * pointers (p_out excepted), extents <= 0, R outside [1, 65535], max_n outside [16 000, 2^31], key < 0, strength outside
+ * [0, 1], floor_level outside (0, 1]; pointers 4-byte aligned, records 8-byte (OV_E_ALIGN).  The kernel checks every
+ * record: one with n < 16 000 or n > max_n, a negative offset, a waveform that leaves [0, src_elems) or an output range
+ * that leaves [0, out_elems) writes nothing.  Additive to ABI 2.12: found by name. */
+int ov_wm_scan_f32(const float* src, int64_t src_elems, const int64_t* records, int R, int64_t max_n, int64_t key,
+                   float strength, float floor_level, int32_t* words, float* pmin, float* level, float* p_out,
+                   int64_t out_elems, ov_stream_t stream);
+/* Offsets one workgroup of ov_wm_scan_f32 owns (tests size their shapes by it). */
+int ov_wm_scan_tile(void);
+/* The hits of a scan, one 256-thread workgroup per record, in ascending offset.  records is a DEVICE int64 [R][2] of
+ * (scan_off, S): offsets s in [0, S) at index scan_off + s of words / pmin / level (scan_elems elements each).  With
+ * G > 0 (groups: DEVICE int32 [G], G <= 8) offset s is a hit when e = min_k popcount(words[s] ^ groups[k]) <=
+ * max_errors (k the lowest such); with G == 0 when pmin[s] >= margin * level[s] (fp32 product), k = -1, e = 0.  The
+ * first `cap` hits of record i are the rows hits[i * cap + .] = (s, words[s], k, e) (DEVICE int32 [R * cap][4]; cap = 0:
+ * count only, hits may be NULL), counts[i] is the number of hits whether they fitted or not.  The compaction is ordered
+ * (ballot, popcount, a running base): the list does not depend on the launch.  Host checks (OV_E_BADARG): null pointers,
+ * scan_elems <= 0, R outside [1, 65535], G outside [0, 8], max_errors outside [0, 32], margin < 0, cap < 0; alignment as
+ * above.  A record with a negative field, S >= 2^31 or a range that leaves [0, scan_elems) writes nothing, counts[i]
+ * included.  Additive to ABI 2.12: found by name. */
+int ov_wm_scan_pick(const int32_t* words, const float* pmin, const float* level, int64_t scan_elems, const int64_t* records,
+                    int R, const int32_t* groups, int G, int max_errors, float margin, int32_t* hits, int cap,
+                    int32_t* counts, ov_stream_t stream);
 
 /* Rate conversion at the audio boundary, reference openvoice/api.py:123,144 (``librosa.load(path, sr=...)`` = resampy's
  * kaiser_best band-limited sinc interpolation): a polyphase FIR over a mono waveform,
@@ -1002,7 +1037,8 @@ int ov_conv1d_wino_pack_f32(const float* w, int Cout, int Cin, int K, float* dst
  * workgroup; ov_conv1d_wino_chunk(11, 32) = 2 where 2.07 returned 0).  2.09: ov_conv1d_wino_params.out_slope (the field that
  * was `reserved0`: same size and offset, 0 = none).  2.10: ov_frame_hops_windows_f32, ov_stitch_window_cores_f32.  2.11: ov_frame_hops_multi_f32.  2.12: ov_carry_rows_f32 (and, added later within 2.12 without a version change, ov_polyphase_fir_rows_f32 and ov_vad_frame_energy_f32, ov_vad_segments_i32, ov_vad_compact_f32, ov_rows_f32_to_cl_bf16, ov_cl_bf16_to_rows_f32: additive symbols, which the Python binding looks up by name when it loads the library; likewise ov_wn_layer_wino_f32, ov_wn_layer_wino_tile, ov_wn_wino_pack_size and ov_wn_wino_pack_f32, and ov_join_segments_f32, and ov_pack_groups_cl_bf16 and ov_unpack_groups_f32, and ov_wn_layer_bf16, ov_wn_layer_bf16_supported,
  * ov_wn_layer_bf16_tile, ov_wn_bf16_pack_size and ov_wn_bf16_pack, and ov_wm_embed_windows_f32 and
- * ov_wm_detect_windows_f32, and ov_wm_embed_blocks_f32, and ov_stft_mag_f32,
+ * ov_wm_detect_windows_f32, and ov_wm_embed_blocks_f32, and ov_wm_scan_f32, ov_wm_scan_tile and ov_wm_scan_pick,
+ * and ov_stft_mag_f32,
  * ov_stft_tile_frames and ov_mel_log_f32; and ov_conv1d_params.scale_b, one pointer appended
  * to the struct and read only under OV_F_SCALE_B, a flag no older caller sets: the version stays 212 and a caller built
  * against the shorter struct stays binary compatible).  The Python binding

@@ -207,6 +207,10 @@ SIGNATURES = {
     "ov_wm_detect_windows_f32": (ctypes.c_int, [_fp, _i64, _fp, _i, _i64, ctypes.c_float, ctypes.c_float, _fp, _fp, _fp]),
     "ov_wm_embed_blocks_f32": (ctypes.c_int, [_fp, _i64, _fp, _i64, _fp, _i, _fp, _i64, _i64, ctypes.c_float, ctypes.c_float,
                                               _fp]),
+    "ov_wm_scan_f32": (ctypes.c_int, [_fp, _i64, _fp, _i, _i64, _i64, ctypes.c_float, ctypes.c_float, _fp, _fp, _fp, _fp, _i64,
+                                      _fp]),
+    "ov_wm_scan_tile": (ctypes.c_int, []),
+    "ov_wm_scan_pick": (ctypes.c_int, [_fp, _fp, _fp, _i64, _fp, _i, _fp, _i, _i, ctypes.c_float, _fp, _i, _fp, _fp]),
     "ov_stft_mag_f32": (ctypes.c_int, [_fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _fp]),
     "ov_stft_tile_frames": (ctypes.c_int, []),
     "ov_mel_log_f32": (ctypes.c_int, [_fp, _fp, _fp, _i, _i, _i, _i, _i, _i64, _i, ctypes.c_float, _fp]),
@@ -326,7 +330,7 @@ VALUE_FUNCS = {"ov_version", "ov_build_experiment", "ov_conv1d_pack_size", "ov_c
                "ov_resblock_pair_bf16_supported", "ov_resblock_pair2_bf16_supported", "ov_conv1d_split3_pack_size",
                "ov_conv1d_split3_supported", "ov_conv1d_wino_supported", "ov_conv1d_wino_chunk", "ov_conv1d_wino_pack_size",
                "ov_wn_layer_wino_tile", "ov_wn_wino_pack_size", "ov_wn_layer_bf16_supported", "ov_wn_bf16_pack_size",
-               "ov_wn_layer_bf16_tile", "ov_stft_tile_frames"}
+               "ov_wn_layer_bf16_tile", "ov_stft_tile_frames", "ov_wm_scan_tile"}
 
 
 def binding():

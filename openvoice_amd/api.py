@@ -610,24 +610,27 @@ class ToneColorConverter(OpenVoiceBaseClass):
         return out
 
     @wavenet_keyword
-    def convert(self, audio_src_path, src_se, tgt_se, output_path=None, tau=0.3, message="default", *, seed=None):
+    def convert(self, audio_src_path, src_se, tgt_se, output_path=None, tau=0.3, message="default", *, seed=None,
+                message_repeat=False):
         """reference: openvoice/api.py:141-160.  A file at or beyond the one-pass launch limit
         (``longform.one_pass_limit_frames``: 63 551 frames = 12.3 min for the released configuration), which one pass
         cannot convert, goes through ``convert_long`` with its defaults; every shorter file is converted in one pass.
         ``seed``: counter-based noise of stream ``(seed, 0)`` (or of a pair), the same whichever of the two paths
-        runs."""
+        runs.  ``message_repeat`` (native watermark only): every carrier window of the file carries group ``n % G`` of
+        the message, not the first ``G`` alone (``NativeWatermark.mark_many``)."""
         if seed is not None:
             seed = noise_mod.check_seed(seed)
+        self._check_repeat(message_repeat)
         hps = self.hps
         y = audio_io.load_to_device(audio_src_path, hps.data.sampling_rate, self.device)
         d = hps.data
         if longform.frames_of(y.numel(), d.filter_length, d.hop_length) >= longform.one_pass_limit_frames(self.model.model_cfg):
             return self.convert_long(y, src_se, tgt_se, output_path=output_path, tau=tau, message=message,
-                                     **noise_mod.kw(seed))
+                                     message_repeat=message_repeat, **noise_mod.kw(seed))
         o_hat, _ = self.convert_batch(y.unsqueeze(0), src_se, tgt_se, tau=tau,
                                       **noise_mod.kw(None if seed is None else [seed]))
         if self._native_watermark():         # marked on the device, before the copy to the host
-            self.watermark_model.mark_many([o_hat[0, 0].data], message)
+            self.watermark_model.mark_many([o_hat[0, 0].data], message, message_repeat=message_repeat)
         audio = o_hat[0, 0].data.cpu().float().numpy()
         if not self._native_watermark():
             audio = self.add_watermark(audio, message)
@@ -657,7 +660,13 @@ class ToneColorConverter(OpenVoiceBaseClass):
         device by ``NativeWatermark.mark_many``, one launch per call, instead of the host loop of ``add_watermark``."""
         return isinstance(self.watermark_model, watermark_mod.NativeWatermark)
 
-    def _finish_many(self, outs, message, out_srs):
+    def _check_repeat(self, message_repeat):
+        """``message_repeat=True`` on a file needs the native watermark (the wavmark hook marks the leading windows
+        only); ValueError otherwise, at the call."""
+        if message_repeat and not self._native_watermark():
+            raise ValueError('message_repeat=True needs the native watermark: ToneColorConverter(..., watermark="native")')
+
+    def _finish_many(self, outs, message, out_srs, message_repeat=False):
         """``_finish`` of many converted waveforms: without a model, or with the native one (which marks every carrier
         window of every item in ONE launch first), the rate conversion is one launch for all items; any other model
         keeps the per-item host loop."""
@@ -665,17 +674,17 @@ class ToneColorConverter(OpenVoiceBaseClass):
         if self.watermark_model is not None and not self._native_watermark():
             return [self._finish(o, message, r) for o, r in zip(outs, out_srs)]
         if self._native_watermark():
-            self.watermark_model.mark_many(outs, message)
+            self.watermark_model.mark_many(outs, message, message_repeat=message_repeat)
         outs = rates.resample_many(outs, [(msr, r) for r in out_srs], self.device)
         return [o.cpu().numpy() for o in outs]
 
-    def _finish(self, o, message, out_sr):
+    def _finish(self, o, message, out_sr, message_repeat=False):
         """Converted device waveform at the model rate -> host audio at ``out_sr`` (None: the model rate).  The watermark
         hook runs at the model rate, before the rate conversion."""
         msr = self.hps.data.sampling_rate
         resample = out_sr is not None and int(out_sr) != int(msr)
         if self._native_watermark():
-            self.watermark_model.mark_many([o], message)
+            self.watermark_model.mark_many([o], message, message_repeat=message_repeat)
         if self.watermark_model is None or self._native_watermark():
             return (audio_io.resample_on_device(o, msr, out_sr) if resample else o).cpu().numpy()
         audio = self.add_watermark(o.cpu().numpy(), message)
@@ -686,7 +695,7 @@ class ToneColorConverter(OpenVoiceBaseClass):
     @wavenet_keyword
     def convert_long(self, audio_or_path, src_se, tgt_se, output_path=None, tau=0.3, message="default",
                      window_frames=longform.DEFAULT_WINDOW_FRAMES, windows_per_launch=longform.DEFAULT_WINDOWS_PER_LAUNCH,
-                     noise=None, sr=None, out_sr=None, *, seed=None):
+                     noise=None, sr=None, out_sr=None, *, seed=None, message_repeat=False):
         """``convert`` for a recording of any length: overlapping windows of ``window_frames`` frames, up to
         ``windows_per_launch`` of them per launch (``longform.WindowedConverter``); device memory is bounded by the window,
         not by the file.  ``audio_or_path``: a file path, or a 1-D float32 waveform (host or device) at ``sr`` Hz (None:
@@ -695,13 +704,14 @@ class ToneColorConverter(OpenVoiceBaseClass):
         rate; or ``seed`` (an int: stream ``(seed, 0)``, or a pair): counter-based noise, each window generating its own
         frames, the same values as a one-pass ``convert(seed=...)``, a ``stream`` or a ``live_stream`` with that seed
         draws.  ``out_sr``: the rate of the returned / written audio (None: the model rate).  Otherwise the same return
-        value / file output as ``convert``."""
+        value / file output as ``convert``.  ``message_repeat``: as for ``convert``."""
         noise_mod.exclusive(seed, noise=noise)
+        self._check_repeat(message_repeat)
         sr, out_sr = rates.check_rate(sr, "sr"), rates.check_rate(out_sr, "out_sr")
         y = self._to_model_rate(audio_or_path, sr)
         o = self._windowed(window_frames, windows_per_launch).convert(y, src_se, tgt_se, tau=tau, noise=noise,
                                                                       **noise_mod.kw(seed))
-        audio = self._finish(o, message, out_sr)
+        audio = self._finish(o, message, out_sr, message_repeat)
         if output_path is None:
             return audio
         audio_io.write(output_path, audio, self.hps.data.sampling_rate if out_sr is None else out_sr)
@@ -810,7 +820,7 @@ class ToneColorConverter(OpenVoiceBaseClass):
     @wavenet_keyword
     def convert_many(self, items, src_se, tgt_se, tau=0.3, window_frames=longform.DEFAULT_WINDOW_FRAMES,
                      windows_per_launch=longform.DEFAULT_MANY_WINDOWS_PER_LAUNCH, noise=None, output_paths=None,
-                     message="default", sr=None, out_sr=None, *, seed=None, generator=None):
+                     message="default", sr=None, out_sr=None, *, seed=None, generator=None, message_repeat=False):
         """``convert_long`` of many recordings with their windows packed ACROSS recordings into launches of up to
         ``windows_per_launch`` (``longform.WindowedConverter.convert_many``).  ``items``: file paths (any rate, decoded
         and resampled like ``convert_long``) or 1-D waveforms at ``sr`` Hz (None: the model rate; one rate, or a list
@@ -824,8 +834,9 @@ class ToneColorConverter(OpenVoiceBaseClass):
         ``convert_long`` of it with the same ``window_frames``, noise and rates.  ``generator`` (keyword only): None
         follows ``use_bf16_generator``, ``"fp32"`` / ``"bf16"`` choose the generator's kernels for this call.  ``tau``:
         one number, or one per item; windows of items with different ``tau`` share launches, and each item still equals
-        its ``convert_long`` with its own ``tau``."""
+        its ``convert_long`` with its own ``tau``.  ``message_repeat``: as for ``convert``."""
         _lib.check_generator(generator, optional=True)
+        self._check_repeat(message_repeat)
         hps = self.hps
         msr = hps.data.sampling_rate
         items = list(items)
@@ -848,7 +859,7 @@ class ToneColorConverter(OpenVoiceBaseClass):
         outs = self._windowed(window_frames, windows_per_launch).convert_many(waves, srcs, tgts, tau=tau, noises=noise,
                                                                               **noise_mod.kw(seed, "seeds"),
                                                                               **_lib.generator_kw(generator))
-        audios = self._finish_many(outs, message, out_srs)
+        audios = self._finish_many(outs, message, out_srs, message_repeat)
         if output_paths is None:
             return audios
         for path, audio, r in zip(output_paths, audios, out_srs):
@@ -903,3 +914,19 @@ class ToneColorConverter(OpenVoiceBaseClass):
             print("Audio too short, fail to detect watermark")
             return "Fail"
         return bits_to_string(np.stack(groups).reshape(-1, 8))
+
+    def find_watermark(self, audio, message=None, **kw):
+        """Find the native watermark wherever it starts: ``audio`` is a file path (decoded and resampled to the model
+        rate like ``convert``'s input) or a 1-D float array / tensor AT THE MODEL RATE (audio at another rate is out of
+        scope: the chips are counted in model-rate samples).  Every offset is scanned on the device
+        (``NativeWatermark.find``, whose keywords ``max_errors``, ``margin``, ``max_false_alarm`` and ``capacity`` pass
+        through) and the verdict for the one waveform is returned: ``marked``, ``offset``, ``first_group``, ``message``,
+        ``windows``, ``false_alarm``, ``hits``, ``overflow``.  ``message=None`` is the blind mode, a heuristic.  Needs
+        ``watermark="native"``: ValueError otherwise.  ``detect_watermark`` is untouched."""
+        if not self._native_watermark():
+            raise ValueError('find_watermark needs the native watermark: ToneColorConverter(..., watermark="native")')
+        if isinstance(audio, (str, os.PathLike)):
+            y = audio_io.load_to_device(audio, self.hps.data.sampling_rate, self.device)
+        else:
+            y = torch.as_tensor(audio, dtype=torch.float32).reshape(-1).to(self.device)
+        return self.watermark_model.find([y], message, **kw)[0]

@@ -474,6 +474,8 @@ TORCH_LIBRARY(openvoice_amd, m) {
   bind_device<&ov_wm_embed_windows_f32>(m, "wm_embed_windows_f32");
   bind_device<&ov_wm_detect_windows_f32>(m, "wm_detect_windows_f32");
   bind_device<&ov_wm_embed_blocks_f32>(m, "wm_embed_blocks_f32");
+  bind_device<&ov_wm_scan_f32>(m, "wm_scan_f32");
+  bind_device<&ov_wm_scan_pick>(m, "wm_scan_pick");
   bind_device<&ov_stft_mag_f32>(m, "stft_mag_f32");
   bind_device<&ov_mel_log_f32>(m, "mel_log_f32");
   bind_device<&ov_stitch_window_cores_f32>(m, "stitch_window_cores_f32");
@@ -526,6 +528,7 @@ TORCH_LIBRARY(openvoice_amd, m) {
   bind_value<&ov_conv1d_wino_supported>(m, "conv1d_wino_supported");
   bind_value<&ov_conv1d_wino_chunk>(m, "conv1d_wino_chunk");
   bind_value<&ov_stft_tile_frames>(m, "stft_tile_frames");
+  bind_value<&ov_wm_scan_tile>(m, "wm_scan_tile");
   bind_value<&ov_conv1d_pack_size>(m, "conv1d_pack_size");
   bind_value<&ov_conv1d_pack_rows>(m, "conv1d_pack_rows");
   bind_value<&ov_wn_pack_size>(m, "wn_pack_size");

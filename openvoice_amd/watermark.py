@@ -23,8 +23,10 @@ host audio already carries strongly enough is left alone and an unattacked read 
 0.02`` and ``floor = 2^-12`` are design parameters: the floor keeps a silent window's mark above int16 rounding (which
 moves a projection by at most half an LSB, 1.6e-5).
 
-Out of scope: deciding whether audio is marked at all (like upstream's ``detect_watermark``, reading unmarked audio
-returns arbitrary characters), and robustness to resampling, MP3 coding or a time shift.
+Out of scope: robustness to resampling or MP3 coding, and audio at another rate than the model's (the chips are counted
+in model-rate samples).  ``detect_watermark`` keeps upstream's behaviour -- it reads the windows counted from sample 0 and
+returns arbitrary characters for unmarked audio; ``find`` (below, "the scan") is the reader that decides whether audio
+is marked and where.
 
 ``encode`` / ``decode`` / ``mark_many`` run the kernels (csrc/watermark.hip: ``ov_wm_embed_windows_f32``,
 ``ov_wm_detect_windows_f32``, record-driven, one workgroup per window, ONE launch for all windows); ``encode_host`` /
@@ -59,6 +61,25 @@ it does not depend on chunking, on the pool or on the launch.  A sample leaves o
 ``H - 1`` samples later than without a message; samples outside carrier windows pass through in order, behind a held
 block; at the end of the stream the samples of an unfinished block leave unmarked.  ``plan_blocks`` is the schedule,
 ``mark_stream_host`` the float64 mirror of a whole stream, ``MarkBank`` the device side for many streams in one launch.
+
+The scan (``NativeWatermark.find``, ``ToneColorConverter.find_watermark``): chips and bit ownership are counted from the
+window's start, so a mark survives any change to the start of the audio -- a cut, a prepended jingle, a clip from the
+middle of a ``message_repeat`` stream -- and only a reader that looks at EVERY offset is needed.  With ``i = 32 m + j``,
+``t = s + j`` and ``C[m][j] = c[32 m + j]`` (500 x 32, entries +-1)::
+
+    Q[t][j] = sum_{m < 500} x[t + 32 m] C[m][j]          p_j(s) = Q[s + j][j] / 500
+    W[t]    = sum_{m < 500} x[t + 32 m]^2                a(s)   = max(strength sqrt(sum_j W[s + j] / 16 000), floor)
+
+which is, for 32 consecutive ``t``, one 32 x 32 x 500 product of the waveform read as a ``[., 32]`` matrix with ``C``:
+``ov_wm_scan_f32`` (csrc/watermark_scan.hip) runs it on the fp32 matrix pipe and writes per offset the 32 read bits, ``min_j
+|p_j|`` and the level; ``ov_wm_scan_pick`` compacts the offsets whose bits are within ``max_errors`` of a group of the
+message -- or, without a message ("blind"), whose weakest projection reaches ``margin`` times the level, which an
+unattacked file mark does at every bit by construction and the unmarked test signals did at 11 of 6.5 million offsets,
+never twice at the stride -- into an ordered list.  The host
+then chains hits that lie ``STRIDE`` apart and whose groups follow each other.  With a known message the expected number
+of chance chains of that length, ``S G (sum_{e <= max_errors} C(32, e) / 2^32)^len`` over ``S`` offsets, is reported as
+``false_alarm`` and decides ``marked``; the blind criterion (a chain of at least two windows) is a heuristic without
+such a figure.  ``scan_host`` is the float64 mirror.
 """
 import numpy as np
 
@@ -154,6 +175,140 @@ def decode_host(carrier, key=0, strength=DEFAULT_STRENGTH, floor=DEFAULT_FLOOR):
     """Scores ``[B, 32]`` in float64: ``0.5 + 0.5 tanh(q / a)``."""
     q, a = read_host(carrier, key, strength, floor)
     return 0.5 + 0.5 * np.tanh(q / a[:, None])
+
+
+def plan_windows(length, groups, repeat=False):
+    """The carrier windows of a file of ``length`` samples whose message has ``groups`` groups: ``[(start, group)]`` for
+    every window ``n`` (``start = 32 000 n``) that lies wholly inside the file and carries a group -- ``n`` itself below
+    ``groups``, ``n % groups`` for every ``n`` with ``repeat``."""
+    out, n = [], 0
+    while n * STRIDE + WINDOW <= int(length):
+        group = _group_of(n, int(groups), repeat)
+        if group is None:
+            break
+        out.append((n * STRIDE, group))
+        n += 1
+    return out
+
+
+def scan_host(x, key=0, strength=DEFAULT_STRENGTH, floor=DEFAULT_FLOOR):
+    """The float64 mirror of ``ov_wm_scan_f32``: ``(p [S, 32], level [S])`` of the waveform ``x`` (1-D, ``S = len(x) -
+    15 999`` offsets): row ``s`` is ``read_host(x[s:s + 16 000])``, computed through the decomposition of the module
+    docstring -- ``Q = X C`` on a strided view of ``x``, then the skewed read ``p[s][j] = Q[s + j][j] / 500``."""
+    key, strength, floor = check_params(key, strength, floor)
+    x = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1))
+    S = x.size - WINDOW + 1
+    if S < 1:
+        raise ValueError(f"scan_host: {x.size} samples hold no window of {WINDOW}")
+    rows = WINDOW // BITS
+    C = chips_host(key, WINDOW).reshape(rows, BITS)
+    T = S + BITS - 1                                     # t = s + j
+    X = np.lib.stride_tricks.as_strided(x, shape=(T, rows), strides=(x.strides[0], BITS * x.strides[0]), writeable=False)
+    Q, W = np.empty((T, BITS)), np.empty(T)
+    for t0 in range(0, T, 8192):                         # (the strided view is copied by the product: bound it)
+        part = X[t0:t0 + 8192]
+        Q[t0:t0 + 8192] = part @ C
+        W[t0:t0 + 8192] = np.einsum("tm,tm->t", part, part)
+    sj = np.arange(S)[:, None] + np.arange(BITS)[None, :]
+    p = Q[sj, np.arange(BITS)[None, :]] / rows
+    energy = W[sj].sum(axis=1)
+    return p, np.maximum(strength * np.sqrt(energy / WINDOW), floor)
+
+
+# ---- the scan: chains of hits and their chance -------------------------------------------------------------------------
+HIT_CAPACITY = 4096         # hit rows kept per waveform (the true count is reported beyond it)
+MAX_GROUPS = 8
+SCAN_RECORD_FIELDS = 3      # (src_off, n, out_off)
+
+
+def word_to_string(word):
+    """The four latin-1 characters a payload word carries (the inverse of ``groups_of`` for one group)."""
+    from .api import bits_to_string
+    bits = np.array([(int(word) >> j) & 1 for j in range(BITS)], dtype=np.uint8)
+    return bits_to_string(bits.reshape(-1, 8))
+
+
+def false_alarm(offsets, groups, max_errors, length):
+    """The expected number of chance chains of ``length`` windows among ``offsets`` scanned offsets for a message of
+    ``groups`` groups: ``offsets * groups * (sum_{e <= max_errors} C(32, e) / 2^32)^length`` -- unmarked audio's read
+    bits taken as fair coins, independent between windows ``STRIDE`` apart."""
+    from math import comb
+    if length < 1:
+        raise ValueError("false_alarm: a chain has at least one window")
+    q = sum(comb(BITS, e) for e in range(int(max_errors) + 1)) / 2.0 ** BITS
+    return float(offsets) * float(groups) * q ** int(length)
+
+
+def build_chains(hits, groups):
+    """Chains among ``hits`` (rows ``(s, word, k, errors)`` in ascending ``s``, at most one per ``s``): maximal runs of
+    hits at ``s, s + 32 000, ...`` whose group indices run ``k, (k + 1) % groups, ...``; with ``groups == 0`` (blind) any
+    hits at that stride chain.  Returns the chains, each a list of hit rows, best first: longest, then fewest errors,
+    then earliest."""
+    by_s = {int(h[0]): tuple(int(v) for v in h) for h in hits}
+    if len(by_s) != len(hits):
+        raise ValueError("build_chains: two hits at one offset")
+
+    def follows(a, b):
+        return groups == 0 or b[2] == (a[2] + 1) % groups
+
+    chains = []
+    for s in sorted(by_s):
+        h = by_s[s]
+        prev = by_s.get(s - STRIDE)
+        if prev is not None and follows(prev, h):
+            continue                                     # inside a chain that started earlier
+        chain = [h]
+        while True:
+            nxt = by_s.get(chain[-1][0] + STRIDE)
+            if nxt is None or not follows(chain[-1], nxt):
+                break
+            chain.append(nxt)
+        chains.append(chain)
+    chains.sort(key=lambda c: (-len(c), sum(h[3] for h in c), c[0][0]))
+    return chains
+
+
+def judge(hits, count, offsets, words, message, max_errors, max_false_alarm, ratios=None):
+    """One waveform's verdict from its hit rows (``count``: the true number of hits, which may exceed ``len(hits)``;
+    ``words``: the message's groups, empty for blind mode; ``ratios``: ``pmin / level`` per hit row, or None)."""
+    G = len(words)
+    ratios = [None] * len(hits) if ratios is None else [float(r) for r in ratios]
+    ratio_of = {int(h[0]): r for h, r in zip(hits, ratios)}
+    chains = build_chains(hits, G)
+    res = {"marked": False, "offset": None, "first_group": None, "message": message, "windows": [], "false_alarm": None,
+           "hits": int(count), "overflow": int(count) > len(hits)}
+    if not chains:
+        return res
+    best = chains[0]
+    res["offset"] = best[0][0]
+    res["windows"] = [(s, k if G else None, w & 0xFFFFFFFF, e, ratio_of[s]) for s, w, k, e in best]
+    if G:
+        res["first_group"] = best[0][2]
+        res["false_alarm"] = false_alarm(offsets, G, max_errors, len(best))
+        res["marked"] = res["false_alarm"] <= max_false_alarm
+    else:
+        res["message"] = "".join(word_to_string(w) for _, w, _, _ in best)
+        res["marked"] = len(best) >= 2
+    return res
+
+
+def check_find_args(message, max_errors, margin, max_false_alarm, capacity=HIT_CAPACITY):
+    """The arguments of ``find`` as ``(payload words, max_errors, margin, max_false_alarm, capacity)``; ValueError for a
+    message that is no string, ``max_errors`` outside ``[0, 32]``, ``margin`` outside ``(0, 1]``, ``max_false_alarm``
+    outside ``(0, 1]`` or a negative capacity."""
+    if message is not None and not isinstance(message, str):
+        raise ValueError(f"message must be a string or None, got {message!r}")
+    if not _is_int(max_errors) or not 0 <= int(max_errors) <= BITS:
+        raise ValueError(f"max_errors: an int in [0, {BITS}], got {max_errors!r}")
+    if not isinstance(margin, (int, float, np.floating)) or isinstance(margin, bool) or not 0.0 < float(margin) <= 1.0:
+        raise ValueError(f"margin outside (0, 1]: {margin!r}")
+    if not isinstance(max_false_alarm, (int, float, np.floating)) or isinstance(max_false_alarm, bool) or \
+            not 0.0 < float(max_false_alarm) <= 1.0:
+        raise ValueError(f"max_false_alarm outside (0, 1]: {max_false_alarm!r}")
+    if not _is_int(capacity) or int(capacity) < 0:
+        raise ValueError(f"capacity: a non-negative int, got {capacity!r}")
+    words = [] if message is None else groups_of(message)
+    return words, int(max_errors), float(margin), float(max_false_alarm), int(capacity)
 
 
 # ---- streams: the schedule and the float64 mirror ---------------------------------------------------------------------
@@ -314,6 +469,58 @@ def embed_blocks(src, dst, records, state, key=0, strength=DEFAULT_STRENGTH, flo
         recs = torch.tensor(part, dtype=torch.int64).to(src.device)
         _lib.call("ov_wm_embed_blocks_f32", src, src.numel(), dst, dst.numel(), recs, len(part), state, state.shape[0], key,
                   strength, floor)
+
+
+def scan(src, records, key=0, strength=DEFAULT_STRENGTH, floor=DEFAULT_FLOOR, out_elems=None, projections=False):
+    """``ov_wm_scan_f32`` on host rows ``(src_off, n, out_off)``: ``(words int32 [E], pmin [E], level [E])`` on the
+    device (``E = out_elems``, default: where the last output range ends), and ``p [E, 32]`` as a fourth with
+    ``projections``.  What no record covers keeps its fill: 0 / NaN.  ONE launch (per 65535 records).  The rows go to the
+    kernel as they are: it checks every one and a bad one writes nothing."""
+    import torch
+    key, strength, floor = check_params(key, strength, floor)
+    _check_buffer(src, "src")
+    table = [tuple(int(v) for v in rec) for rec in records]
+    if not table or any(len(rec) != SCAN_RECORD_FIELDS for rec in table):
+        raise ValueError("a scan record is (src_off, n, out_off), and a call has at least one")
+    if out_elems is None:
+        out_elems = max(oo + max(n - WINDOW + 1, 0) for _, n, oo in table)
+    out_elems = max(int(out_elems), 1)
+    dev = src.device
+    words = torch.zeros(out_elems, dtype=torch.int32, device=dev)
+    pmin = torch.full((out_elems,), float("nan"), dtype=torch.float32, device=dev)
+    level = torch.full((out_elems,), float("nan"), dtype=torch.float32, device=dev)
+    p = torch.full((out_elems, BITS), float("nan"), dtype=torch.float32, device=dev) if projections else None
+    for i in range(0, len(table), MAX_RECORDS):
+        part = table[i:i + MAX_RECORDS]
+        max_n = min(max(max(n for _, n, _ in part), WINDOW), MAX_WINDOW)
+        recs = torch.tensor(part, dtype=torch.int64).to(dev)
+        _lib.call("ov_wm_scan_f32", src, src.numel(), recs, len(part), max_n, key, strength, floor, words, pmin, level, p,
+                  out_elems)
+    return (words, pmin, level, p) if projections else (words, pmin, level)
+
+
+def scan_pick(words, pmin, level, records, groups=(), max_errors=0, margin=0.98, capacity=HIT_CAPACITY):
+    """``ov_wm_scan_pick`` on host rows ``(scan_off, S)``: ``(hits int32 [R, capacity, 4], counts int32 [R])`` on the
+    device; ``groups``: up to 8 payload words, none for blind mode.  ONE launch (per 65535 records)."""
+    import torch
+    dev = words.device
+    table = [tuple(int(v) for v in rec) for rec in records]
+    if not table or any(len(rec) != 2 for rec in table):
+        raise ValueError("a pick record is (scan_off, S), and a call has at least one")
+    groups = [int(g) for g in groups]
+    if len(groups) > MAX_GROUPS:
+        raise ValueError(f"at most {MAX_GROUPS} groups")
+    g = None
+    if groups:
+        g = torch.tensor([w - (1 << BITS) if w >= 1 << (BITS - 1) else w for w in groups], dtype=torch.int32).to(dev)
+    hits = torch.zeros(len(table), capacity, 4, dtype=torch.int32, device=dev)
+    counts = torch.zeros(len(table), dtype=torch.int32, device=dev)
+    for i in range(0, len(table), MAX_RECORDS):
+        part = table[i:i + MAX_RECORDS]
+        recs = torch.tensor(part, dtype=torch.int64).to(dev)
+        _lib.call("ov_wm_scan_pick", words, pmin, level, words.numel(), recs, len(part), g, len(groups), int(max_errors),
+                  float(margin), hits[i:i + len(part)] if capacity else None, capacity, counts[i:i + len(part)])
+    return hits, counts
 
 
 def stream_mark(model, message, hold=DEFAULT_HOLD, repeat=False):
@@ -546,10 +753,12 @@ class NativeWatermark:
         """The payload words of ``message`` (padded / cut to 8 latin-1 characters): one per 32-bit group, in order."""
         return groups_of(message)
 
-    def mark_many(self, waves, messages):
+    def mark_many(self, waves, messages, *, message_repeat=False):
         """Mark, in place and in ONE launch, every carrier window of every waveform of ``waves`` (1-D float32 device
         tensors at the model rate) with its message (``messages``: one string for all, or one per waveform).  The
-        windows are the hook's: group n of the message in the 16 000 samples from 32 000 n.  A waveform too short for
+        windows are the hook's: group n of the message in the 16 000 samples from 32 000 n; with ``message_repeat``
+        every window n the file holds carries group ``n % G``, as a stream's may, so that a file cut anywhere still
+        holds a chain ``find`` can follow.  A waveform too short for
         all groups carries the leading ones and the upstream notice is printed, once per such waveform.  Waveforms that
         are views of one tensor (``convert_many``'s outputs) are marked where they are; others are gathered into one
         buffer first and copied back.  Returns ``waves``."""
@@ -566,8 +775,8 @@ class NativeWatermark:
         words = {m: self.groups_of(m) for m in set(msgs)}
         for i, (w, m) in enumerate(zip(waves, msgs)):
             groups = words[m]
-            fit = [g for n, g in enumerate(groups) if n * STRIDE + WINDOW <= w.numel()]
-            plan += [(i, n * STRIDE, g) for n, g in enumerate(fit)]
+            fit = plan_windows(w.numel(), len(groups), bool(message_repeat))
+            plan += [(i, start, groups[k]) for start, k in fit]
             if len(fit) < len(groups):
                 print("Audio too short, fail to add watermark")
         if not plan:
@@ -589,3 +798,63 @@ class NativeWatermark:
             for i in used:
                 waves[i].copy_(base[offs[i]:offs[i] + waves[i].numel()])
         return waves
+
+    def find(self, waves, message=None, *, max_errors=0, margin=0.98, max_false_alarm=1e-6, capacity=HIT_CAPACITY):
+        """Look for the mark at EVERY offset of every waveform of ``waves`` (1-D float32 device tensors at the model
+        rate): one ``ov_wm_scan_f32`` launch and one ``ov_wm_scan_pick`` launch for all of them, then chains on the
+        host.  With ``message`` an offset is a hit when its 32 read bits are within ``max_errors`` of one of the
+        message's groups; hits ``32 000`` apart whose groups follow each other (``k, k + 1 mod G``) form a chain, and
+        the best chain (longest, fewest errors, earliest) is the answer.  Returns one dict per waveform:
+
+        * ``marked``: ``false_alarm <= max_false_alarm``;
+        * ``offset``: the start of the chain's first window (None without a hit), ``first_group``: the group it carries;
+        * ``message``: the message asked for, or in blind mode the characters read, four per window in chain order;
+        * ``windows``: ``(offset, group, word, errors, pmin / level)`` per window of the chain;
+        * ``false_alarm``: the expected number of chance chains of this length, ``S G (sum_{e <= max_errors} C(32, e) /
+          2^32)^len`` over the ``S`` offsets scanned -- about 1e-4 for ONE exact window in a 10 s file, which is
+          therefore reported but not called marked at the default, and 1e-14 for two;
+        * ``hits``: hit offsets in all, ``overflow``: more than ``capacity`` of them (the chains then come from the first
+          ``capacity``).
+
+        Without a message (blind mode) an offset is a hit when ``min_j |p_j| >= margin * level`` -- every bit reaches
+        the level, as the embedder guarantees for a file mark and unmarked test signals gave at 11 of 6.5 million
+        offsets; any hits ``32 000`` apart chain, ``marked`` needs a chain of at least two windows and ``false_alarm`` is
+        None: this criterion is a HEURISTIC, with no proven false-alarm figure (DESIGN.md section 29 gives the counts
+        measured on unmarked signals), and audio that went through int16 or any other change may fall under
+        ``margin``.  Audio at another rate than the model's is out of scope.  Arguments are checked at the call."""
+        import torch
+        words, max_errors, margin, max_false_alarm, capacity = check_find_args(message, max_errors, margin, max_false_alarm,
+                                                                               capacity)
+        waves = list(waves)
+        for w in waves:
+            if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or not w.is_cuda or w.dim() != 1:
+                raise ValueError("find: waveforms must be 1-D float32 tensors on a ROCm device")
+        long = [i for i, w in enumerate(waves) if w.numel() >= WINDOW]
+        results = [judge([], 0, 0, words, message, max_errors, max_false_alarm) for _ in waves]
+        if not long:
+            return results
+        src = torch.cat([waves[i] for i in long]) if len(long) > 1 else waves[long[0]].contiguous()
+        recs, picks, so, oo = [], [], 0, 0
+        for i in long:
+            n = waves[i].numel()
+            recs.append((so, n, oo))
+            picks.append((oo, n - WINDOW + 1))
+            so, oo = so + n, oo + n - WINDOW + 1
+        sw, pmin, level = scan(src, recs, *self._params(), out_elems=oo)
+        hits, counts = scan_pick(sw, pmin, level, picks, words, max_errors, margin, capacity)
+        self.launches += 2 * ((len(recs) + MAX_RECORDS - 1) // MAX_RECORDS)
+        counts = counts.cpu().numpy()
+        kept = np.minimum(counts, capacity)
+        hits = hits.cpu().numpy()
+        where = np.concatenate([picks[r][0] + hits[r, :kept[r], 0].astype(np.int64) for r in range(len(long))])
+        ratios = np.zeros(0)
+        if where.size:
+            idx = torch.from_numpy(where).to(src.device)
+            ratios = (pmin[idx] / level[idx]).cpu().numpy()
+        at = 0
+        for r, i in enumerate(long):
+            rows = [tuple(int(v) for v in h) for h in hits[r, :kept[r]]]
+            results[i] = judge(rows, counts[r], picks[r][1], words, message, max_errors, max_false_alarm,
+                               ratios[at:at + kept[r]])
+            at += kept[r]
+        return results
