@@ -598,6 +598,31 @@ int ov_wm_scan_pick(const int32_t* words, const float* pmin, const float* level,
                     int R, const int32_t* groups, int G, int max_errors, float margin, int32_t* hits, int cap,
                     int32_t* counts, ov_stream_t stream);
 
+/* speed= / duration= of a conversion (openvoice_amd/stretch.py: the definition and its float64 / integer mirror; the
+ * project's own -- nothing in the reference stretches a conversion): the masked latent z_hat, fp32 rows, resampled along
+ * time between the reverse flow and the generator.  records is a DEVICE int64 [n_records][10] of
+ *   (src_off, dst_off, rows, src_ld, dst_ld, t_in, i0, j0, n_out, step)
+ * offsets and lds in elements relative to src / dst; i0 the GLOBAL frame index of the source's column 0, j0 the global
+ * index of the first output frame written, step = round(speed * 2^32) in [2^31, 2^33].  For jj < n_out, j = j0 + jj:
+ *   pos = j * step (int64),  i = pos >> 32,  f = ((pos & 0xffffffff) >> 8) * 2^-24   (exact in fp32)
+ *   dst[dst_off + r * dst_ld + jj] = a + f * (b - a),   a = src[src_off + r * src_ld + i - i0],
+ *                                                       b = src[src_off + r * src_ld + min(i + 1 - i0, t_in - 1)]
+ * in fp32, in that order -- subtract, multiply, add, never contracted to an fma.  The weights depend on the global j
+ * alone: a window of a long recording computes the bits of the whole-file stretch, and nothing depends on the launch's
+ * shape.  step = 2^32 copies.  Source and destination must not overlap.  records_host is a HOST copy of the same
+ * table: the call checks every record of it before it launches anything, and one bad record makes it return
+ * OV_E_BADARG with nothing launched; it also sizes the grid (the largest n_out and rows).  The kernel checks every
+ * record of the DEVICE table again, with the same function, so a record that is out of range there is never executed
+ * and writes nothing.  A record is good when rows, t_in and n_out lie in [1, 2^31], t_in <= src_ld <= 2^31,
+ * n_out <= dst_ld <= 2^31, the offsets in [0, 2^61], 0 <= i0 <= 2^31, j0 >= 0, j0 + n_out <= 2^29, both spans lie inside
+ * [0, src_elems) / [0, dst_elems), and 0 <= i - i0 <= t_in - 1 for every j it covers.  The neighbour i + 1 is clamped to
+ * the slice's last column: the caller gives a slice that holds column i + 1 of its last j or that ends at the
+ * recording's true end (openvoice_amd/stretch.py: plan_windows).  Other host checks: null pointers, n_records outside
+ * [1, 65535], extents <= 0 (OV_E_BADARG); src / dst 4-byte, records 8-byte aligned (OV_E_ALIGN).  Plain VALU, threads
+ * along j, no LDS, no atomics.  Additive to ABI 2.12: found by name. */
+int ov_stretch_rows_f32(const int64_t* records, const int64_t* records_host, int n_records, const float* src,
+                        int64_t src_elems, float* dst, int64_t dst_elems, ov_stream_t stream);
+
 /* Rate conversion at the audio boundary, reference openvoice/api.py:123,144 (``librosa.load(path, sr=...)`` = resampy's
  * kaiser_best band-limited sinc interpolation): a polyphase FIR over a mono waveform,
  *   y[t] = sum_{j < 2 taps} h[t % P][j] * x[(t * Q) / P - taps + 1 + j]        (x = 0 outside [0, n_in))
@@ -1038,7 +1063,7 @@ int ov_conv1d_wino_pack_f32(const float* w, int Cout, int Cin, int K, float* dst
  * was `reserved0`: same size and offset, 0 = none).  2.10: ov_frame_hops_windows_f32, ov_stitch_window_cores_f32.  2.11: ov_frame_hops_multi_f32.  2.12: ov_carry_rows_f32 (and, added later within 2.12 without a version change, ov_polyphase_fir_rows_f32 and ov_vad_frame_energy_f32, ov_vad_segments_i32, ov_vad_compact_f32, ov_rows_f32_to_cl_bf16, ov_cl_bf16_to_rows_f32: additive symbols, which the Python binding looks up by name when it loads the library; likewise ov_wn_layer_wino_f32, ov_wn_layer_wino_tile, ov_wn_wino_pack_size and ov_wn_wino_pack_f32, and ov_join_segments_f32, and ov_pack_groups_cl_bf16 and ov_unpack_groups_f32, and ov_wn_layer_bf16, ov_wn_layer_bf16_supported,
  * ov_wn_layer_bf16_tile, ov_wn_bf16_pack_size and ov_wn_bf16_pack, and ov_wm_embed_windows_f32 and
  * ov_wm_detect_windows_f32, and ov_wm_embed_blocks_f32, and ov_wm_scan_f32, ov_wm_scan_tile and ov_wm_scan_pick,
- * and ov_stft_mag_f32,
+ * and ov_stretch_rows_f32, and ov_stft_mag_f32,
  * ov_stft_tile_frames and ov_mel_log_f32; and ov_conv1d_params.scale_b, one pointer appended
  * to the struct and read only under OV_F_SCALE_B, a flag no older caller sets: the version stays 212 and a caller built
  * against the shorter struct stays binary compatible).  The Python binding

@@ -211,6 +211,7 @@ SIGNATURES = {
                                       _fp]),
     "ov_wm_scan_tile": (ctypes.c_int, []),
     "ov_wm_scan_pick": (ctypes.c_int, [_fp, _fp, _fp, _i64, _fp, _i, _fp, _i, _i, ctypes.c_float, _fp, _i, _fp, _fp]),
+    "ov_stretch_rows_f32": (ctypes.c_int, [_fp, _fp, _i, _fp, _i64, _fp, _i64, _fp]),
     "ov_stft_mag_f32": (ctypes.c_int, [_fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _fp]),
     "ov_stft_tile_frames": (ctypes.c_int, []),
     "ov_mel_log_f32": (ctypes.c_int, [_fp, _fp, _fp, _i, _i, _i, _i, _i, _i64, _i, ctypes.c_float, _fp]),

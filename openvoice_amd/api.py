@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib, audio_io, longform, rates, utils
+from . import stretch as stretch_mod
 from .engine import item_tau, wavenet_keyword
 from . import noise as noise_mod
 from . import watermark as watermark_mod
@@ -521,7 +522,7 @@ class ToneColorConverter(OpenVoiceBaseClass):
 
     @wavenet_keyword
     @torch.no_grad()
-    def convert_batch(self, waveforms, src_se, tgt_se, tau=0.3, noise=None, *, seed=None):
+    def convert_batch(self, waveforms, src_se, tgt_se, tau=0.3, noise=None, *, seed=None, speed=None):
         """Batched conversion, everything on the device.
 
         ``waveforms``: float32 tensor ``[B, N]`` (equal lengths), or a list of 1-D tensors/arrays of
@@ -535,7 +536,16 @@ class ToneColorConverter(OpenVoiceBaseClass):
         draws ``noise.normal((s, b), 192, 0, T)``, whatever the batch it is in.  ``tau``: one number, or one value per
         waveform (a sequence, or a 1-D float32 device tensor; ``engine.item_tau``): item ``b`` is then converted with
         ``tau[b]`` in the same launches, bit for bit what the batch gives with that number for all (a per-item ``tau``
-        runs eagerly: captured graphs are keyed on one ``tau``)."""
+        runs eagerly: captured graphs are keyed on one ``tau``).  ``speed`` (keyword only; None: all of the above, launch
+        for launch): one number in ``[0.5, 2.0]`` or one per waveform -- item ``b`` comes out ``speed[b]`` times faster at
+        unchanged pitch: its masked latent is resampled along time on the device in front of the generator
+        (``openvoice_amd/stretch.py``, the project's own definition; ``ov_stretch_rows_f32``), which then makes
+        ``T_out[b] = stretch.t_out(T[b], step)`` frames.  The returned lengths are ``T_out * hop``, the padded tail is
+        zero; ``tau``, ``seed`` and ``noise`` act before the stretch; a stretched call runs eagerly.  ``speed=1.0`` is
+        the identity and launches nothing.  ValueError outside the range.  The one-pass launch limit
+        (``longform.one_pass_limit_frames``, 63 551 frames) holds for ``T_out`` as it does for ``T``: slowed down, a
+        waveform of half that length already reaches it (``OvError`` from the generator's launchers); ``convert`` routes
+        on ``max(T, T_out)`` and hands such a file to ``convert_long``."""
         noise_mod.exclusive(seed, noise=noise)
         tau = item_tau(len(waveforms), tau)
         hop = self.hps.data.hop_length
@@ -554,6 +564,14 @@ class ToneColorConverter(OpenVoiceBaseClass):
             spec_lengths = torch.full((spec.shape[0],), spec.shape[2], dtype=torch.int64, device=self.device)
         if seed is not None:
             seed = noise_mod.per_item(seed, spec.shape[0])
+        frames = frames if ragged else [spec.shape[2]] * spec.shape[0]
+        steps = stretch_mod.resolve_items(speed, None, frames, hop, self.hps.data.sampling_rate)
+        if steps is not None and any(s != stretch_mod.ONE for s in steps):
+            o_hat = self.model.voice_conversion(spec, torch.tensor(frames, dtype=torch.int64), sid_src=src_se,
+                                                sid_tgt=tgt_se, tau=tau, noise=noise, stretch=steps,
+                                                **noise_mod.kw(seed))[0]
+            out_frames = [stretch_mod.t_out(T, s) for T, s in zip(frames, steps)]
+            return o_hat, torch.tensor(out_frames, dtype=torch.int64).to(self.device) * hop
         if self.use_graphs:
             # the graph's outputs are static buffers: hand the caller its own copy
             o_hat = self.model.voice_conversion(spec, spec_lengths, sid_src=src_se, sid_tgt=tgt_se, tau=tau,
@@ -611,24 +629,37 @@ class ToneColorConverter(OpenVoiceBaseClass):
 
     @wavenet_keyword
     def convert(self, audio_src_path, src_se, tgt_se, output_path=None, tau=0.3, message="default", *, seed=None,
-                message_repeat=False):
+                message_repeat=False, speed=None, duration=None):
         """reference: openvoice/api.py:141-160.  A file at or beyond the one-pass launch limit
         (``longform.one_pass_limit_frames``: 63 551 frames = 12.3 min for the released configuration), which one pass
         cannot convert, goes through ``convert_long`` with its defaults; every shorter file is converted in one pass.
         ``seed``: counter-based noise of stream ``(seed, 0)`` (or of a pair), the same whichever of the two paths
         runs.  ``message_repeat`` (native watermark only): every carrier window of the file carries group ``n % G`` of
-        the message, not the first ``G`` alone (``NativeWatermark.mark_many``)."""
+        the message, not the first ``G`` alone (``NativeWatermark.mark_many``).  ``speed`` (a number in ``[0.5, 2.0]``) or
+        ``duration`` (seconds; the speed is then ``T * hop / (duration * sr)``, same range) -- one of them, ValueError for
+        both -- change the length of the result at unchanged pitch (``convert_batch``); they go with an over-length file
+        to ``convert_long``.  The watermark is made on the stretched waveform."""
         if seed is not None:
             seed = noise_mod.check_seed(seed)
         self._check_repeat(message_repeat)
+        if speed is not None and duration is not None:
+            stretch_mod.resolve(speed, duration)
         hps = self.hps
         y = audio_io.load_to_device(audio_src_path, hps.data.sampling_rate, self.device)
         d = hps.data
-        if longform.frames_of(y.numel(), d.filter_length, d.hop_length) >= longform.one_pass_limit_frames(self.model.model_cfg):
+        T = longform.frames_of(y.numel(), d.filter_length, d.hop_length)
+        step = stretch_mod.resolve(speed, duration, T, d.hop_length, d.sampling_rate) if T >= 1 else None
+        # the generator runs on T_out frames: a file slowed down past the one-pass limit goes to the windows too
+        longest = T if step is None else max(T, stretch_mod.t_out(T, step))
+        if longest >= longform.one_pass_limit_frames(self.model.model_cfg):
             return self.convert_long(y, src_se, tgt_se, output_path=output_path, tau=tau, message=message,
-                                     message_repeat=message_repeat, **noise_mod.kw(seed))
-        o_hat, _ = self.convert_batch(y.unsqueeze(0), src_se, tgt_se, tau=tau,
-                                      **noise_mod.kw(None if seed is None else [seed]))
+                                     message_repeat=message_repeat, **noise_mod.kw(seed),
+                                     **stretch_mod.kw(speed=speed, duration=duration))
+        o_hat, n = self.convert_batch(y.unsqueeze(0), src_se, tgt_se, tau=tau,
+                                      **noise_mod.kw(None if seed is None else [seed]),
+                                      **stretch_mod.kw(speed=None if step is None else step / stretch_mod.ONE))
+        if step is not None:
+            o_hat = o_hat[:, :, :int(n[0])]
         if self._native_watermark():         # marked on the device, before the copy to the host
             self.watermark_model.mark_many([o_hat[0, 0].data], message, message_repeat=message_repeat)
         audio = o_hat[0, 0].data.cpu().float().numpy()
@@ -695,7 +726,7 @@ class ToneColorConverter(OpenVoiceBaseClass):
     @wavenet_keyword
     def convert_long(self, audio_or_path, src_se, tgt_se, output_path=None, tau=0.3, message="default",
                      window_frames=longform.DEFAULT_WINDOW_FRAMES, windows_per_launch=longform.DEFAULT_WINDOWS_PER_LAUNCH,
-                     noise=None, sr=None, out_sr=None, *, seed=None, message_repeat=False):
+                     noise=None, sr=None, out_sr=None, *, seed=None, message_repeat=False, speed=None, duration=None):
         """``convert`` for a recording of any length: overlapping windows of ``window_frames`` frames, up to
         ``windows_per_launch`` of them per launch (``longform.WindowedConverter``); device memory is bounded by the window,
         not by the file.  ``audio_or_path``: a file path, or a 1-D float32 waveform (host or device) at ``sr`` Hz (None:
@@ -704,13 +735,22 @@ class ToneColorConverter(OpenVoiceBaseClass):
         rate; or ``seed`` (an int: stream ``(seed, 0)``, or a pair): counter-based noise, each window generating its own
         frames, the same values as a one-pass ``convert(seed=...)``, a ``stream`` or a ``live_stream`` with that seed
         draws.  ``out_sr``: the rate of the returned / written audio (None: the model rate).  Otherwise the same return
-        value / file output as ``convert``.  ``message_repeat``: as for ``convert``."""
+        value / file output as ``convert``.  ``message_repeat``: as for ``convert``.  ``speed`` / ``duration``: as for
+        ``convert`` (``duration`` is that of the result at the model rate's clock, whatever ``out_sr``); the windows are
+        cut on source frames as always, each stretched with its global position, so the result is the one-pass
+        ``convert_batch(speed=...)`` of the recording within the windows' contract
+        (``WindowedConverter.convert``).  The watermark and ``out_sr`` act on the stretched waveform."""
         noise_mod.exclusive(seed, noise=noise)
         self._check_repeat(message_repeat)
+        if speed is not None and duration is not None:
+            stretch_mod.resolve(speed, duration)
         sr, out_sr = rates.check_rate(sr, "sr"), rates.check_rate(out_sr, "out_sr")
         y = self._to_model_rate(audio_or_path, sr)
+        d = self.hps.data
+        step = stretch_mod.resolve(speed, duration, longform.frames_of(y.numel(), d.filter_length, d.hop_length),
+                                   d.hop_length, d.sampling_rate)
         o = self._windowed(window_frames, windows_per_launch).convert(y, src_se, tgt_se, tau=tau, noise=noise,
-                                                                      **noise_mod.kw(seed))
+                                                                      **noise_mod.kw(seed), **stretch_mod.kw(step=step))
         audio = self._finish(o, message, out_sr, message_repeat)
         if output_path is None:
             return audio
@@ -718,7 +758,7 @@ class ToneColorConverter(OpenVoiceBaseClass):
 
     def stream(self, src_se, tgt_se, tau=0.3, window_frames=longform.DEFAULT_STREAM_WINDOW_FRAMES, noise=None, sr_in=None,
                sr_out=None, *, seed=None, wavenet=None, message=None, watermark_hold=watermark_mod.DEFAULT_HOLD,
-               message_repeat=False):
+               message_repeat=False, speed=None, duration=None):
         """A ``longform.ConversionStream``: ``push(samples)`` -> newly finished converted samples (device tensor, maybe
         empty), ``close()`` -> the rest, ``latency_samples`` = ``(window_frames - 1) * hop + n_fft - (n_fft - hop) / 2``
         at the model rate.  ``sr_in`` / ``sr_out``: the rate of the pushes / of the output (None: the model rate); the
@@ -737,27 +777,33 @@ class ToneColorConverter(OpenVoiceBaseClass):
         is the unmarked stream's passed through ``mark_many``, bit for bit; a shorter hold costs signal-to-mark ratio
         (DESIGN.md section 27).  ``message_repeat``: window n carries group n % G for the stream's life, instead of the
         first G windows only.  The samples of a block unfinished at ``close()`` leave unmarked.  ValueError, at the
-        call, for a message without the native watermark and for a hold outside the list."""
+        call, for a message without the native watermark and for a hold outside the list.  ``speed`` / ``duration``:
+        ValueError -- streams are not stretched (``stretch.reject_stream``)."""
+        stretch_mod.reject_stream("stream", speed, duration)
         return self._windowed(window_frames, 1, wavenet).stream(src_se, tgt_se, tau=tau, noise=noise, sr_in=sr_in, sr_out=sr_out,
                                                        message=message, watermark_hold=watermark_hold,
                                                        message_repeat=message_repeat, **noise_mod.kw(seed))
 
     # ---- many streams and recordings in shared launches -------------------------------------------------------------
     def stream_pool(self, tau=0.3, window_frames=longform.DEFAULT_STREAM_WINDOW_FRAMES,
-                    max_windows_per_launch=longform.DEFAULT_POOL_WINDOWS_PER_LAUNCH, *, wavenet=None):
+                    max_windows_per_launch=longform.DEFAULT_POOL_WINDOWS_PER_LAUNCH, *, wavenet=None, speed=None,
+                    duration=None):
         """A ``longform.StreamPool``: many live streams (``open(src_se, tgt_se, noise=None, sr_in=None, sr_out=None,
         seed=None, tau=None, message=None, watermark_hold=16000, message_repeat=False)`` ->
         handle, ``push(h, samples)``, ``close(h)``), whose ready windows one ``step()`` converts together, up to
         ``max_windows_per_launch`` per launch -> ``{handle: newly finished samples}``; streams at rates of their own are
         resampled in one launch per direction and step.  Each stream's output equals a ``stream(...)`` fed the same
         samples with the same noise and rates.  ``tau`` is the pool's default: ``open(..., tau=None)`` gives a stream its
-        own for life, and windows of streams with different ``tau`` still share launches (one value per launch row)."""
+        own for life, and windows of streams with different ``tau`` still share launches (one value per launch row).
+        ``speed`` / ``duration``: ValueError -- streams are not stretched."""
+        stretch_mod.reject_stream("stream_pool", speed, duration)
         return self._windowed(window_frames, 1, wavenet).stream_pool(tau=tau, max_windows_per_launch=max_windows_per_launch)
 
     # ---- low-latency live streams ------------------------------------------------------------------------------------
     def live_stream(self, src_se, tgt_se, tau=0.3, chunk_frames=15, noise=None, sr_in=None, sr_out=None,
                     generator="fp32", *, seed=None, wavenet=None, lookahead_frames=None, crossfade_samples=None,
-                    message=None, watermark_hold=watermark_mod.DEFAULT_HOLD, message_repeat=False):
+                    message=None, watermark_hold=watermark_mod.DEFAULT_HOLD, message_repeat=False, speed=None,
+                    duration=None):
         """A ``live.LiveStream``: the conversion as a cascade of units that carry their recent input as state.
         ``push(samples)`` -> newly finished samples, ``close()`` -> the rest, ``latency_samples`` =
         ``live.live_latency_samples`` (1.45 s at 15 frames).  ``chunk_frames``: a positive multiple of 15 (the Winograd
@@ -787,7 +833,9 @@ class ToneColorConverter(OpenVoiceBaseClass):
 
         ``message`` / ``watermark_hold`` / ``message_repeat`` (keyword only): as for ``stream`` -- the block-wise native
         watermark of what the stream emits (emitted samples are final; the crossfade runs before the mark), at most
-        ``watermark_hold - 1`` samples later, which ``latency_samples`` includes."""
+        ``watermark_hold - 1`` samples later, which ``latency_samples`` includes.  ``speed`` / ``duration``: ValueError --
+        streams are not stretched."""
+        stretch_mod.reject_stream("live_stream", speed, duration)
         from . import live
         d = self.hps.data
         return live.LiveStream(self.model, src_se, tgt_se, tau=tau, chunk_frames=chunk_frames, noise=noise,
@@ -798,7 +846,7 @@ class ToneColorConverter(OpenVoiceBaseClass):
                                message_repeat=message_repeat, **noise_mod.kw(seed))
 
     def live_pool(self, tau=0.3, chunk_frames=15, max_streams_per_launch=32, generator="fp32", *, wavenet=None,
-                  lookahead_frames=None, crossfade_samples=None):
+                  lookahead_frames=None, crossfade_samples=None, speed=None, duration=None):
         """A ``live.LivePool``: many live streams (``open(src_se, tgt_se, noise=None, sr_in=None, sr_out=None,
         seed=None, tau=None, message=None, watermark_hold=16000, message_repeat=False)`` /
         ``push`` / ``close``), every stream with a ready chunk converted by one ``step()`` in launches of up to
@@ -809,7 +857,9 @@ class ToneColorConverter(OpenVoiceBaseClass):
         ``"bf16"``) for the pool; pools of both kinds may be open on one converter at once.  ``wavenet`` (keyword only):
         the WaveNet layers' kernels of the pool's posterior-encoder and flow units, None (follow ``use_bf16_wavenet``),
         ``"fp32"`` or ``"bf16"``.  ``lookahead_frames`` / ``crossfade_samples`` (keyword only, pool-wide like
-        ``chunk_frames``): as for ``live_stream``; the streams' previews share launches like their committed rounds."""
+        ``chunk_frames``): as for ``live_stream``; the streams' previews share launches like their committed rounds.
+        ``speed`` / ``duration``: ValueError -- streams are not stretched."""
+        stretch_mod.reject_stream("live_pool", speed, duration)
         from . import live
         d = self.hps.data
         return live.LivePool(self.model, tau=tau, chunk_frames=chunk_frames, max_streams_per_launch=max_streams_per_launch,
@@ -820,7 +870,8 @@ class ToneColorConverter(OpenVoiceBaseClass):
     @wavenet_keyword
     def convert_many(self, items, src_se, tgt_se, tau=0.3, window_frames=longform.DEFAULT_WINDOW_FRAMES,
                      windows_per_launch=longform.DEFAULT_MANY_WINDOWS_PER_LAUNCH, noise=None, output_paths=None,
-                     message="default", sr=None, out_sr=None, *, seed=None, generator=None, message_repeat=False):
+                     message="default", sr=None, out_sr=None, *, seed=None, generator=None, message_repeat=False,
+                     speed=None, duration=None):
         """``convert_long`` of many recordings with their windows packed ACROSS recordings into launches of up to
         ``windows_per_launch`` (``longform.WindowedConverter.convert_many``).  ``items``: file paths (any rate, decoded
         and resampled like ``convert_long``) or 1-D waveforms at ``sr`` Hz (None: the model rate; one rate, or a list
@@ -834,7 +885,10 @@ class ToneColorConverter(OpenVoiceBaseClass):
         ``convert_long`` of it with the same ``window_frames``, noise and rates.  ``generator`` (keyword only): None
         follows ``use_bf16_generator``, ``"fp32"`` / ``"bf16"`` choose the generator's kernels for this call.  ``tau``:
         one number, or one per item; windows of items with different ``tau`` share launches, and each item still equals
-        its ``convert_long`` with its own ``tau``.  ``message_repeat``: as for ``convert``."""
+        its ``convert_long`` with its own ``tau``.  ``message_repeat``: as for ``convert``.  ``speed`` / ``duration``
+        (keyword only): one value, or a list with one per item (None in a list: that item is left alone); per item one of
+        the two, as for ``convert_long``, which each item still equals.  The stretched items' windows share launches
+        with each other; the watermark and ``out_sr`` act on the stretched waveforms."""
         _lib.check_generator(generator, optional=True)
         self._check_repeat(message_repeat)
         hps = self.hps
@@ -856,9 +910,13 @@ class ToneColorConverter(OpenVoiceBaseClass):
                  else torch.as_tensor(x, dtype=torch.float32).reshape(-1).to(self.device) for x in items]
         paths = [isinstance(x, (str, os.PathLike)) for x in items]
         waves = rates.resample_many(waves, [(None, None) if p else (r, msr) for p, r in zip(paths, srs)], self.device)
+        d = hps.data
+        steps = stretch_mod.resolve_items(speed, duration, [longform.frames_of(w.numel(), d.filter_length, d.hop_length)
+                                                            for w in waves], d.hop_length, msr)
         outs = self._windowed(window_frames, windows_per_launch).convert_many(waves, srcs, tgts, tau=tau, noises=noise,
                                                                               **noise_mod.kw(seed, "seeds"),
-                                                                              **_lib.generator_kw(generator))
+                                                                              **_lib.generator_kw(generator),
+                                                                              **stretch_mod.kw(steps=steps))
         audios = self._finish_many(outs, message, out_srs, message_repeat)
         if output_paths is None:
             return audios

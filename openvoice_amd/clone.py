@@ -28,6 +28,7 @@ speed per sentence.  The contract reads the same with that call as the public pi
 import numpy as np
 
 from . import _lib, longform, rates
+from . import stretch as stretch_mod
 from .engine import item_tau, rows_tau, wavenet_keyword
 
 RECORD_FIELDS = 4           # ov_join_segments_f32's record: (src_off, n, dst_off, gap)
@@ -155,7 +156,7 @@ def sentence_batches(lengths, keys, max_sentences_per_launch=DEFAULT_SENTENCES_P
 
 
 class _Request:
-    __slots__ = ("ids", "speaker", "src_se", "tgt_se", "speed", "out_sr", "tau")
+    __slots__ = ("ids", "speaker", "src_se", "tgt_se", "speed", "out_sr", "tau", "convert_step")
 
 
 class VoiceCloner:
@@ -185,9 +186,11 @@ class VoiceCloner:
         reqs = []
         for i, q in enumerate(requests):
             if isinstance(q, dict):
-                q = (q["ids"], q["speaker"], q["src_se"], q["tgt_se"], q.get("speed", 1.0), q.get("out_sr"), q.get("tau"))
-            if not 4 <= len(q) <= 7:
-                raise ValueError(f"request {i}: (id sequences, speaker, src_se, tgt_se[, speed[, out_sr[, tau]]])")
+                q = (q["ids"], q["speaker"], q["src_se"], q["tgt_se"], q.get("speed", 1.0), q.get("out_sr"), q.get("tau"),
+                     q.get("convert_speed"))
+            if not 4 <= len(q) <= 8:
+                raise ValueError(f"request {i}: (id sequences, speaker, src_se, tgt_se[, speed[, out_sr[, tau[, "
+                                 f"convert_speed]]]])")
             r = _Request()
             r.ids = [np.asarray(s, dtype=np.int64).reshape(-1) for s in q[0]]
             if not r.ids or any(s.shape[0] == 0 for s in r.ids):
@@ -200,6 +203,8 @@ class VoiceCloner:
             r.tau = item_tau(1, q[6]) if len(q) > 6 and q[6] is not None else None      # None: the call's tau=
             if r.tau is not None and not isinstance(r.tau, float):
                 raise _lib.OvError(f"request {i}: tau is one number per request")
+            # convert_speed: the CONVERTER's speed= (the latent stretch of convert_many), distinct from the TTS speed
+            r.convert_step = stretch_mod.step_of(q[7]) if len(q) > 7 and q[7] is not None else None
             reqs.append(r)
         n = len(reqs)
         for name, per_request in (("noise_w", noise_w), ("noise_z", noise_z)):
@@ -276,7 +281,9 @@ class VoiceCloner:
         tgt_se[, speed[, out_sr[, tau]]])`` (or a dict with those keys) -- the sentences as symbol ids (blanks interspersed by
         the caller if the config asks for it), the base speaker's name or id, the two ``[1, 256, 1]`` embeddings, the
         speed (default 1.0), the rate of the result (None: the converter's) and the request's own ``tau`` (None: the
-        ``tau=`` of the call, one number or one per request).  Requests with different ``tau`` still go through ONE
+        ``tau=`` of the call, one number or one per request), and ``convert_speed`` (None: none): the converter's
+        ``speed=`` for this request (``convert_many``: the converted latent stretched in front of the generator, a number
+        in ``[0.5, 2.0]``), distinct from the TTS ``speed``.  Requests with different ``tau`` still go through ONE
         ``convert_many``, their windows sharing its launches.  Explicit noise makes a call
         reproducible: ``noise_w[i][s]`` ``[2, Tx]`` and ``noise_z[i][s]`` ``[192, >= Ty]`` per sentence, ``noise[i]``
         ``[1, 192, >= T]`` per request for the converter; None: drawn on the device.  Returns one float32 numpy array
@@ -305,8 +312,12 @@ class VoiceCloner:
                                          mixed=mixed, **gen_kw)
             msr = int(conv.hps.data.sampling_rate)
             waves = rates.resample_many(waves, [(self.tts_sr, msr)] * len(waves), self.device)
+            steps = None
+            if any(r.convert_step is not None for r in reqs):
+                steps = [stretch_mod.ONE if r.convert_step is None else r.convert_step for r in reqs]
             outs = conv._windowed(window_frames, windows_per_launch).convert_many(
-                waves, [r.src_se for r in reqs], [r.tgt_se for r in reqs], tau=tau, noises=noise, **gen_kw)
+                waves, [r.src_se for r in reqs], [r.tgt_se for r in reqs], tau=tau, noises=noise, **gen_kw,
+                **stretch_mod.kw(steps=steps))
             out_srs = [r.out_sr for r in reqs]
             audios = conv._finish_many(outs, message, out_srs)
         if output_paths is not None:

@@ -427,6 +427,29 @@ void conv1d_wino_multi_f32(const OptTensor& x0, const OptTensor& w0, const OptTe
   finish(ov_conv1d_wino_multi_f32(ps, (int)n, c.stream()), "ov_conv1d_wino_multi_f32");
 }
 
+// records: the DEVICE table; records_host: its HOST copy, which the call checks before it launches (ov_stretch_rows_f32)
+void stretch_rows_f32(const OptTensor& records, const OptTensor& records_host, int64_t n, const OptTensor& src,
+                      int64_t src_elems, const OptTensor& dst, int64_t dst_elems) {
+  Ctx c{"stretch_rows_f32", false};
+  const int64_t* rec = tensor_ptr<int64_t>(records, c, 0);
+  const int64_t* host = nullptr;
+  if (records_host.has_value() && records_host->defined()) {
+    TORCH_CHECK(records_host->device().is_cpu() && records_host->scalar_type() == at::kLong && records_host->is_contiguous(),
+                "stretch_rows_f32: argument 1 must be a contiguous HOST (CPU) int64 tensor");
+    TORCH_CHECK(n >= 0 && records_host->numel() >= 10 * n, "stretch_rows_f32: the host table holds fewer than n records");
+    host = static_cast<const int64_t*>(records_host->data_ptr());
+  }
+  if (records.has_value() && records->defined())
+    TORCH_CHECK(n >= 0 && records->numel() >= 10 * n, "stretch_rows_f32: the device table holds fewer than n records");
+  const float* s = tensor_ptr<float>(src, c, 3);
+  float* d = tensor_ptr<float>(dst, c, 5);
+  if (s) TORCH_CHECK(src_elems <= src->numel(), "stretch_rows_f32: src_elems exceeds the tensor");
+  if (d) TORCH_CHECK(dst_elems <= dst->numel(), "stretch_rows_f32: dst_elems exceeds the tensor");
+  TORCH_CHECK(n >= INT32_MIN && n <= INT32_MAX, "stretch_rows_f32: argument 2 does not fit a 32-bit int");
+  DeviceScope scope(c);
+  finish(ov_stretch_rows_f32(rec, host, (int)n, s, src_elems, d, dst_elems, c.stream()), "ov_stretch_rows_f32");
+}
+
 }  // namespace
 
 TORCH_LIBRARY(openvoice_amd, m) {
@@ -456,6 +479,8 @@ TORCH_LIBRARY(openvoice_amd, m) {
         "Tensor? b1, Tensor(b!)? o1, Tensor? r1, Tensor? a1, Tensor? x2, Tensor? w2, Tensor? b2, Tensor(c!)? o2, Tensor? r2, "
         "Tensor? a2, Tensor? col_limit, int n, int[] ip, float[] fp) -> ()",
         &conv1d_wino_multi_f32);
+  m.def("stretch_rows_f32(Tensor? records, Tensor? records_host, int n, Tensor? src, int src_elems, Tensor(a!)? dst, "
+        "int dst_elems) -> ()", &stretch_rows_f32);
   // ---- device entry points with flat argument lists (schema derived from the C prototype)
   bind_device<&ov_frame_hops_f32>(m, "frame_hops_f32");
   bind_device<&ov_frame_hops_windows_f32>(m, "frame_hops_windows_f32");

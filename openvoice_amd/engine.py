@@ -20,6 +20,7 @@ import torch
 
 from . import _lib
 from . import noise as noise_mod
+from . import stretch as stretch_mod
 from ._lib import EPI_COUPLE, EPI_GATE, EPI_POSTERIOR, EPI_RESSKIP, F_MASK_V, F_OUT2_INIT
 from .generator import (FINAL_LRELU_SLOPE, GENERATOR_MARGIN, LRELU_SLOPE, conv_transpose_as_conv,  # noqa: F401
                         generator_margin_frames, generator_stages, resblock_convs, samples_per_frame, scratch_per_frame)
@@ -148,6 +149,13 @@ def item_tau(B, tau, device=None):
         if not math.isfinite(v):
             bad(f"non-finite element in {vals}")
     return [float(v) for v in vals]
+
+
+def stretch_rows(table, host, n, src, dst):
+    """One ``ov_stretch_rows_f32`` launch: ``table`` the DEVICE int64 records (``stretch.record``), ``host`` their host
+    copy -- the call checks it and raises ``OvError`` (OV_E_BADARG) on a bad record before anything is launched --
+    ``src`` / ``dst`` fp32 device tensors, the records' offsets relative to their first elements."""
+    _lib.call("ov_stretch_rows_f32", table, host, int(n), src, src.numel(), dst, dst.numel())
 
 
 def rows_tau(taus):
@@ -381,6 +389,7 @@ class ConverterEngine:
         self.generator = GeneratorFp32(sd, cfg, dev, self.launcher)
         self.ref_enc = ReferenceEncoder(sd, spec_channels, dev, self.launcher) if "ref_enc.gru.weight_ih_l0" in sd else None
         self._ws, self._graphs = {}, {}
+        self._stretch_ws = None       # (key, workspace): the generator's workspace of a stretched call
         self._live_ws, self._live_ws_bf16, self.live_ws_builds = {}, {}, 0    # live unit scratch, per (unit, rows)
         # (B, T) workspaces kept resident at once, least recently used evicted first.  1 (the default): a new shape
         # frees the previous one.  StreamPool raises it to its ladder of launch sizes so that a varying ready count
@@ -405,8 +414,11 @@ class ConverterEngine:
             return self.launcher.linear(g, wn.cond_w_fused, wn.cond_b_fused)
         return self.launcher.linear(g, wn.cond_w, wn.cond_b)
 
-    def _workspace(self, B, T):
-        key = (B, T)
+    def _workspace(self, B, T, frames_only=False):
+        """The workspace of a (B, T) conversion.  ``frames_only`` (a stretched call, whose generator runs on another
+        shape out of ``generator_workspace``): the frame-rate tensors alone, a shape of its own in the same LRU -- so a
+        stretched call never holds decoder scratch for the frames it does not generate."""
+        key = (B, T, "frames") if frames_only else (B, T)
         ws = self._ws.pop(key, None)
         if ws is not None:
             self._ws[key] = ws     # re-inserted last: the dict is the LRU order
@@ -422,7 +434,8 @@ class ConverterEngine:
             lat = f(3, B, C, Tp)         # the three latents in ONE allocation: one ov_unpad_rows_f32 returns them dense
             ws = dict(Tp=Tp, mask=f(B, Tp), h=f(B, H, Tp), h2=f(B, H, Tp), acts=f(B, H, Tp), skip=f(B, H, Tp), noise=f(B, C, Tp),
                       lat=lat, z=lat[0], z_p=lat[1], z_hat=lat[2])
-            self.generator.add_workspace(ws, B, T)       # pre, dec, dec_extra
+            if not frames_only:
+                self.generator.add_workspace(ws, B, T)       # pre, dec, dec_extra
             self._ws[key] = ws
         return ws
 
@@ -512,7 +525,7 @@ class ConverterEngine:
     @torch.no_grad()
     @on_own_device
     def voice_conversion(self, spec, spec_lengths, sid_src, sid_tgt, tau=1.0, noise=None, skip_padding=False, *,
-                         seed=None, generator=None, wavenet=None):
+                         seed=None, generator=None, wavenet=None, stretch=None):
         """Same contract as the reference seam (openvoice/models.py:492-499):
         ``(o_hat [B,1,256T], y_mask [B,1,T], (z, z_p, z_hat) [B,192,T])``.  ``noise`` [B,192,T]
         replaces the reference's ``torch.randn_like`` draw (models.py:220); when omitted it is drawn
@@ -532,12 +545,20 @@ class ConverterEngine:
         item -- a sequence (uploaded once per call as a float32 device vector) or a 1-D float32 device tensor of ``B``
         values (used as it is, nothing synchronises); see ``item_tau``.  Per item it reaches the one place ``tau``
         enters, the ``q_proj`` epilogue, as ``ov_conv1d_params.scale_b``: the same launches as with a number, and item
-        ``b`` holds the bits of the batch run with the number ``tau[b]``."""
+        ``b`` holds the bits of the batch run with the number ``tau[b]``.  ``stretch`` (None: everything above,
+        launch for launch): one entry per item, a step (``stretch.step_of(speed)``) or, for a window of a long
+        recording, ``(step, i0, j0, n_out)`` -- the masked ``z_hat`` is resampled along time by ``ov_stretch_rows_f32``
+        (the project's own definition: ``openvoice_amd/stretch.py``) between the reverse flow and the generator, which
+        then runs on ``T_out[b]`` frames per item (length-aware work lists when they differ).  ``o_hat``, ``y_mask``
+        and the lengths it implies are the stretched ones; ``z``, ``z_p`` and ``z_hat`` are returned unstretched;
+        ``tau``, ``seed`` and ``noise`` act before the stretch.  The item lengths are read on the host (one copy of
+        ``spec_lengths`` when it lives on the device)."""
         use_bf16 = self._bf16_on
         if _lib.check_generator(generator, optional=True) is not None:
             use_bf16 = generator == "bf16"
         with self.wavenet_scope(wavenet):
-            return self._voice_conversion(spec, spec_lengths, sid_src, sid_tgt, tau, noise, skip_padding, seed, use_bf16)
+            return self._voice_conversion(spec, spec_lengths, sid_src, sid_tgt, tau, noise, skip_padding, seed, use_bf16,
+                                          stretch)
 
     def _tau_args(self, B, tau):
         """``(scale, scale_b)`` of a ``q_proj`` launch of ``B`` rows from a ``tau=`` argument (``item_tau``)."""
@@ -548,7 +569,8 @@ class ConverterEngine:
             tau = torch.tensor(tau, dtype=torch.float32).to(self.device)
         return 1.0, tau
 
-    def _voice_conversion(self, spec, spec_lengths, sid_src, sid_tgt, tau, noise, skip_padding, seed, use_bf16):
+    def _voice_conversion(self, spec, spec_lengths, sid_src, sid_tgt, tau, noise, skip_padding, seed, use_bf16,
+                          stretch=None):
         dev = self.device
         spec = spec.to(dev, torch.float32)
         B, F, T = spec.shape
@@ -558,11 +580,13 @@ class ConverterEngine:
         if not (spec.stride(2) == 1 and spec.stride(1) >= T and spec.stride(0) >= F * spec.stride(1)):
             spec = spec.contiguous()
         C = self.inter
+        if stretch is not None:       # the stretch's records are built on the host: the lengths are read before any launch
+            stretch = self._stretch_plan(stretch, spec_lengths, B, T)
         lengths = spec_lengths.to(dev, torch.int64).contiguous()
         g_src = sid_src.to(dev, torch.float32).reshape(sid_src.shape[0], -1).contiguous()
         g_tgt = sid_tgt.to(dev, torch.float32).reshape(sid_tgt.shape[0], -1).contiguous()
         noise_mod.exclusive(seed, noise=noise)
-        ws = self._workspace(B, T)
+        ws = self._workspace(B, T, frames_only=stretch is not None)
         Tp, mask = ws["Tp"], ws["mask"]
         if seed is not None:
             self.seed_noise(ws["noise"], seed, B, T, Tp)
@@ -582,10 +606,34 @@ class ConverterEngine:
         self._frames(ws, 0, B, spec, conds, tau)
         z, z_p, z_hat = ws["z"], ws["z_p"], ws["z_hat"]
         # ---- generator (models.py:272-291); z_hat * y_mask is the identity (z_hat already masked) --
+        if stretch is None:
+            o_hat = self.generate(z_hat, T, lengths, conds["d"], g_tgt, ws, skip_padding, use_bf16)
+            out_mask, T_out = mask, T
+        else:
+            # the masked z_hat, resampled along time in front of the generator (and of the bf16 generator's layout change)
+            zs, gws, lengths_out, T_out, ragged = self._stretch(z_hat, Tp, stretch, B)
+            o_hat = self.generate(zs, T_out, lengths_out, conds["d"], g_tgt, gws, ragged, use_bf16)
+            out_mask = gws["mask"]
+            _lib.call("ov_sequence_mask_f32", lengths_out, out_mask, B, T_out, gws["Tp"])
+        # fresh dense tensors for the caller (the workspace is reused by the next call): padded rows -> [.., T]
+        dense = torch.empty(3, B, C, T, dtype=torch.float32, device=dev)
+        _lib.call("ov_unpad_rows_f32", ws["lat"], dense, 3 * B * C, T, Tp)
+        y_mask = torch.empty(B, 1, T_out, dtype=torch.float32, device=dev)
+        _lib.call("ov_unpad_rows_f32", out_mask, y_mask, B, T_out, ws["Tp"] if stretch is None else gws["Tp"])
+        return o_hat, y_mask, (dense[0], dense[1], dense[2])
+
+    def generate(self, z_rows, T, lengths, cond_d, g_tgt, ws, skip_padding=False, use_bf16=False):
+        """The generator on a masked latent in the fp32 rows layout: ``z_rows`` [B, inter, ld] with ``T`` valid columns
+        per row, ``lengths`` int64 [B] on the device, ``cond_d`` = ``generator.cond(g_tgt)``, ``ws`` a workspace that
+        holds the generator's entries for (B, T) (``_workspace`` or ``generator_workspace``) -> ``o_hat`` [B, 1, T *
+        spf].  ``skip_padding``: the fp32 generator computes ``length + limit_margin`` frames per item and writes zeros
+        beyond ``length``; the bf16 generator computes the padded batch and the tail is masked.  This is the generator
+        step of ``voice_conversion``, on ``z_hat`` or -- with ``stretch=`` -- on the stretched ``z_hat``."""
+        B, dev = z_rows.shape[0], self.device
         if use_bf16:
             g_d = self._g(g_tgt)
             o_hat = self.launcher.timed("gen_bf16", 0.0,
-                                        lambda: self.bf16_generator().decode(z_hat[:, :, :T], g_d.unsqueeze(-1)))
+                                        lambda: self.bf16_generator().decode(z_rows[:, :, :T], g_d.unsqueeze(-1)))
             if skip_padding:
                 # the bf16 generator has no length-aware work lists (it computes the padded batch); the contract of
                 # skip_padding -- every sample beyond an utterance's own length is zero -- is kept by masking
@@ -593,13 +641,66 @@ class ConverterEngine:
                 o_hat.masked_fill_(torch.arange(o_hat.shape[2], device=dev).view(1, 1, -1) >= keep_samples, 0.0)
         else:
             limits = self.generator.frame_limits(lengths, T) if skip_padding else None
-            o_hat = self.generator.decode(z_hat, conds["d"], ws, T=T, limits=limits)
-        # fresh dense tensors for the caller (the workspace is reused by the next call): padded rows -> [.., T]
-        dense = torch.empty(3, B, C, T, dtype=torch.float32, device=dev)
-        _lib.call("ov_unpad_rows_f32", ws["lat"], dense, 3 * B * C, T, Tp)
-        y_mask = torch.empty(B, 1, T, dtype=torch.float32, device=dev)
-        _lib.call("ov_unpad_rows_f32", mask, y_mask, B, T, Tp)
-        return o_hat, y_mask, (dense[0], dense[1], dense[2])
+            o_hat = self.generator.decode(z_rows, cond_d, ws, T=T, limits=limits)
+        return o_hat
+
+    # ---- speed= / duration=: the stretch between the reverse flow and the generator (openvoice_amd/stretch.py) ------
+    def _stretch_plan(self, stretch, spec_lengths, B, T):
+        """Per item ``(step, t_in, i0, j0, n_out)`` from ``voice_conversion``'s ``stretch=``: a step stretches the whole
+        item (``i0 = j0 = 0``, ``n_out = T_out``), a ``(step, i0, j0, n_out)`` tuple is a window of a long recording."""
+        if len(stretch) != B:
+            raise ValueError(f"stretch: one entry per item ({B}), got {len(stretch)}")
+        lens = [min(int(n), T) for n in torch.as_tensor(spec_lengths).reshape(-1).tolist()]
+        plan = []
+        for item, t_in in zip(stretch, lens):
+            if isinstance(item, (tuple, list)):
+                step, i0, j0, n_out = (int(v) for v in item)
+            else:
+                step, i0, j0, n_out = int(item), 0, 0, stretch_mod.t_out(max(t_in, 1), int(item))
+            if not stretch_mod.ONE // 2 <= step <= 2 * stretch_mod.ONE:
+                raise ValueError(f"stretch: step {step} outside [2^31, 2^33]")
+            plan.append((step, max(t_in, 1), i0, j0, n_out))
+        return plan
+
+    def generator_workspace(self, B, T):
+        """The generator's own workspace of a (B, T) launch -- what ``generate`` needs and nothing of the frame-rate
+        part: the conv_pre output and the decoder scratch (``GeneratorFp32.add_workspace``), the stretched latent ``zs``
+        [B, inter, Tp] and its mask.  One shape stays resident (the stretched path's counterpart of ``_workspace``, next
+        to the frames-only workspace of the call: together what an unstretched conversion of ``max(T, T_out)`` frames
+        holds at most); ``release_stretch_workspace`` frees it."""
+        key = (B, T)
+        if self._stretch_ws is None or self._stretch_ws[0] != key:
+            Tp = padded_frames(T)
+            f = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=self.device)
+            gws = dict(Tp=Tp, zs=f(B, self.inter, Tp), mask=f(B, Tp))
+            self.generator.add_workspace(gws, B, T)
+            self._stretch_ws = (key, gws)
+        return self._stretch_ws[1]
+
+    def release_stretch_workspace(self):
+        """Drop the generator workspace a stretched call left resident (the next stretched call builds its own)."""
+        self._stretch_ws = None
+
+    def _stretch(self, z_hat, Tp, plan, B):
+        """``ov_stretch_rows_f32`` of the workspace's masked ``z_hat`` [B, inter, Tp] into the generator workspace's
+        ``zs``: one record per item, one launch.  Returns ``(zs, workspace, lengths_out int64 [B] on the device, T_out of
+        the batch, whether the items' output lengths differ)``.  Columns beyond an item's ``n_out`` are zero, as the
+        masked latent's are."""
+        C = self.inter
+        n_outs = [p[4] for p in plan]
+        T_out = max(n_outs)
+        gws = self.generator_workspace(B, T_out)
+        zs, Tp2 = gws["zs"], gws["Tp"]
+        ragged = any(n != T_out for n in n_outs)
+        if ragged:
+            zs.zero_()                      # a shorter item's tail: zero, whatever the previous call left there
+        recs = [stretch_mod.record(b * C * Tp, b * C * Tp2, C, Tp, Tp2, t_in, i0, j0, n_out, step)
+                for b, (step, t_in, i0, j0, n_out) in enumerate(plan)]
+        # records and output lengths in one host table: one host -> device copy
+        host = torch.tensor([v for r in recs for v in r] + n_outs, dtype=torch.int64)
+        table = host.to(self.device)
+        stretch_rows(table, host, B, z_hat, zs)
+        return zs, gws, table[10 * B:], T_out, ragged
 
     def seed_noise(self, dst, seed, B, T, ld, purpose=noise_mod.PURPOSE_POSTERIOR):
         """Counter-based noise of ``seed`` (``noise.rows``: one ``(seed, stream, first frame)`` per row) into the first

@@ -26,6 +26,7 @@ import torch
 from . import _lib, rates
 from .engine import item_tau, rows_tau, wavenet_keyword
 from . import noise as noise_mod
+from . import stretch as stretch_mod
 from .streams import PushedPool, WaveBuffer
 from . import watermark as watermark_mod
 from .generator import GENERATOR_MARGIN, generator_margin_frames, generator_stages, samples_per_frame
@@ -71,6 +72,25 @@ def context_frames(cfg):
     reach += max(GENERATOR_MARGIN, generator_margin_frames(cfg))
     g = winograd_grid_frames(cfg)
     return -(-reach // g) * g
+
+
+def frame_reach_frames():
+    """One-sided reach, in frames, of the frame-rate part of a conversion -- the posterior encoder's WaveNet and the
+    flow forward and reverse (``context_frames`` without the generator's term): 96."""
+    return ENC_Q_LAYERS * (ENC_Q_KERNEL - 1) // 2 + 2 * N_FLOWS * FLOW_LAYERS * (FLOW_KERNEL - 1) // 2
+
+
+def generator_context_frames(cfg):
+    """The generator's term of ``context_frames``: ``max(GENERATOR_MARGIN, generator_margin_frames(cfg))`` frames AT THE
+    GENERATOR'S INPUT RATE -- output frames of a stretched conversion."""
+    return max(GENERATOR_MARGIN, generator_margin_frames(cfg))
+
+
+def stretch_context_frames(cfg, step):
+    """``context_frames`` of a conversion whose latent is stretched by ``step`` in front of the generator
+    (``stretch.context_frames``): the generator's reach is counted in OUTPUT frames, which are ``speed`` source frames
+    each, so the source-frame context grows with ``max(1, speed)``; 120 at speed <= 1, 150 at speed 2."""
+    return stretch_mod.context_frames(frame_reach_frames(), generator_context_frames(cfg), step, winograd_grid_frames(cfg))
 
 
 def plan_windows(T, window_frames, context, grid=1):
@@ -290,7 +310,7 @@ class WindowedConverter:
 
     @torch.no_grad()
     @wavenet_keyword
-    def convert_many(self, waves, src_ses, tgt_ses, tau=0.3, noises=None, *, seeds=None, generator=None):
+    def convert_many(self, waves, src_ses, tgt_ses, tau=0.3, noises=None, *, seeds=None, generator=None, steps=None):
         """``convert`` of many recordings with their windows packed across recordings into launches of up to
         ``windows_per_launch`` (``ov_frame_hops_multi_f32``: each window framed from its own recording).  ``src_ses`` /
         ``tgt_ses``: one embedding per recording; ``noises``: None or one ``[1, inter, >= T_i]`` (or None) per
@@ -303,13 +323,36 @@ class WindowedConverter:
         ``generator`` (keyword only): None follows the engine's ``use_bf16_generator`` switch, ``"fp32"`` / ``"bf16"``
         choose the generator's kernels for this call (``ConverterEngine.voice_conversion``); the windows of a launch
         have one length, so the bf16 generator runs them as the dense batch they are.  ``tau``: one number, or one per
-        recording (``engine.item_tau``); every window carries the ``tau`` of its recording."""
+        recording (``engine.item_tau``); every window carries the ``tau`` of its recording.  ``steps`` (None: all of the
+        above): one ``stretch.step_of(speed)`` per recording (``stretch.ONE``: left alone); the stretched recordings run
+        ``_convert_stretched`` and share launches with each other, the others run as always."""
         _lib.check_generator(generator, optional=True)
         dev = self._device()
         n = len(waves)
         tau = item_tau(n, tau)
         if torch.is_tensor(tau):        # windows are regrouped on the host: a device vector is read back once
             tau = tau.tolist()
+        if steps is not None and any(int(s) != stretch_mod.ONE for s in steps):
+            if len(steps) != n or len(src_ses) != n or len(tgt_ses) != n or (noises is not None and len(noises) != n):
+                raise ValueError("convert_many: one src / tgt embedding, step (and noise) per recording")
+            noise_mod.exclusive(seeds, noises=noises)
+            seeds = [None] * n if seeds is None else noise_mod.per_item(seeds, n)
+            outs = [None] * n
+            # two subsets, each through its own path: the recordings left alone (today's launches) and the stretched ones
+            for stretched in (False, True):
+                idx = [i for i in range(n) if (int(steps[i]) != stretch_mod.ONE) == stretched]
+                if not idx:
+                    continue
+                pick = lambda xs: [xs[i] for i in idx]
+                sub = dict(tau=pick(tau) if isinstance(tau, list) else tau, noises=None if noises is None else pick(noises),
+                           **noise_mod.kw(None if seeds[0] is None else pick(seeds), "seeds"), **_lib.generator_kw(generator))
+                if stretched:
+                    res = self._convert_stretched(pick(waves), pick(src_ses), pick(tgt_ses), steps=pick(steps), **sub)
+                else:
+                    res = self.convert_many(pick(waves), pick(src_ses), pick(tgt_ses), **sub)
+                for i, o in zip(idx, res):
+                    outs[i] = o
+            return outs
         if len(src_ses) != n or len(tgt_ses) != n or (noises is not None and len(noises) != n):
             raise ValueError("convert_many: one src / tgt embedding (and noise) per recording")
         noise_mod.exclusive(seeds, noises=noises)
@@ -330,14 +373,82 @@ class WindowedConverter:
         self._run_jobs([w for w, _, _ in items], jobs, tau, out, self.windows_per_launch, generator=generator)
         return [out[o * self.spf:(o + T) * self.spf] for o, (_, T, _) in zip(offs, items)]
 
+    def _convert_stretched(self, waves, src_ses, tgt_ses, tau, steps, noises=None, seeds=None, generator=None):
+        """``convert_many`` of recordings that are all stretched (``steps[i]``: recording i's step).  Windows are cut on
+        SOURCE frames as always (``plan_windows``, with the context ``stretch_context_frames`` derives for the step);
+        window w of a recording is framed and converted like any window, and inside ``voice_conversion`` its latent is
+        stretched with its global position (``stretch=(step, f0, ja, n)``: source column 0 is frame ``f0``, the output
+        frames ``[ja, ja + n)`` are made -- ``stretch.plan_windows``) before the generator runs on those ``n`` frames;
+        the window then emits the output frames whose ``i`` lies in its core.  Windows of equal ``(Tw, n)`` share
+        launches of up to ``windows_per_launch``; every launch is a dense batch.  Never graph-captured.  Returns the
+        stretched waveforms, ``stretch.t_out(T_i, steps[i]) * spf`` samples each (views of one packed output)."""
+        dev = self._device()
+        n_items = len(waves)
+        seeds = [None] * n_items if seeds is None else seeds
+        items = [self._prepare(w, None if noises is None else noises[i], dev, **noise_mod.kw(seeds[i]))
+                 for i, w in enumerate(waves)]
+        R, M = frame_reach_frames(), generator_context_frames(self.cfg)
+        jobs, offs, acc = [], [], 0
+        for i, (wave, T, noise) in enumerate(items):
+            step = int(steps[i])
+            offs.append(acc)
+            Tw = min(T, self.window_frames)
+            plan = plan_windows(T, self.window_frames, stretch_context_frames(self.cfg, step), self.grid)
+            for (f0, lo, hi), (ja, n, j_lo, j_hi) in zip(plan, stretch_mod.plan_windows(plan, T, self.window_frames, step,
+                                                                                       R, M)):
+                nz = noise + (f0,) if seeds[i] is not None else noise[:, :, f0:f0 + Tw]
+                jobs.append((i, f0, Tw, ja, n, j_lo, j_hi, nz, src_ses[i], tgt_ses[i], acc + j_lo, step))
+            acc += stretch_mod.t_out(T, step)
+        out = torch.empty(acc * self.spf, dtype=torch.float32, device=dev)
+        sources = [w for w, _, _ in items]
+        bases, b = [], 0
+        for x in sources:
+            bases.append(b)
+            b += x.numel()
+        pool = sources[0] if len(sources) == 1 else torch.cat(sources)
+        groups = {}
+        for j in jobs:
+            groups.setdefault((j[2], j[4]), []).append(j)
+        for (Tw, n), js in groups.items():
+            for c0 in range(0, len(js), self.windows_per_launch):
+                rows = js[c0:c0 + self.windows_per_launch]
+                W = len(rows)
+                recs = [(bases[j[0]], sources[j[0]].numel(), j[1]) for j in rows]
+                # the stitch's (first_frame, core_lo, core_hi), in output frames of the packed output
+                recs += [(j[10] - (j[5] - j[3]), j[10], j[10] + j[6] - j[5]) for j in rows]
+                recs_dev = torch.tensor(recs, dtype=torch.int64).to(dev)
+                if torch.is_tensor(rows[0][7]):
+                    nz, seed = torch.cat([j[7] for j in rows]), None
+                else:
+                    nz, seed = None, [j[7] for j in rows]
+                g_src = torch.cat([j[8].reshape(1, -1, 1) for j in rows])
+                g_tgt = torch.cat([j[9].reshape(1, -1, 1) for j in rows])
+                launch_tau = rows_tau([tau[j[0]] for j in rows]) if isinstance(tau, list) else tau
+                spec = self._spectrogram().windows_multi(pool, recs_dev[:W], Tw)
+                o_hat = self.model.voice_conversion(spec, torch.full((W,), Tw, dtype=torch.int64), sid_src=g_src,
+                                                    sid_tgt=g_tgt, tau=launch_tau, noise=nz,
+                                                    stretch=[(j[11], j[1], j[3], n) for j in rows], **noise_mod.kw(seed),
+                                                    **_lib.generator_kw(generator), **_lib.wavenet_kw(self.wavenet))[0]
+                _lib.call("ov_stitch_window_cores_f32", o_hat, recs_dev[W:], W, n, self.spf, out, out.numel(), 0)
+        return [out[o * self.spf:(o + stretch_mod.t_out(T, int(steps[i]))) * self.spf]
+                for i, (o, (_, T, _)) in enumerate(zip(offs, items))]
+
     @torch.no_grad()
     @wavenet_keyword
-    def convert(self, wave, src_se, tgt_se, tau=0.3, noise=None, *, seed=None):
+    def convert(self, wave, src_se, tgt_se, tau=0.3, noise=None, *, seed=None, step=None):
         """``wave``: 1-D float32 waveform at the model rate (host or device).  ``noise``: ``[1, inter, >= T]`` or None
         (then ``torch.randn(1, inter, T)`` on the device: the stream of a seeded one-pass ``convert``); ``seed``
         (instead of ``noise``): the counter-based noise of ``(seed, 0)`` (or of a pair), each window generating its own
         frames -- no ``[1, inter, T]`` tensor exists.  Returns the converted waveform ``[spf * T]`` on the device (spf =
-        the generator's samples per frame = hop), ``T`` = frames of ``spectrogram_torch``."""
+        the generator's samples per frame = hop), ``T`` = frames of ``spectrogram_torch``.  ``step`` (None or
+        ``stretch.ONE``: all of the above): the recording stretched by ``stretch.step_of(speed)``
+        (``_convert_stretched``) -> ``[spf * stretch.t_out(T, step)]``, the one-pass ``voice_conversion(stretch=[step])``
+        of the recording: bit for bit with direct kernels, within the cross-family bar with the defaults."""
+        if step is not None and int(step) != stretch_mod.ONE:
+            noise_mod.exclusive(seed, noise=noise)
+            return self._convert_stretched([wave], [src_se], [tgt_se], tau, [int(step)],
+                                           noises=None if noise is None else [noise],
+                                           seeds=None if seed is None else [noise_mod.check_seed(seed)])[0]
         dev = self._device()
         wave, T, noise = self._prepare(wave, noise, dev, **noise_mod.kw(seed))
         N = wave.numel()

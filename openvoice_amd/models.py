@@ -104,7 +104,7 @@ class SynthesizerTrn(nn.Module):
 
     @wavenet_keyword
     def voice_conversion(self, y, y_lengths, sid_src, sid_tgt, tau=1.0, noise=None, graph=False, skip_padding=False, *,
-                         seed=None, generator=None):
+                         seed=None, generator=None, stretch=None):
         """reference: openvoice/models.py:492-499; ``noise`` is the explicit form of the
         reference's ``randn_like`` draw (optional), ``seed`` the counter-based one (``noise.py``: an int ``s`` gives
         row ``b`` the stream ``(s, b)``; or one seed / pair per row).  ``graph=True`` replays the launch sequence of
@@ -116,7 +116,9 @@ class SynthesizerTrn(nn.Module):
         follows the engine's ``use_bf16_generator`` switch; ``"fp32"`` / ``"bf16"`` choose for this call (eager calls
         only: a captured graph follows the switch).  ``tau``: one number, or one per item (a sequence or a 1-D float32
         device tensor of ``B`` values, ``engine.item_tau``); graphs are keyed on one ``tau``, so a per-item ``tau`` runs
-        eagerly even with ``graph=True`` and returns fresh tensors."""
+        eagerly even with ``graph=True`` and returns fresh tensors.  ``stretch`` (None: all of the above): one step per
+        item, the latent resampled along time in front of the generator (``ConverterEngine.voice_conversion``,
+        ``openvoice_amd/stretch.py``); a stretched call never uses a captured graph."""
         _lib.check_generator(generator, optional=True)
         eng = self.engine()
         if self.n_speakers != 0:
@@ -124,6 +126,9 @@ class SynthesizerTrn(nn.Module):
         if graph and generator is not None:
             raise _lib.OvError("voice_conversion: generator= chooses per eager call; a captured graph (graph=True) follows "
                                "use_bf16_generator")
+        if stretch is not None:
+            return eng.voice_conversion(y, y_lengths, sid_src, sid_tgt, tau=tau, noise=noise, skip_padding=skip_padding,
+                                        stretch=stretch, **noise_mod.kw(seed), **_lib.generator_kw(generator))
         if graph and isinstance(item_tau(y.shape[0], tau), float):
             g = eng.graphed(y.shape[0], y.shape[2], tau, sid_src.shape[0], sid_tgt.shape[0], skip_padding=skip_padding)
             return g(y, y_lengths, sid_src, sid_tgt, noise=noise, **noise_mod.kw(seed))
